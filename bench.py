@@ -29,6 +29,9 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JS
     warm-up is checkpointed (smx_save, outside the timed region) and the reference continues it (ref_driver --load) at the same counts,
     1 core pinned; an all-cores line (independent processes from that state -- the reference has no threads) and the "as-is" line.
   * "parity_vs_reference": z-scores of the timed engine against the reference itself (tools/p2_reference.py: 1024^2, 16 control streams).
+  * --dump-outputs DIR: after the timed steps, what the headline's last timed tick left in the map -- per cell: height, the soil type on top,
+    the water / track / wind frequency maps, and the cell indices themselves -- as DIR/<name>.npy in float32 / float64 (collect_outputs; every
+    cell up to 1024^2, a fixed seeded sample of 2^20 cells beyond: 36 MB). The inputs depend on the arguments alone, so two builds compare array for array.
   * N > 1: one process per GPU. The throughput engines run ONE map in N column strips, driven inside the library (smx_strips_*: halo
     columns + migrating particles point to point with ncclSend/ncclRecv on device buffers, live count by ncclAllReduce). Default "scaling": "weak" -- the map is
     (N*size) x size, every GPU owns a size x size strip and its share of N x the particles, so per-GPU work is the N=1 line's;
@@ -159,8 +162,44 @@ def cpu_baseline(soil: str, size: int, nwater: int, nwind: int, ticks: int, pool
     return out
 
 
+DUMP_CELLS = 1 << 20        # --dump-outputs: cells written per array (all of them on maps up to 1024^2, a fixed sample beyond)
+DUMP_SEED = 20240917        # the sample's seed: the same cells in every run and every build
+DUMP_MAX_BYTES = 64 << 20
+
+
+def output_sample(ncells: int, cap: int = DUMP_CELLS):
+    """Cell indices (y*dimx+x, ascending) the dump covers: every cell, or a fixed seeded sample of `cap` cells on larger maps."""
+    import numpy as np
+    if ncells <= cap:
+        return np.arange(ncells, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ncells, size=cap, replace=False))
+
+
+def collect_outputs(m) -> dict:
+    """What a caller of the timed path receives from the map after its last tick, per cell: height (smx_read_heights), the soil type
+    on top (smx_read_surface) and the three frequency maps (Layermap.frequency) -- on the cells of output_sample, as float32 / float64."""
+    import numpy as np
+    idx = output_sample(m.dimx * m.dimy)
+    wf, wt, wi = m.frequency()
+    return {"cell_index": idx.astype(np.float64), "height": m.heights()[idx], "surface_type": m.surface()[idx].astype(np.float64),
+            "water_frequency": wf[idx], "water_track": wt[idx], "wind_frequency": wi[idx]}
+
+
+def write_outputs(arrays: dict, out_dir: str) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, DUMP_MAX_BYTES at most in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"outputs of {total} bytes exceed the {DUMP_MAX_BYTES}-byte dump limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"output {name}: dtype {a.dtype} (float32 or float64 only)")
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def measure(cfg, soil, n, seed, nwater, nwind, dowind, engine, pool, device, steps, warmup, barrier=None, rand_seed=None, keep_heights=False, save_after_warmup=None,
-            water_generations=None, save_after_window=None, water_stagger=None):
+            water_generations=None, save_after_window=None, water_stagger=None, outputs=False):
     """warmup ticks, then `steps` timed ticks on a fresh context. Returns a dict (rank-local numbers).
     rand_seed: re-seed the libc stream after the terrain is built (same map, another rand() stream: the parity control)."""
     from soilmachine_amd.machine import SoilMachine
@@ -218,6 +257,8 @@ def measure(cfg, soil, n, seed, nwater, nwind, dowind, engine, pool, device, ste
     }
     if keep_heights:
         r["heights"] = m.heights()
+    if outputs:                                                 # what the timed window's last tick left in the map (outside the timed region)
+        r["outputs"] = collect_outputs(m)
     if save_after_window:
         # OUTSIDE the timed region: the state the window ends with is checkpointed and ONE more tick runs on the device -- the tick the CPU
         # baseline's second sample continues from that checkpoint (the tick grows inside the window: lakes accumulate)
@@ -487,6 +528,9 @@ def main():
                                                                         "default: the engine's own (8 since round 6: inside the reference's spread on all eight figures at the headline workload, "
                                                                         "profiles/r06_p2_reference_4096.json); 4 = round 5's default, 1 = round 4's schedule: faster, outside it)")
     ap.add_argument("--water-stagger", type=int, default=None, help="relaxed engine: the water generations born this many epochs apart inside ONE phase (smx_set_water_stagger; 0 = one after the other; default: the library's)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last step left in the map as DIR/<name>.npy (write_outputs); "
+                         "single-process runs only (refused on the strips path, N > 1)")
     args = ap.parse_args()
 
     import torch
@@ -533,13 +577,18 @@ def main():
         if not args.strong:
             dimx, nwater, nwind = n * world, nwater * world, nwind * world
             pool = max(10_000_000, 3 * dimx * n)
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the single-process path only")
         r = measure_strips(cfg, dimx, n, nwater, nwind, pool, local_rank, args.steps, args.warmup, dist, barrier, torch, engine)
     else:
         want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "soil_ref_lean"))
         ckpt = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"soilmx_bench_{os.getpid()}.smx") if want_cpu else None
         ckpt2 = (ckpt + ".end") if (ckpt and args.steps > 1) else None
         r = measure(cfg, soil, n, seed, nwater, nwind, nwind > 0, engine, pool, local_rank, args.steps, args.warmup, barrier, save_after_warmup=ckpt,
-                    water_generations=args.water_generations if throughput else None, save_after_window=ckpt2, water_stagger=args.water_stagger if throughput else None)
+                    water_generations=args.water_generations if throughput else None, save_after_window=ckpt2, water_stagger=args.water_stagger if throughput else None,
+                    outputs=bool(args.dump_outputs) and rank == 0)
+        if "outputs" in r:
+            write_outputs(r.pop("outputs"), args.dump_outputs)
         if ckpt and not os.path.exists(ckpt):
             ckpt = None
         if ckpt2 and not os.path.exists(ckpt2):

@@ -95,9 +95,8 @@ class Layermap:
         nc, ns = self.dimx * self.dimy, int(ns.value)
         count = np.zeros(nc, np.uint32); ty = np.zeros(ns, np.uint32)
         size = np.zeros(ns); floor = np.zeros(ns); sat = np.zeros(ns)
-        wf = np.zeros(nc, np.float32); wt = np.zeros(nc, np.float32); wi = np.zeros(nc, np.float32)
         self._chk(self.L.smx_export_columns(self.h, capi.ptr(count), capi.ptr(ty), capi.ptr(size), capi.ptr(floor), capi.ptr(sat)))
-        self._chk(self.L.smx_read_frequency(self.h, capi.ptr(wf), capi.ptr(wt), capi.ptr(wi)))
+        wf, wt, wi = self.frequency()
         c = self.counters()
         return Snapshot(self.dimx, self.dimy, self.cfg.SCALE, len(self.cfg.soils), c["rand_calls"], c["pool_free"],
                         count, ty, size, floor, sat, wf, wt, wi)
@@ -106,6 +105,13 @@ class Layermap:
         out = np.zeros(self.dimx * self.dimy)
         self._chk(self.L.smx_read_heights(self.h, capi.ptr(out)))
         return out
+
+    def frequency(self):
+        """The water frequency, water track and wind frequency maps (f32 per cell, index y*dimx+x)."""
+        nc = self.dimx * self.dimy
+        wf, wt, wi = (np.zeros(nc, np.float32) for _ in range(3))
+        self._chk(self.L.smx_read_frequency(self.h, capi.ptr(wf), capi.ptr(wt), capi.ptr(wi)))
+        return wf, wt, wi
 
     def surface(self) -> np.ndarray:
         out = np.zeros(self.dimx * self.dimy, np.uint32)

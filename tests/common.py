@@ -50,3 +50,36 @@ SNAP_CASES = {
     "rocksand48x80": ("rocksand.soil", 3, True, [0, 5]),
     "painted64": ("painted.soil", 1, True, [0, 5]),
 }
+
+
+SNAPSHOT_DTYPES = {"count": "<u4", "type": "<u4", "size": "<f8", "floor": "<f8", "sat": "<f8", "wfreq": "<f4", "wtrack": "<f4", "windfreq": "<f4"}
+
+
+def snapshot_hashes(s: Snapshot) -> dict:
+    """A state as stored vectors of tests/golden: dims, rand() draws and the SHA-256 of every array's bytes -- equal exactly when
+    snapshot.compare finds nothing (it compares the same arrays bit for bit)."""
+    import hashlib
+    out = {"dimx": int(s.dimx), "dimy": int(s.dimy), "rand_calls": int(s.rand_calls), "nsec": int(s.nsec)}
+    for name, dt in SNAPSHOT_DTYPES.items():
+        a = getattr(s, name)
+        assert a.dtype == np.dtype(dt), (name, a.dtype)
+        out[name] = hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    return out
+
+
+def restatement_golden() -> dict:
+    return json.load(open(os.path.join(GOLD, "restatement_ref.json")))
+
+
+# oracle restatement vs the compiled reference (tests/test_oracle_vs_ref.py): soil, size, seed, ticks, nwater, nwind
+RESTATEMENT_CASES = [
+    ("default.soil", 96, 11, 12, 200, 0),
+    ("rocksand.soil", 80, 2, 6, 120, 80),
+    ("rockgravelpebbles.soil", 72, 5, 8, 150, 0),
+    ("sand.soil", 64, 9, 6, 50, 120),
+    ("bigbutte.soil", 64, 4, 6, 100, 0),
+]
+
+
+def restatement_case_id(soil, size, seed, ticks, nwater, nwind) -> str:
+    return f"{soil[:-5]}_{size}_s{seed}_t{ticks}_w{nwater}_d{nwind}"

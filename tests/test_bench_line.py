@@ -122,3 +122,24 @@ def test_nan_and_inf_do_not_reach_the_line():
     line = json.dumps(bench.compact_line(d, None), default=float, separators=(",", ":"), allow_nan=False)
     out = json.loads(line)
     assert out["roofline"]["traffic"] is None and out["value_top_level"] is None
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: the same cells in every run; every cell on small maps; float32 / float64 only; 64 MB at most in all."""
+    import numpy as np
+    assert np.array_equal(bench.output_sample(64 * 64), np.arange(64 * 64))
+    big = bench.output_sample(4096 * 4096)
+    assert np.array_equal(big, bench.output_sample(4096 * 4096)) and len(big) == bench.DUMP_CELLS
+    assert (np.diff(big) > 0).all() and big[0] >= 0 and big[-1] < 4096 * 4096
+    n = len(big)
+    arrays = {"cell_index": big.astype(np.float64), "height": np.linspace(0, 1, n), "surface_type": np.ones(n),
+              "water_frequency": np.zeros(n, np.float32), "water_track": np.zeros(n, np.float32), "wind_frequency": np.zeros(n, np.float32)}
+    bench.write_outputs(arrays, str(tmp_path / "out"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == sorted(arrays) and sum(p.stat().st_size for p in (tmp_path / "out").iterdir()) <= bench.DUMP_MAX_BYTES
+    for k, a in arrays.items():
+        assert got[k].dtype == a.dtype and np.array_equal(got[k], a)
+    with pytest.raises(TypeError):
+        bench.write_outputs({"count": np.zeros(4, np.uint32)}, str(tmp_path / "bad"))
+    with pytest.raises(ValueError):
+        bench.write_outputs({"huge": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)}, str(tmp_path / "huge"))

@@ -15,7 +15,8 @@ import pytest
 
 from common import GOLD, ROOT, SOILS, load_cfg
 
-HOST = os.path.join(ROOT, "build", "host", "soilmachine_headless")
+HOSTDIR = os.path.join(ROOT, "oracle", "_ref", "host")         # tools/build_host.sh, run by build() where the reference tree exists
+HOST = os.path.join(HOSTDIR, "soilmachine_headless")
 REF = "/root/reference"
 FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(SOILS, "*.soil")))
 
@@ -24,7 +25,7 @@ FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(SOILS, "*.soi
 def test_unmodified_host_compiles_against_compat_headers():
     subprocess.check_call([os.path.join(ROOT, "tools", "build_host.sh")])
     assert os.path.exists(HOST)
-    src = os.path.join(ROOT, "build", "host", "source")
+    src = os.path.join(HOSTDIR, "source")
     ours = os.path.join(ROOT, "soilmachine_amd", "compat", "source")
     for f in ("layermap.h", "surface.h", "particle"):             # the drop-in: exactly these three
         assert os.path.realpath(os.path.join(src, f)) == os.path.realpath(os.path.join(ours, f))
@@ -66,7 +67,7 @@ def _soil_colors(path, names):
 @pytest.mark.parametrize("soil,ticks", [("default.soil", 20), ("rockgravelpebblessand.soil", 3)])
 def test_unmodified_host_runs_and_matches_reference(tmp_path, soil, ticks):
     if not os.path.exists(HOST):
-        pytest.skip("build/host/soilmachine_headless not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/host/soilmachine_headless not built (needs the reference tree at build time)")
     from oracle_lib import Oracle
     cfg = load_cfg(soil)
     env = dict(os.environ, TICKS=str(ticks))
@@ -93,7 +94,7 @@ def test_unmodified_host_runs_and_matches_reference(tmp_path, soil, ticks):
     assert len(np.unique(top)) > 1 or soil == "default.soil"
 
 
-PROBE = os.path.join(ROOT, "build", "host", "compat_probe")
+PROBE = os.path.join(HOSTDIR, "compat_probe")
 
 
 @pytest.mark.gpu
@@ -105,7 +106,7 @@ def test_compat_queries_and_point_modifiers_through_the_class_api(tmp_path):
     import ctypes as C
     from soilmachine_amd.machine import SoilMachine
     if not os.path.exists(PROBE):
-        pytest.skip("build/host/compat_probe not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/host/compat_probe not built (needs the reference tree at build time)")
     soil = "rocksand.soil"
     cfg = load_cfg(soil)
     out = subprocess.run([PROBE, "-SEED", "4", "-soil", os.path.join(SOILS, soil), "-ticks", "2", "-o", "p.f64"], cwd=tmp_path,

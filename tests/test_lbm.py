@@ -3,9 +3,10 @@
 The reference has no test or golden vector for this path and no GL runs here -- but its shaders are near-C: the unmodified
 statements of lbmwind/shader/LBM/*.cs and shader/move.cs are compiled as C++ (oracle/lbm_ref.cpp through oracle/glsl2cpp.py +
 oracle/shim/glsl_cs.h) into oracle/_ref/liblbm_ref.so. That PINS the CPU restatement (oracle/lbm_oracle.cpp): live against
-the compiled shaders where /root/reference exists, against the committed vectors they produced (tests/golden/lbm_ref.npz)
-everywhere. On top: the published D3Q19 / TRT algebra (moments of the equilibrium, conservation in collisions, rest state,
+the compiled shaders where build() produced them, against the committed vectors they produced (tests/golden/lbm_ref.npz, and the
+per-step trace of the live cases in tests/golden/lbm_ref_live.json) everywhere. On top: the published D3Q19 / TRT algebra (moments of the equilibrium, conservation in collisions, rest state,
 symmetry). GPU (-m gpu): the fused HIP kernel (csrc/soil_lbm.h) against the restatement and the golden vectors, bit for bit."""
+import json
 import os
 
 import numpy as np
@@ -49,20 +50,50 @@ def test_restatement_reproduces_the_reference_shaders_golden_vectors(case):
     assert np.array_equal(bits(o.move(g[f"{case}_p"])), bits(g[f"{case}_moved"]))              # move.cs
 
 
-@pytest.mark.skipif(not os.path.exists(LBM_REF_LIB), reason="oracle/_ref/liblbm_ref.so is built where /root/reference exists")
-@pytest.mark.parametrize("dims,steps", [((64, 40, 64), 6), ((33, 17, 70), 7), ((5, 4, 3), 12)])
-def test_restatement_equals_the_compiled_reference_shaders_live(dims, steps):
-    """the reference's lattice (lbmwind.h:18-21) and two awkward shapes, every step, all three buffers + the tracers"""
-    b = terrain_boundary(*dims)
-    o, r = LbmOracle(*dims), LbmRef(*dims)
-    o.set_boundary(b); r.set_boundary(b); o.initialize(); r.initialize()
-    for k in range(steps + 1):
-        for name, a, w in zip(("rho", "v", "f"), o.read(), r.read()):
-            assert np.array_equal(bits(a), bits(w)), (name, k)
-        o.step(1); r.step(1)
+LIVE_CASES = [((64, 40, 64), 6), ((33, 17, 70), 7), ((5, 4, 3), 12)]
+GOLD_LIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lbm_ref_live.json")
+
+
+def live_tracers(dims):
     rng = np.random.default_rng(2)
-    p = (rng.random((3000, 4)) * np.array([dims[0] - 2, dims[1] - 2, dims[2] - 2, 1]) + np.array([0.5, 0.5, 0.5, 0])).astype(np.float32)
-    assert np.array_equal(bits(o.move(p)), bits(r.move(p)))
+    return (rng.random((3000, 4)) * np.array([dims[0] - 2, dims[1] - 2, dims[2] - 2, 1]) + np.array([0.5, 0.5, 0.5, 0])).astype(np.float32)
+
+
+def lbm_trace(model, dims, steps):
+    """SHA-256 of rho, v and f after every step 0..steps and of the moved tracers: the stored form of the live comparison
+    (tests/golden/lbm_ref_live.json, written by make_golden_lbm_live.py from the compiled shaders)"""
+    import hashlib
+    h = lambda a: hashlib.sha256(bits(a).tobytes()).hexdigest()
+    model.set_boundary(terrain_boundary(*dims)); model.initialize()
+    out = {"steps": []}
+    for k in range(steps + 1):
+        out["steps"].append(dict(zip(("rho", "v", "f"), (h(a) for a in model.read()))))
+        if k < steps:
+            model.step(1)
+    out["moved"] = h(model.move(live_tracers(dims)))
+    return out
+
+
+@pytest.mark.parametrize("dims,steps", LIVE_CASES)
+def test_restatement_equals_the_compiled_reference_shaders_live(dims, steps):
+    """the reference's lattice (lbmwind.h:18-21) and two awkward shapes, every step, all three buffers + the tracers: against the
+    compiled shaders where build() produced oracle/_ref/liblbm_ref.so, against their stored trace everywhere"""
+    if os.path.exists(LBM_REF_LIB):
+        b = terrain_boundary(*dims)
+        o, r = LbmOracle(*dims), LbmRef(*dims)
+        o.set_boundary(b); r.set_boundary(b); o.initialize(); r.initialize()
+        for k in range(steps + 1):
+            for name, a, w in zip(("rho", "v", "f"), o.read(), r.read()):
+                assert np.array_equal(bits(a), bits(w)), (name, k)
+            if k < steps:
+                o.step(1); r.step(1)
+        p = live_tracers(dims)                  # moved on the state after `steps` steps, as in lbm_trace
+        assert np.array_equal(bits(o.move(p)), bits(r.move(p)))
+    want = json.load(open(GOLD_LIVE))["x".join(map(str, dims)) + f"_{steps}"]
+    got = lbm_trace(LbmOracle(*dims), dims, steps)
+    for k, (g, w) in enumerate(zip(got["steps"], want["steps"])):
+        assert g == w, k
+    assert len(got["steps"]) == len(want["steps"]) and got["moved"] == want["moved"]
 
 
 def test_velocity_set_is_d3q19():

@@ -1,48 +1,45 @@
-"""Live differential test oracle restatement <-> the compiled reference (oracle/_ref/soil_ref).
-Skipped where the reference binary is absent (it is built from /root/reference by oracle/Makefile)."""
+"""Oracle restatement <-> the compiled reference (oracle/_ref/soil_ref).
+
+The restatement is held to the reference's states stored under tests/golden (restatement_ref.json, written by
+tests/golden/make_golden_restatement.py from the compiled reference) everywhere, and live against the binary where
+build() produced it. The resume test checks the reference driver itself and needs the binary."""
 import os
 import tempfile
 
 import pytest
 
-from common import load_cfg
+from common import RESTATEMENT_CASES, SOILS, load_cfg, restatement_case_id, restatement_golden, snapshot_hashes
 from oracle_lib import Oracle, have_ref, run_ref
 from soilmachine_amd.snapshot import compare, read_snapshot
 
-pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref/soil_ref not built (needs /root/reference)")
-REFSOIL = "/root/reference/soil"
 
-
-@pytest.mark.parametrize("soil,size,seed,ticks,nwater,nwind", [
-    ("default.soil", 96, 11, 12, 200, 0),
-    ("rocksand.soil", 80, 2, 6, 120, 80),
-    ("rockgravelpebbles.soil", 72, 5, 8, 150, 0),
-    ("sand.soil", 64, 9, 6, 50, 120),
-    ("bigbutte.soil", 64, 4, 6, 100, 0),
-])
+@pytest.mark.parametrize("soil,size,seed,ticks,nwater,nwind", RESTATEMENT_CASES)
 def test_restatement_equals_reference(soil, size, seed, ticks, nwater, nwind):
-    if not os.path.exists(os.path.join(REFSOIL, soil)):
-        pytest.skip("reference soil files absent")
+    want = restatement_golden()[restatement_case_id(soil, size, seed, ticks, nwater, nwind)]
     cfg = load_cfg(soil)
-    with tempfile.TemporaryDirectory() as td:
-        run_ref(os.path.join(REFSOIL, soil), seed=seed, size=size, ticks=ticks, nwater=nwater, nwind=nwind,
-                wind=nwind > 0, dump_prefix=os.path.join(td, "r"), dump_at=[0, ticks])
-        r0 = read_snapshot(os.path.join(td, "r.t0.snap"))
-        r1 = read_snapshot(os.path.join(td, f"r.t{ticks}.snap"))
     o = Oracle(cfg, size, size, seed=seed)
     o.initialize()
-    assert not compare(o.snapshot(), r0)
+    s0 = o.snapshot()
     for _ in range(ticks):
         o.tick(nwater, nwind, True, nwind > 0)
-    assert not compare(o.snapshot(), r1)
+    s1 = o.snapshot()
+    if have_ref():                                  # live: the binary's own states, with compare's itemised differences
+        with tempfile.TemporaryDirectory() as td:
+            run_ref(os.path.join(SOILS, soil), seed=seed, size=size, ticks=ticks, nwater=nwater, nwind=nwind,
+                    wind=nwind > 0, dump_prefix=os.path.join(td, "r"), dump_at=[0, ticks])
+            r0 = read_snapshot(os.path.join(td, "r.t0.snap"))
+            r1 = read_snapshot(os.path.join(td, f"r.t{ticks}.snap"))
+        assert not compare(s0, r0)
+        assert not compare(s1, r1)
+    assert snapshot_hashes(s0) == want["t0"]
+    assert snapshot_hashes(s1) == want["end"]
 
 
+@pytest.mark.skipif(not have_ref(), reason="oracle/_ref/soil_ref not built (build() makes it where the reference sources are present)")
 def test_reference_driver_resumes_from_a_snapshot_bit_exactly():
     """oracle/ref_driver.cpp --load (what bench.py's cpu_baseline uses to time the CPU path on the GPU line's own state): k ticks, snapshot,
     load, n - k ticks == n ticks uninterrupted -- full state, rand() draws, and the JSON figures the P2 envelope reads."""
-    soil = os.path.join(REFSOIL, "rockgravelpebblessand.soil")
-    if not os.path.exists(soil):
-        pytest.skip("reference soil files absent")
+    soil = os.path.join(SOILS, "rockgravelpebblessand.soil")
     kw = dict(seed=3, size=96, nwater=300, nwind=120, lean=True)
     with tempfile.TemporaryDirectory() as td:
         whole = run_ref(soil, ticks=9, dump_prefix=os.path.join(td, "w"), dump_at=[4, 9], **kw)
