@@ -167,6 +167,42 @@ int smx_reset_frequency(smx_ctx* ctx);                  /* :319      WaterPartic
 int smx_tick(smx_ctx* ctx, int32_t nwater, int32_t nwind, int32_t dowater, int32_t dowind);   /* all of the above, in order */
 int smx_sync(smx_ctx* ctx);                             /* wait for all queued device work */
 
+/* ---- ensembles: many independent maps on the exact SERIAL engine, ticked together; replaces a host loop of
+ *      SoilMachine.cpp:283-329 over several worlds (seeds, soil tables, sizes, SCALE) ----
+ * A member is an ordinary full-map context, created by smx_ensemble_add on the ensemble's stream and owned by the ensemble:
+ * every single-context entry point works on it (set_soils, set_scale, srand, initialize, import / export, save / load, digest,
+ * counters, read_*, smx_tick between two ensemble ticks), and work queued through the member and through the ensemble stays in
+ * order. smx_destroy on a member frees nothing (smx_last_error says so); smx_ensemble_remove frees one member, smx_ensemble_destroy
+ * the ensemble and all its members.
+ * smx_ensemble_tick leaves member i in exactly the state smx_tick(member_i, nwater[i], nwind[i], dowater, dowind) would: columns,
+ * frequency planes, the rand() generator and every counter. Each phase is a fixed number of launches for all members, one
+ * wavefront per member on the walkers, so the launch count of a tick does not depend on the member count; the member table is
+ * the only per-tick copy.
+ * Limits: at most SMX_ENSEMBLE_MAX_MEMBERS members, all on the ensemble's device, each with cfg->engine == SMX_ENGINE_SERIAL
+ * (others: -2). A member's section pool is cfg->pool_capacity as given -- the reference's POOLSIZE (10 M sections, 360 MB with
+ * the free list) is far too much for hundreds of members; a member whose pool runs out counts pool_overflow in its own counters
+ * and drops sections exactly as a standalone context does, without touching its neighbours. An add that runs out of device
+ * memory returns < 0 and leaves the ensemble as it was. */
+typedef struct smx_ensemble smx_ensemble;
+enum { SMX_ENSEMBLE_MAX_MEMBERS = 4096 };
+int smx_ensemble_create(int32_t device, smx_ensemble** out);   /* -3 + error text without a device; destroy is safe on the handle */
+void smx_ensemble_destroy(smx_ensemble* e);                    /* frees the ensemble AND its members */
+const char* smx_ensemble_last_error(smx_ensemble* e);
+int smx_ensemble_add(smx_ensemble* e, const smx_config* cfg, smx_ctx** member);   /* Layermap::Layermap per member (as smx_create) */
+/* waits for the ensemble's queued work, takes the member out (the members after it move up one place in the order of addition) and
+ * frees it; -2 if it is not a member of e */
+int smx_ensemble_remove(smx_ensemble* e, smx_ctx* member);
+int smx_ensemble_size(smx_ensemble* e, int32_t* n);
+/* SoilMachine.cpp:283-329 for every member: nwater[i] / nwind[i] per member in order of addition; nwater[i] < 0 = member i sits
+ * this tick out entirely. nwind may be NULL when dowind == 0. */
+int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwind, int32_t dowater, int32_t dowind);
+int smx_ensemble_sync(smx_ensemble* e);                                              /* wait for all queued device work */
+/* phase times and launch counts of the ensemble's ticks (the smx_timing fields of the serial engine: water / grid / wind / freq
+ * phases, and the kernels k_ens_water, k_ens_wind, k_ens_classify, k_ens_frequency in the kernel_water / _wind / _classify /
+ * _mapfreq fields), written as smx_get_timing_sized does */
+int smx_ensemble_get_timing(smx_ensemble* e, smx_timing* out, uint64_t struct_size);
+int smx_ensemble_timing_reset(smx_ensemble* e);
+
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */
 int smx_remove(smx_ctx* ctx, int32_t x, int32_t y, double h, double* remainder);        /* layermap.h:310 */

@@ -80,7 +80,11 @@ SYMBOLS = [
     "smx_d_unpack_columns", "smx_d_pack_particles", "smx_d_unpack_particles", "smx_d_grid_begin", "smx_d_grid_sweep_cols",
     "smx_lbm_create", "smx_lbm_destroy", "smx_lbm_last_error", "smx_lbm_set_boundary", "smx_lbm_boundary_from_map", "smx_lbm_initialize",
     "smx_lbm_step", "smx_lbm_read", "smx_lbm_write_f", "smx_lbm_move", "smx_lbm_get_timing",
+    "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
+    "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
 ]
+
+ENSEMBLE_MAX_MEMBERS = 4096    # SMX_ENSEMBLE_MAX_MEMBERS
 
 _lib = None
 
@@ -183,9 +187,20 @@ def load() -> C.CDLL:
     L.smx_lbm_move.argtypes = [vp, vp, i32]
     L.smx_lbm_get_timing.argtypes = [vp, C.POINTER(dbl), C.POINTER(u64), i32]
     L.smx_stream.argtypes = [vp]; L.smx_stream.restype = vp
+    L.smx_ensemble_create.argtypes = [i32, C.POINTER(vp)]
+    L.smx_ensemble_destroy.argtypes = [vp]; L.smx_ensemble_destroy.restype = None
+    L.smx_ensemble_last_error.argtypes = [vp]; L.smx_ensemble_last_error.restype = C.c_char_p
+    L.smx_ensemble_add.argtypes = [vp, C.POINTER(Config), C.POINTER(vp)]
+    L.smx_ensemble_remove.argtypes = [vp, vp]
+    L.smx_ensemble_size.argtypes = [vp, C.POINTER(i32)]
+    L.smx_ensemble_tick.argtypes = [vp, vp, vp, i32, i32]
+    L.smx_ensemble_sync.argtypes = [vp]
+    L.smx_ensemble_get_timing.argtypes = [vp, C.POINTER(Timing), u64]
+    L.smx_ensemble_timing_reset.argtypes = [vp]
     for name in SYMBOLS:
         f = getattr(L, name)
-        if name not in ("smx_destroy", "smx_last_error", "smx_stream", "smx_lbm_destroy", "smx_lbm_last_error"):
+        if name not in ("smx_destroy", "smx_last_error", "smx_stream", "smx_lbm_destroy", "smx_lbm_last_error",
+                        "smx_ensemble_destroy", "smx_ensemble_last_error"):
             f.restype = C.c_int
     _lib = L
     return L

@@ -8,6 +8,8 @@
 //                                    3x3 neighbourhood or the column holds a non-zero saturation)
 //   k_grid_serial                    exact walk over the (dynamic) active set in the reference's x-major order
 //   k_map_frequency / k_reset_frequency   water.h:353-365, float4-vectorised streaming kernels
+//   k_ens_*                          ensembles (smx_ensemble_*): the walkers above, one wavefront per member of a device
+//                                    table, and the streaming kernels of the serial tick with the member in blockIdx.y
 //   k_init_terrain                   Layermap::initialize (layermap.h:163-216): FBm OpenSimplex2 per cell + column build
 //   k_heights / k_surface / k_normals / k_bilinear   whole-map read-side primitives (layermap.h:341-439)
 //   k_fill_vertices                  Layermap::update(Vertexpool&) (layermap.h:475-555): the 44-byte vertex stream
@@ -55,9 +57,9 @@ static_assert(sizeof(Sec) == 32, "Sec must be 32 bytes");
     reinterpret_cast<uint32_t*>(sh)[i_] = reinterpret_cast<const uint32_t*>(s.soils)[i_];           \
   __syncthreads();
 
-__global__ void __launch_bounds__(64) k_water_serial(DevState s, int n) {
-  SMX_LOAD_SOILS(sh)
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// The walkers of the exact engine, one lane in reference order. k_*_serial run them on a context's own DevState, the ensemble
+// kernels (k_ens_*) on one member's entry of a device table, one wavefront per member: one definition of the step for both.
+SMX_D void serial_water_walk(const DevState& s, const SoilP* sh, int n) {
   SerialPolicy pol(s);
   Sim<SerialPolicy> sim(s, sh, pol);
   Frame st[MAX_FRAMES];
@@ -73,9 +75,7 @@ __global__ void __launch_bounds__(64) k_water_serial(DevState s, int n) {
   pol.finish(s);
 }
 
-__global__ void __launch_bounds__(64) k_wind_serial(DevState s, int n) {
-  SMX_LOAD_SOILS(sh)
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+SMX_D void serial_wind_walk(const DevState& s, const SoilP* sh, int n) {
   SerialPolicy pol(s);
   Sim<SerialPolicy> sim(s, sh, pol);
   for (int i = 0; i < n; i++) {                            // SoilMachine.cpp:304-307
@@ -89,79 +89,7 @@ __global__ void __launch_bounds__(64) k_wind_serial(DevState s, int n) {
   pol.finish(s);
 }
 
-// One thread per cell, 256 consecutive cells (cell order) per block = 4 level-0 bitmap words.
-__global__ void __launch_bounds__(256) k_grid_classify(DevState s) {
-  const size_t n = (size_t)s.x_hi * s.dimy;
-  const size_t c = (size_t)s.x_lo * s.dimy + (size_t)blockIdx.x * 256 + threadIdx.x;   // (x_lo*dimy is a multiple of 64: launch_classify)
-  bool act = false;
-  if (c < n) {
-    const int x = (int)(c / s.dimy), y = (int)(c % s.dimy);
-    uint8_t f = s.flags[c];
-    act = (f & F_SAT) != 0;
-    uint8_t any = f;
-    const bool xm = x > s.x_lo, xp = x < s.x_hi - 1, ym = y > 0, yp = y < s.dimy - 1;
-    if (ym) any |= s.flags[c - 1];
-    if (yp) any |= s.flags[c + 1];
-    if (xm) { any |= s.flags[c - s.dimy]; if (ym) any |= s.flags[c - s.dimy - 1]; if (yp) any |= s.flags[c - s.dimy + 1]; }
-    if (xp) { any |= s.flags[c + s.dimy]; if (ym) any |= s.flags[c + s.dimy - 1]; if (yp) any |= s.flags[c + s.dimy + 1]; }
-    act = act || (any & F_AIR);
-  }
-  const unsigned long long m = __ballot(act);
-  if ((threadIdx.x & 63) == 0 && c < n) {
-    const size_t w0 = c >> 6;
-    s.active[w0] = m;
-    if (m) {
-      atomicOr(&s.active1[w0 >> 6], 1ull << (w0 & 63));
-      atomicOr(&s.active2[w0 >> 12], 1ull << ((w0 >> 6) & 63));
-    }
-  }
-}
-
-// The same, eight cells per thread (dimy a multiple of 8: a thread's cells lie in one map row x): three aligned 8-byte
-// loads of flag bytes (rows x-1, x, x+1) + the two flanking bytes of each row instead of nine byte loads per cell; a
-// wave writes eight complete 64-bit words of the bitmap. 1 B/cell read, 1 bit/cell written: an HBM-streaming kernel.
-__global__ void __launch_bounds__(256) k_grid_classify8(DevState s) {
-  __shared__ unsigned long long sm[32];                      // 256 threads x 8 bits
-  const size_t n = (size_t)s.x_hi * s.dimy, c_lo = (size_t)s.x_lo * s.dimy;   // (c_lo is a multiple of 64: launch_classify)
-  const size_t c = c_lo + ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
-  uint32_t act = 0;
-  if (c < n) {
-    const int x = (int)(c / s.dimy), y = (int)(c % s.dimy);
-    const bool xm = x > s.x_lo, xp = x < s.x_hi - 1, ym = y > 0, yp = y + 8 < s.dimy;
-    const unsigned long long zero = 0ull;
-    const unsigned long long r0 = *reinterpret_cast<const unsigned long long*>(s.flags + c);
-    const unsigned long long rm = xm ? *reinterpret_cast<const unsigned long long*>(s.flags + c - s.dimy) : zero;
-    const unsigned long long rp = xp ? *reinterpret_cast<const unsigned long long*>(s.flags + c + s.dimy) : zero;
-    uint32_t lo = 0, hi = 0;                                 // flag bytes left of cell 0 / right of cell 7, the three rows or-ed
-    if (ym) { lo |= s.flags[c - 1]; if (xm) lo |= s.flags[c - s.dimy - 1]; if (xp) lo |= s.flags[c + s.dimy - 1]; }
-    if (yp) { hi |= s.flags[c + 8]; if (xm) hi |= s.flags[c - s.dimy + 8]; if (xp) hi |= s.flags[c + s.dimy + 8]; }
-    const unsigned long long col = r0 | rm | rp;             // per cell: own column of three rows
-    // F_AIR anywhere in the 3x3: the cell's own column or-ed with its left and right neighbours'
-    const unsigned long long airc = col & 0x0101010101010101ull * F_AIR;
-    const unsigned long long left = (airc << 8) | (unsigned long long)(lo & F_AIR);
-    const unsigned long long right = (airc >> 8) | ((unsigned long long)(hi & F_AIR) << 56);
-    const unsigned long long any = airc | left | right | ((r0 & (0x0101010101010101ull * F_SAT)) >> 1);   // F_SAT = 2 -> bit 0
-#pragma unroll
-    for (int k = 0; k < 8; k++) act |= (uint32_t)((any >> (8 * k)) & 1ull) << k;
-  }
-  reinterpret_cast<uint8_t*>(sm)[threadIdx.x] = (uint8_t)act;
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    const size_t w0 = (c_lo >> 6) + (size_t)blockIdx.x * 32 + threadIdx.x;   // 2048 cells per block = 32 bitmap words
-    if (w0 * 64 < n) {
-      const unsigned long long m = sm[threadIdx.x];
-      s.active[w0] = m;
-      if (m) {
-        atomicOr(&s.active1[w0 >> 6], 1ull << (w0 & 63));
-        atomicOr(&s.active2[w0 >> 12], 1ull << ((w0 >> 6) & 63));
-      }
-    }
-  }
-}
-
-__global__ void __launch_bounds__(64) k_grid_serial(DevState s) {
-  SMX_LOAD_SOILS(sh)
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+SMX_D void serial_grid_walk(const DevState& s, const SoilP* sh) {
   SerialPolicy pol(s);
   Sim<SerialPolicy> sim(s, sh, pol);
   sim.grid_mode = true;
@@ -186,6 +114,173 @@ __global__ void __launch_bounds__(64) k_grid_serial(DevState s) {
   sim.flush_counters();
   pol.add_counter(s, C_GRID_ACTIVE, visited);
   pol.finish(s);
+}
+
+__global__ void __launch_bounds__(64) k_water_serial(DevState s, int n) {
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  serial_water_walk(s, sh, n);
+}
+
+__global__ void __launch_bounds__(64) k_wind_serial(DevState s, int n) {
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  serial_wind_walk(s, sh, n);
+}
+
+// Classification of the grid pass, block `blk` of a context: one thread per cell, 256 consecutive cells (cell order) per block =
+// 4 level-0 bitmap words.
+SMX_D void grid_classify_block(const DevState& s, size_t blk) {
+  const size_t n = (size_t)s.x_hi * s.dimy;
+  const size_t c = (size_t)s.x_lo * s.dimy + blk * 256 + threadIdx.x;   // (x_lo*dimy is a multiple of 64: launch_classify)
+  bool act = false;
+  if (c < n) {
+    const int x = (int)(c / s.dimy), y = (int)(c % s.dimy);
+    uint8_t f = s.flags[c];
+    act = (f & F_SAT) != 0;
+    uint8_t any = f;
+    const bool xm = x > s.x_lo, xp = x < s.x_hi - 1, ym = y > 0, yp = y < s.dimy - 1;
+    if (ym) any |= s.flags[c - 1];
+    if (yp) any |= s.flags[c + 1];
+    if (xm) { any |= s.flags[c - s.dimy]; if (ym) any |= s.flags[c - s.dimy - 1]; if (yp) any |= s.flags[c - s.dimy + 1]; }
+    if (xp) { any |= s.flags[c + s.dimy]; if (ym) any |= s.flags[c + s.dimy - 1]; if (yp) any |= s.flags[c + s.dimy + 1]; }
+    act = act || (any & F_AIR);
+  }
+  const unsigned long long m = __ballot(act);
+  if ((threadIdx.x & 63) == 0 && c < n) {
+    const size_t w0 = c >> 6;
+    s.active[w0] = m;
+    if (m) {
+      atomicOr(&s.active1[w0 >> 6], 1ull << (w0 & 63));
+      atomicOr(&s.active2[w0 >> 12], 1ull << ((w0 >> 6) & 63));
+    }
+  }
+}
+__global__ void __launch_bounds__(256) k_grid_classify(DevState s) { grid_classify_block(s, blockIdx.x); }
+
+// The same, eight cells per thread (dimy a multiple of 8: a thread's cells lie in one map row x): three aligned 8-byte
+// loads of flag bytes (rows x-1, x, x+1) + the two flanking bytes of each row instead of nine byte loads per cell; a
+// wave writes eight complete 64-bit words of the bitmap. 1 B/cell read, 1 bit/cell written: an HBM-streaming kernel.
+// `sm`: 32 words of LDS (256 threads x 8 bits).
+SMX_D void grid_classify8_block(const DevState& s, size_t blk, unsigned long long* sm) {
+  const size_t n = (size_t)s.x_hi * s.dimy, c_lo = (size_t)s.x_lo * s.dimy;   // (c_lo is a multiple of 64: launch_classify)
+  const size_t c = c_lo + (blk * 256 + threadIdx.x) * 8;
+  uint32_t act = 0;
+  if (c < n) {
+    const int x = (int)(c / s.dimy), y = (int)(c % s.dimy);
+    const bool xm = x > s.x_lo, xp = x < s.x_hi - 1, ym = y > 0, yp = y + 8 < s.dimy;
+    const unsigned long long zero = 0ull;
+    const unsigned long long r0 = *reinterpret_cast<const unsigned long long*>(s.flags + c);
+    const unsigned long long rm = xm ? *reinterpret_cast<const unsigned long long*>(s.flags + c - s.dimy) : zero;
+    const unsigned long long rp = xp ? *reinterpret_cast<const unsigned long long*>(s.flags + c + s.dimy) : zero;
+    uint32_t lo = 0, hi = 0;                                 // flag bytes left of cell 0 / right of cell 7, the three rows or-ed
+    if (ym) { lo |= s.flags[c - 1]; if (xm) lo |= s.flags[c - s.dimy - 1]; if (xp) lo |= s.flags[c + s.dimy - 1]; }
+    if (yp) { hi |= s.flags[c + 8]; if (xm) hi |= s.flags[c - s.dimy + 8]; if (xp) hi |= s.flags[c + s.dimy + 8]; }
+    const unsigned long long col = r0 | rm | rp;             // per cell: own column of three rows
+    // F_AIR anywhere in the 3x3: the cell's own column or-ed with its left and right neighbours'
+    const unsigned long long airc = col & 0x0101010101010101ull * F_AIR;
+    const unsigned long long left = (airc << 8) | (unsigned long long)(lo & F_AIR);
+    const unsigned long long right = (airc >> 8) | ((unsigned long long)(hi & F_AIR) << 56);
+    const unsigned long long any = airc | left | right | ((r0 & (0x0101010101010101ull * F_SAT)) >> 1);   // F_SAT = 2 -> bit 0
+#pragma unroll
+    for (int k = 0; k < 8; k++) act |= (uint32_t)((any >> (8 * k)) & 1ull) << k;
+  }
+  reinterpret_cast<uint8_t*>(sm)[threadIdx.x] = (uint8_t)act;
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    const size_t w0 = (c_lo >> 6) + blk * 32 + threadIdx.x;   // 2048 cells per block = 32 bitmap words
+    if (w0 * 64 < n) {
+      const unsigned long long m = sm[threadIdx.x];
+      s.active[w0] = m;
+      if (m) {
+        atomicOr(&s.active1[w0 >> 6], 1ull << (w0 & 63));
+        atomicOr(&s.active2[w0 >> 12], 1ull << ((w0 >> 6) & 63));
+      }
+    }
+  }
+}
+__global__ void __launch_bounds__(256) k_grid_classify8(DevState s) {
+  __shared__ unsigned long long sm[32];
+  grid_classify8_block(s, blockIdx.x, sm);
+}
+
+__global__ void __launch_bounds__(64) k_grid_serial(DevState s) {
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  serial_grid_walk(s, sh);
+}
+
+// ---------------- ensembles of exact contexts (smx_ensemble_*): one launch per phase for every member ----------------
+// The host re-uploads the table every tick (smx_set_soils / smx_set_scale change a member's DevState between ticks). A member that
+// sits a tick out (on == 0) returns at once in every kernel; bounds come from each member's own DevState (members differ in dims).
+struct EnsEntry {
+  DevState s;
+  int32_t nwater, nwind;   // this tick's particle counts
+  int32_t on;              // 0: the member sits this tick out
+  int32_t classify8;       // the eight-cells-per-thread classification applies (launch_classify's rule)
+};
+
+// The table is written only by the copy queued before a tick's launches, so inside a kernel it is constant memory. Read through the
+// constant address space, the compiler may re-load a member's DevState fields (scalar loads) instead of keeping them live in registers
+// across the walk -- as it does with a kernel argument: k_ens_wind through a generic pointer took 256 VGPR + 42 AGPR and one wave per
+// SIMD, through this one it takes the 190 VGPR and two waves of k_wind_serial (profiles/r07_ensemble_kernel_resources.md).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const EnsEntry __attribute__((address_space(4))) EnsTab;
+#else
+typedef const EnsEntry EnsTab;   // (the host pass only parses the kernels)
+#endif
+SMX_D EnsTab* ens_tab(const EnsEntry* p) { return (EnsTab*)p; }
+
+// one wavefront per member (blockIdx.x): the walkers of k_water_serial / k_wind_serial / k_grid_serial on the member's state
+__global__ void __launch_bounds__(64) k_ens_water(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  if (!tab[blockIdx.x].on) return;
+  const DevState s = tab[blockIdx.x].s;
+  const int n = tab[blockIdx.x].nwater;
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0) return;
+  serial_water_walk(s, sh, n);
+}
+__global__ void __launch_bounds__(64) k_ens_wind(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  if (!tab[blockIdx.x].on) return;
+  const DevState s = tab[blockIdx.x].s;
+  const int n = tab[blockIdx.x].nwind;
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0) return;
+  serial_wind_walk(s, sh, n);
+}
+__global__ void __launch_bounds__(64) k_ens_grid(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  if (!tab[blockIdx.x].on) return;
+  const DevState s = tab[blockIdx.x].s;
+  SMX_LOAD_SOILS(sh)
+  if (threadIdx.x != 0) return;
+  serial_grid_walk(s, sh);
+}
+// the grid pass's memsets of the bitmap's summary levels (smx_grid_pass): one workgroup per member, the words create_range allocated
+__global__ void __launch_bounds__(256) k_ens_grid_clear(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  if (!tab[blockIdx.x].on) return;
+  const DevState s = tab[blockIdx.x].s;
+  const size_t n = (size_t)s.dimx * s.dimy, nw0 = (n + 63) >> 6, nw1 = (nw0 + 63) >> 6, nw2 = (nw1 + 63) >> 6;
+  for (size_t i = threadIdx.x; i < nw1 + 64; i += blockDim.x) s.active1[i] = 0ull;
+  for (size_t i = threadIdx.x; i < nw2 + 64; i += blockDim.x) s.active2[i] = 0ull;
+}
+// k_grid_classify / k_grid_classify8, member blockIdx.y, block blockIdx.x of that member's cells
+__global__ void __launch_bounds__(256) k_ens_classify(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  __shared__ unsigned long long sm[32];
+  if (!tab[blockIdx.y].on) return;
+  const DevState s = tab[blockIdx.y].s;
+  const size_t n = (size_t)s.dimx * s.dimy;
+  if (tab[blockIdx.y].classify8) {
+    if ((size_t)blockIdx.x * 2048 >= n) return;
+    grid_classify8_block(s, blockIdx.x, sm);
+  } else {
+    if ((size_t)blockIdx.x * 256 >= n) return;
+    grid_classify_block(s, blockIdx.x);
+  }
 }
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
@@ -1001,21 +1096,50 @@ __global__ void __launch_bounds__(256) k_strip_unpack_particles(BatchShared bs, 
   uint32_t i; memcpy(&i, o, 4);
   if constexpr (WIND) memcpy(&bs.wind[i], o + 4, sizeof(BWind)); else memcpy(&bs.water[i], o + 4, sizeof(BWater));
 }
-__global__ void __launch_bounds__(256) k_map_frequency(float* __restrict__ freq, const float* __restrict__ track, size_t n4, size_t n) {
+SMX_D float map_frequency1(float f, float t) {   // water.h:358-365
   const float lrate = 0.01f, K = 50.0f;      // water.h:359-360
+  return (1.0f - lrate) * f + lrate * K * t / (1.0f + K * t);
+}
+__global__ void __launch_bounds__(256) k_map_frequency(float* __restrict__ freq, const float* __restrict__ track, size_t n4, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t k = i; k < n4; k += stride) {
     float4 f = reinterpret_cast<float4*>(freq)[k];
     const float4 t = reinterpret_cast<const float4*>(track)[k];
-    f.x = (1.0f - lrate) * f.x + lrate * K * t.x / (1.0f + K * t.x);
-    f.y = (1.0f - lrate) * f.y + lrate * K * t.y / (1.0f + K * t.y);
-    f.z = (1.0f - lrate) * f.z + lrate * K * t.z / (1.0f + K * t.z);
-    f.w = (1.0f - lrate) * f.w + lrate * K * t.w / (1.0f + K * t.w);
+    f.x = map_frequency1(f.x, t.x);
+    f.y = map_frequency1(f.y, t.y);
+    f.z = map_frequency1(f.z, t.z);
+    f.w = map_frequency1(f.w, t.w);
     reinterpret_cast<float4*>(freq)[k] = f;
   }
   for (size_t k = n4 * 4 + i; k < n; k += stride)
-    freq[k] = (1.0f - lrate) * freq[k] + lrate * K * track[k] / (1.0f + K * track[k]);
+    freq[k] = map_frequency1(freq[k], track[k]);
+}
+// ensembles: k_map_frequency followed by the reset of the water track (smx_map_frequency + smx_reset_frequency, water.h:353-365) in
+// one pass, member blockIdx.y; a cell's track is read before it is cleared, as in the two steps
+__global__ void __launch_bounds__(256) k_ens_frequency(const EnsEntry* __restrict__ tab_) {
+  EnsTab* tab = ens_tab(tab_);
+  if (!tab[blockIdx.y].on) return;
+  const DevState s = tab[blockIdx.y].s;
+  const size_t n = (size_t)s.dimx * s.dimy, n4 = n / 4;
+  float* __restrict__ freq = s.wfreq;
+  float* __restrict__ track = s.wtrack;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = i; k < n4; k += stride) {
+    float4 f = reinterpret_cast<float4*>(freq)[k];
+    const float4 t = reinterpret_cast<const float4*>(track)[k];
+    f.x = map_frequency1(f.x, t.x);
+    f.y = map_frequency1(f.y, t.y);
+    f.z = map_frequency1(f.z, t.z);
+    f.w = map_frequency1(f.w, t.w);
+    reinterpret_cast<float4*>(freq)[k] = f;
+    reinterpret_cast<float4*>(track)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (size_t k = n4 * 4 + i; k < n; k += stride) {
+    freq[k] = map_frequency1(freq[k], track[k]);
+    track[k] = 0.f;
+  }
 }
 
 // Layermap::initialize (layermap.h:163-216). One thread per cell builds its whole column: the layers are
@@ -1209,11 +1333,19 @@ struct roctx_range {
   ~roctx_range() { if (on) g_roctx.pop(); }
 };
 struct EvPair { hipEvent_t a, b; int phase; uint32_t launches; };
+// the stream a context (or an ensemble) queues its work on, and the HIP-event brackets of its phases (smx_timing)
+struct EventTimer {
+  hipStream_t stream = nullptr;
+  std::vector<EvPair> pending;
+  std::vector<hipEvent_t> evpool;
+  smx_timing timing{};
+};
 
-struct smx_ctx {
+struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
-  hipStream_t stream = nullptr;
+  bool own_stream = true;             // false: the stream is an ensemble's (smx_ensemble_add), which destroys it
+  smx_ensemble* ensemble = nullptr;   // the ensemble that owns this context (smx_destroy refuses it), or null
   std::string err;
   size_t ncells = 0, nw0 = 0, nw1 = 0, nw2 = 0;
   size_t c_lo = 0, c_hi = 0, lcells = 0;   // cells HELD by this context: [c_lo, c_hi) = columns [x_lo, x_hi) (the whole map unless smx_create_strip)
@@ -1225,9 +1357,6 @@ struct smx_ctx {
   float* d_vtx = nullptr; float* d_vcol = nullptr; float* d_vtx1 = nullptr;   // smx_fill_vertices scratch (kept); d_vtx1: one 256-cell block (smx_fill_vertex_cut)
   float vcol_host[256 * 4]; int vcol_n = -1;          // the colour table on the device
   void* d_plane = nullptr; size_t plane_cap = 0;     // smx_read_heights / _surface / smx_normals scratch (kept)
-  std::vector<EvPair> pending;
-  std::vector<hipEvent_t> evpool;
-  smx_timing timing{};
   uint32_t spec_sub = 0, spec_maxnest = 0; bool spec_realloc = false;   // smx_set_spec_limits (0 = defaults)
   int water_generations = SMX_WATER_GENERATIONS;             // smx_set_water_generations (throughput engines: 8)
   int water_stagger = SMX_WATER_STAGGER;                     // smx_set_water_stagger: > 0 = the k generations of a water phase are BORN this many epochs apart inside ONE phase (relaxed engine)
@@ -1278,11 +1407,11 @@ struct smx_ctx {
     }                                                                                                 \
   } while (0)
 
-static hipEvent_t ev_get(smx_ctx* ctx) {
+static hipEvent_t ev_get(EventTimer* ctx) {
   if (!ctx->evpool.empty()) { hipEvent_t e = ctx->evpool.back(); ctx->evpool.pop_back(); return e; }
   hipEvent_t e; hipEventCreate(&e); return e;
 }
-static void drain_events(smx_ctx* ctx) {
+static void drain_events(EventTimer* ctx) {
   for (EvPair& p : ctx->pending) {
     hipEventSynchronize(p.b);
     float ms = 0; hipEventElapsedTime(&ms, p.a, p.b);
@@ -1306,8 +1435,8 @@ static void drain_events(smx_ctx* ctx) {
   ctx->pending.clear();
 }
 struct PhaseTimer {
-  smx_ctx* ctx; EvPair p;
-  PhaseTimer(smx_ctx* c, int phase, uint32_t launches = 1) : ctx(c) { p.a = ev_get(c); p.b = ev_get(c); p.phase = phase; p.launches = launches; hipEventRecord(p.a, c->stream); }
+  EventTimer* ctx; EvPair p;
+  PhaseTimer(EventTimer* c, int phase, uint32_t launches = 1) : ctx(c) { p.a = ev_get(c); p.b = ev_get(c); p.phase = phase; p.launches = launches; hipEventRecord(p.a, c->stream); }
   ~PhaseTimer() { hipEventRecord(p.b, ctx->stream); ctx->pending.push_back(p); if (ctx->pending.size() > 512) drain_events(ctx); }
 };
 
@@ -1327,7 +1456,8 @@ extern "C" {
 
 const char* smx_last_error(smx_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-static int create_range(const smx_config* cfg, int x_lo, int x_hi, smx_ctx** out) {
+// stream: queue the context's work on this stream, which the caller owns (smx_ensemble_add); null = a stream of its own
+static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t stream, smx_ctx** out) {
   if (!cfg || !out || cfg->dimx <= 0 || cfg->dimy <= 0 || cfg->pool_capacity == 0 || cfg->pool_capacity >= 0x7FFFFFFFull) return -2;
   if (x_lo < 0 || x_hi > cfg->dimx || x_lo >= x_hi) return -2;
   smx_ctx* ctx = new smx_ctx();
@@ -1336,7 +1466,8 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, smx_ctx** out
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { ctx->err = "no HIP device visible (the soilmx product path has no CPU fallback)"; return -3; }
   HIPCHK(hipSetDevice(cfg->device));
-  HIPCHK(hipStreamCreate(&ctx->stream));
+  if (stream) { ctx->stream = stream; ctx->own_stream = false; }
+  else HIPCHK(hipStreamCreate(&ctx->stream));
   hipDeviceSetLimit(hipLimitStackSize, 16384);   // recursion depth of cascade<->nested particles is bounded by spill (water.h:34)
   const size_t n = (size_t)cfg->dimx * cfg->dimy;
   ctx->ncells = n;
@@ -1380,12 +1511,12 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, smx_ctx** out
   if (const char* e = getenv("SMX_RELAX_WIND_STEPS")) { const int v = atoi(e); if (v >= 1 && v <= R_MAXSTEPS) ctx->relax_wind_steps = v; }
   return 0;
 }
-int smx_create(const smx_config* cfg, smx_ctx** out) { return create_range(cfg, 0, cfg ? cfg->dimx : 0, out); }
+int smx_create(const smx_config* cfg, smx_ctx** out) { return create_range(cfg, 0, cfg ? cfg->dimx : 0, nullptr, out); }
 // A context that HOLDS only the columns [x_lo, x_hi) of a dimx x dimy map -- a column strip and its halo (smx_strips_*): cells, flags
 // and the engines' per-cell planes are allocated for that range, per-rank memory follows the strip. x_lo*dimy must be a multiple of 64.
 int smx_create_strip(const smx_config* cfg, int32_t x_lo, int32_t x_hi, smx_ctx** out) {
   if (cfg && ((size_t)x_lo * (size_t)cfg->dimy) % 64 != 0) return -2;
-  return create_range(cfg, x_lo, x_hi, out);
+  return create_range(cfg, x_lo, x_hi, nullptr, out);
 }
 #define FULLMAP(what)                                                                                                 \
   if (ctx->partial()) { ctx->err = what ": not available on a strip context (smx_create_strip): it holds only a part of the map"; return -2; }
@@ -1393,6 +1524,7 @@ int smx_create_strip(const smx_config* cfg, int32_t x_lo, int32_t x_hi, smx_ctx*
 static void strips_free(smx_ctx* ctx);
 void smx_destroy(smx_ctx* ctx) {
   if (!ctx) return;
+  if (ctx->ensemble) { ctx->err = "smx_destroy: this context is a member of an ensemble; smx_ensemble_destroy frees it (nothing was freed)"; return; }
   strips_free(ctx);
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   if (getenv("SMX_FLOOD_PROF") && atoi(getenv("SMX_FLOOD_PROF"))) {
@@ -1449,7 +1581,7 @@ void smx_destroy(smx_ctx* ctx) {
     if (ctx->h_draws) hipHostFree(ctx->h_draws);
     if (ctx->h_bctrl) hipHostFree(ctx->h_bctrl);
   }
-  if (ctx->stream) hipStreamDestroy(ctx->stream);
+  if (ctx->stream && ctx->own_stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -2749,6 +2881,202 @@ int smx_tick(smx_ctx* ctx, int32_t nwater, int32_t nwind, int32_t dowater, int32
 int smx_sync(smx_ctx* ctx) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipGetLastError());
+  return 0;
+}
+}  // extern "C"
+
+// ---------------- ensembles: many exact contexts, one launch per phase for all of them ----------------
+// The members are ordinary SERIAL contexts created on the ensemble's stream (create_range), so a call on a member and a call on the
+// ensemble are ordered without events. A tick writes the member table into one slot of a pinned ring, uploads it with one async copy
+// and launches the same kernels whatever the member count: k_ens_water, k_ens_grid_clear, k_ens_classify, k_ens_grid, k_ens_wind,
+// k_ens_frequency. A ring slot is rewritten only after the copy out of it has run (its event), so the host may run ahead of the stream.
+constexpr int ENS_RING = 4;
+struct smx_ensemble : EventTimer {
+  int device = 0;
+  std::string err;
+  std::vector<smx_ctx*> members;          // in order of addition
+  uint32_t cap = 0;                       // members the tables are sized for
+  EnsEntry* d_tab = nullptr;              // the table the kernels read
+  EnsEntry* h_tab = nullptr;              // ENS_RING pinned tables of `cap` entries
+  hipEvent_t h_free[ENS_RING] = {};       // recorded after the upload out of ring slot k
+  bool h_used[ENS_RING] = {};
+  int slot = 0;
+};
+
+#define EHIPCHK(call)                                                                                 \
+  do {                                                                                                \
+    hipError_t e_ = (call);                                                                           \
+    if (e_ != hipSuccess) {                                                                           \
+      e->err = std::string(#call) + ": " + hipGetErrorString(e_);                                     \
+      return -1;                                                                                      \
+    }                                                                                                 \
+  } while (0)
+
+static void ens_free_tables(smx_ensemble* e) {
+  hipFree(e->d_tab); e->d_tab = nullptr;
+  if (e->h_tab) hipHostFree(e->h_tab);
+  e->h_tab = nullptr; e->cap = 0;
+  for (int k = 0; k < ENS_RING; k++) e->h_used[k] = false;
+}
+static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
+  if (n <= e->cap) return 0;
+  uint32_t cap = e->cap ? e->cap : 64u;
+  while (cap < n) cap *= 2u;
+  if (cap > (uint32_t)SMX_ENSEMBLE_MAX_MEMBERS) cap = (uint32_t)SMX_ENSEMBLE_MAX_MEMBERS;
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  EnsEntry* d = nullptr; EnsEntry* h = nullptr;
+  if (hipMalloc(&d, (size_t)cap * sizeof(EnsEntry)) != hipSuccess ||
+      hipHostMalloc(&h, (size_t)ENS_RING * cap * sizeof(EnsEntry), hipHostMallocDefault) != hipSuccess) {
+    hipFree(d);
+    (void)hipGetLastError();
+    e->err = "smx_ensemble_add: out of memory for the member table";
+    return -1;
+  }
+  ens_free_tables(e);
+  e->d_tab = d; e->h_tab = h; e->cap = cap;
+  return 0;
+}
+
+extern "C" {
+int smx_ensemble_create(int32_t device, smx_ensemble** out) {
+  if (!out) return -2;
+  smx_ensemble* e = new smx_ensemble();
+  e->device = device;
+  *out = e;   // handed out even on failure so the caller can read smx_ensemble_last_error(); smx_ensemble_destroy() is safe
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { e->err = "no HIP device visible (the soilmx product path has no CPU fallback)"; return -3; }
+  EHIPCHK(hipSetDevice(device));
+  EHIPCHK(hipStreamCreate(&e->stream));
+  for (int k = 0; k < ENS_RING; k++) EHIPCHK(hipEventCreateWithFlags(&e->h_free[k], hipEventDisableTiming));
+  return 0;
+}
+void smx_ensemble_destroy(smx_ensemble* e) {
+  if (!e) return;
+  if (e->stream) hipStreamSynchronize(e->stream);
+  for (smx_ctx* m : e->members) { m->ensemble = nullptr; smx_destroy(m); }
+  e->members.clear();
+  drain_events(e);
+  for (hipEvent_t ev : e->evpool) hipEventDestroy(ev);
+  for (int k = 0; k < ENS_RING; k++) if (e->h_free[k]) hipEventDestroy(e->h_free[k]);
+  ens_free_tables(e);
+  if (e->stream) hipStreamDestroy(e->stream);
+  delete e;
+}
+const char* smx_ensemble_last_error(smx_ensemble* e) { return e ? e->err.c_str() : "null ensemble"; }
+
+int smx_ensemble_add(smx_ensemble* e, const smx_config* cfg, smx_ctx** member) {
+  if (!e) return -2;
+  if (!cfg || !member) { e->err = "smx_ensemble_add: null argument"; return -2; }
+  *member = nullptr;
+  if (!e->stream) { e->err = "smx_ensemble_add: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (cfg->engine != SMX_ENGINE_SERIAL) { e->err = "smx_ensemble_add: members run the exact SERIAL engine only (speculative, batched and relaxed contexts are refused)"; return -2; }
+  if (cfg->device != e->device) { e->err = "smx_ensemble_add: a member lives on the ensemble's device"; return -2; }
+  if (e->members.size() >= (size_t)SMX_ENSEMBLE_MAX_MEMBERS) { e->err = "smx_ensemble_add: SMX_ENSEMBLE_MAX_MEMBERS reached"; return -2; }
+  if (int rc = ens_reserve(e, (uint32_t)e->members.size() + 1u)) return rc;
+  smx_ctx* ctx = nullptr;
+  const int rc = create_range(cfg, 0, cfg->dimx, e->stream, &ctx);
+  if (rc != 0) {
+    e->err = std::string("smx_ensemble_add: ") + (ctx ? ctx->err : std::string("invalid configuration (dims, pool_capacity)"));
+    if (ctx) smx_destroy(ctx);              // (not yet a member: frees what was allocated, leaves the ensemble's stream alone)
+    (void)hipGetLastError();                // an out-of-memory failure must not surface in the next tick's launch check
+    return rc;
+  }
+  ctx->ensemble = e;
+  e->members.push_back(ctx);
+  *member = ctx;
+  return 0;
+}
+int smx_ensemble_remove(smx_ensemble* e, smx_ctx* member) {
+  if (!e) return -2;
+  auto it = std::find(e->members.begin(), e->members.end(), member);
+  if (!member || it == e->members.end()) { e->err = "smx_ensemble_remove: not a member of this ensemble"; return -2; }
+  EHIPCHK(hipStreamSynchronize(e->stream));   // (no queued tick still reads the member's state)
+  e->members.erase(it);
+  member->ensemble = nullptr;
+  smx_destroy(member);
+  return 0;
+}
+int smx_ensemble_size(smx_ensemble* e, int32_t* n) {
+  if (!e || !n) return -2;
+  *n = (int32_t)e->members.size();
+  return 0;
+}
+
+int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwind, int32_t dowater, int32_t dowind) {   // SoilMachine.cpp:283-329 per member
+  if (!e) return -2;
+  if (!nwater) { e->err = "smx_ensemble_tick: nwater is null (one count per member; < 0 = the member sits the tick out)"; return -2; }
+  if (dowind && !nwind) { e->err = "smx_ensemble_tick: nwind is null while dowind is set"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  for (uint32_t i = 0; i < nm; i++)
+    if (e->members[i]->cfg.engine != SMX_ENGINE_SERIAL) { e->err = "smx_ensemble_tick: member " + std::to_string(i) + " was switched off the SERIAL engine (smx_set_engine)"; return -2; }
+  roctx_range rr("soilmx:ensemble");
+  const int k = e->slot;
+  e->slot = (e->slot + 1) % ENS_RING;
+  if (e->h_used[k]) EHIPCHK(hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
+  EnsEntry* h = e->h_tab + (size_t)k * e->cap;
+  size_t cls_blocks = 1, freq_blocks = 1;
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = e->members[i];
+    EnsEntry& t = h[i];
+    t.s = c->d;
+    t.nwater = nwater[i];
+    t.nwind = dowind ? nwind[i] : 0;
+    t.on = nwater[i] >= 0;
+    t.classify8 = c->cfg.dimy % 8 == 0 && c->lcells % 64 == 0;   // (launch_classify; a member holds the whole map: c_lo = 0)
+    if (!t.on) continue;
+    cls_blocks = std::max(cls_blocks, t.classify8 ? (c->lcells / 8 + 255) / 256 : (c->lcells + 255) / 256);
+    freq_blocks = std::max(freq_blocks, std::min<size_t>(2048, (c->ncells / 4 + 255) / 256));
+  }
+  EHIPCHK(hipMemcpyAsync(e->d_tab, h, (size_t)nm * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
+  EHIPCHK(hipEventRecord(e->h_free[k], e->stream));
+  e->h_used[k] = true;
+  hipStream_t st = e->stream;
+  const EnsEntry* tab = e->d_tab;
+  if (dowater) {
+    {
+      PhaseTimer t(e, 0);
+      PhaseTimer tk(e, 4);
+      hipLaunchKernelGGL(k_ens_water, dim3(nm), dim3(64), 0, st, tab);
+    }
+    {
+      PhaseTimer t(e, 1);
+      hipLaunchKernelGGL(k_ens_grid_clear, dim3(nm), dim3(256), 0, st, tab);
+      { PhaseTimer tk(e, 6); hipLaunchKernelGGL(k_ens_classify, dim3((unsigned)cls_blocks, nm), dim3(256), 0, st, tab); }
+      hipLaunchKernelGGL(k_ens_grid, dim3(nm), dim3(64), 0, st, tab);
+    }
+  }
+  if (dowind) {
+    PhaseTimer t(e, 2);
+    PhaseTimer tk(e, 5);
+    hipLaunchKernelGGL(k_ens_wind, dim3(nm), dim3(64), 0, st, tab);
+  }
+  if (dowater) {
+    PhaseTimer t(e, 3);
+    PhaseTimer tk(e, 8);
+    hipLaunchKernelGGL(k_ens_frequency, dim3((unsigned)freq_blocks, nm), dim3(256), 0, st, tab);
+  }
+  EHIPCHK(hipGetLastError());
+  return 0;
+}
+int smx_ensemble_sync(smx_ensemble* e) {
+  if (!e || !e->stream) return -2;
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  EHIPCHK(hipGetLastError());
+  return 0;
+}
+int smx_ensemble_get_timing(smx_ensemble* e, smx_timing* out, uint64_t struct_size) {
+  if (!e || !out || !e->stream) return -2;
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  drain_events(e);
+  memcpy(out, &e->timing, struct_size < sizeof(e->timing) ? (size_t)struct_size : sizeof(e->timing));
+  return 0;
+}
+int smx_ensemble_timing_reset(smx_ensemble* e) {
+  if (!e || !e->stream) return -2;
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  drain_events(e);
+  memset(&e->timing, 0, sizeof(e->timing));
   return 0;
 }
 

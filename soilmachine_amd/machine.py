@@ -42,16 +42,9 @@ class Layermap:
         self.seed = seed
         self.pool = int(pool if pool is not None else default_pool(self.dimx, self.dimy))
         c = capi.Config(self.dimx, self.dimy, cfg.SCALE, device, self.pool, engine, 0)
-        h = C.c_void_p()
         self.x_range = x_range                                    # (lo, hi): a STRIP context holding only these columns (smx_create_strip)
-        rc = self.L.smx_create(C.byref(c), C.byref(h)) if x_range is None else self.L.smx_create_strip(C.byref(c), int(x_range[0]), int(x_range[1]), C.byref(h))
-        self.h = h
-        if rc != 0:
-            msg = self.L.smx_last_error(h).decode() if h else "smx_create failed"
-            if h:
-                self.L.smx_destroy(h)
-            self.h = None
-            raise SoilmxError(f"smx_create: {msg} (rc={rc})")
+        self.h = None
+        self.h = self._open(c)
         self._soils = soils_array(cfg)
         self._chk(self.L.smx_set_soils(self.h, capi.ptr(self._soils), len(self._soils)))
         self._chk(self.L.smx_srand(self.h, seed))                 # srand(SEED) SoilMachine.cpp:41
@@ -59,6 +52,18 @@ class Layermap:
             self.initialize(seed)
 
     # -- plumbing --
+    def _open(self, c: capi.Config):
+        """Create the device context (smx_create / smx_create_strip); raises SoilmxError with the library's text."""
+        h = C.c_void_p()
+        x_range = self.x_range
+        rc = self.L.smx_create(C.byref(c), C.byref(h)) if x_range is None else self.L.smx_create_strip(C.byref(c), int(x_range[0]), int(x_range[1]), C.byref(h))
+        if rc != 0:
+            msg = self.L.smx_last_error(h).decode() if h else "smx_create failed"
+            if h:
+                self.L.smx_destroy(h)
+            raise SoilmxError(f"smx_create: {msg} (rc={rc})")
+        return h
+
     def _chk(self, rc: int):
         if rc != 0:
             raise SoilmxError(self.L.smx_last_error(self.h).decode() + f" (rc={rc})")
