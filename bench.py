@@ -3,7 +3,11 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0 -- the LAST line of stdout, compact
 (~4 KB: compact_line below); the detailed record (per-tick entries, extra lines, parity blocks, LBM) goes to a side file
-(gpurun_out/bench_detail_n<N>.json, named on the line).
+(bench_detail_n<N>.json, its path named on the line).
+  * such a plain run does only what the headline needs: set-up, W warm-up ticks, K timed ticks, --dump-outputs, the line. Its roofline comes
+    from the timed ticks' own HIP events; its parity_gate and bit_exact_on_this_workload quote committed records. Everything else below --
+    cpu_baseline, the extra lines (other sizes, soils, engines and schedules, the wet regime, the 8192^2 strips line at N > 1), parity_vs_exact,
+    parity_vs_reference, the LBM line -- runs with --full only (parse_args).
   * a "step" of the bench = one tick of SoilMachine.cpp:283-329 (water particles -> grid pass -> wind particles ->
     frequency update) over the synthetic 4096^2 layermap of BASELINE.json configs[3]
     (soil/rockgravelpebblessand.soil: 4 soils, 2 noise layers, SCALE 120, SEED 0); terrain comes from
@@ -508,7 +512,7 @@ def compact_line(d: dict, detail_path) -> dict:
     return _r(out)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -519,9 +523,10 @@ def main():
     ap.add_argument("--nwind", type=int, default=None)
     ap.add_argument("--engine", type=str, default="relaxed", choices=["auto", "serial", "spec", "batched", "relaxed"])
     ap.add_argument("--only", type=str, default=None, help="measure just this extra line (by name) and print it")
-    ap.add_argument("--full", action="store_true", help="all extra lines (16384^2, both throughput schedules on every map)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lines", action="store_true", help="only the headline measurement")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baseline, the extra lines, the parity blocks and the LBM line")
+    ap.add_argument("--all-lines", action="store_true", help="--full with the extra lines it leaves out (16384^2, both throughput schedules on every map)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-lines", action="store_true", help="--full without the extra lines, the parity blocks and the LBM line")
     ap.add_argument("--cpu-ticks", type=int, default=1)
     ap.add_argument("--strong", action="store_true", help="N > 1: keep the map at --size^2 and split it (default: the map grows with N)")
     ap.add_argument("--water-generations", type=int, default=None, help="throughput engines: the tick's water particles as k consecutive generations (smx_set_water_generations; "
@@ -531,7 +536,18 @@ def main():
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the headline's last step left in the map as DIR/<name>.npy (write_outputs); "
                          "single-process runs only (refused on the strips path, N > 1)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    args.full = args.full or args.all_lines
+    if not args.full:
+        # a plain run times the headline and nothing else: it is run several times per change, and the rest takes minutes
+        # (--only NAME still measures its one line)
+        args.no_cpu_baseline = True
+        args.no_lines = args.no_lines or args.only is None
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     from soilmachine_amd import distrib
@@ -690,13 +706,13 @@ def main():
             dcfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", "default.soil"))
             bcfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", "rockgravelpebbles_big.soil"))
             fc = f"{n}x{n}, soil/{soil}, the file's own NWATER={cfg.NWATER} / NWIND={cfg.NWIND}"
-            extra = []   # name, cfg, soil, size, nwater, nwind, engine, pool, steps, warmup, workload, in the default run?
+            extra = []   # name, cfg, soil, size, nwater, nwind, engine, pool, steps, warmup, workload, in a --full run (else --all-lines only)?
             if throughput:
                 # the bit-exact engine on the HEADLINE's workload (same map, same counts): what parity-green throughput is today
-                # (37 s per tick at 4096^2 / 64 000 + 16 000: measured once, profiles/r04_exact_area_scaled_4096.json; --full or --only re-measures it)
+                # (37 s per tick at 4096^2 / 64 000 + 16 000: measured once, profiles/r04_exact_area_scaled_4096.json; --all-lines or --only re-measures it)
                 extra.append(("exact_area_scaled", cfg, soil, n, nwater, nwind, "spec", pool, 1, 1, workload, False))
                 other = "batched" if eng_name == "relaxed" else "relaxed"
-                extra.append((f"{other}_area_scaled", cfg, soil, n, nwater, nwind, other, pool, k3, w3, workload, False))   # (--full: the exclusive schedule is an internal of the relaxed one -- wind, floods --, not a shipped configuration: DESIGN.md 4.2)
+                extra.append((f"{other}_area_scaled", cfg, soil, n, nwater, nwind, other, pool, k3, w3, workload, False))   # (--all-lines: the exclusive schedule is an internal of the relaxed one -- wind, floods --, not a shipped configuration: DESIGN.md 4.2)
                 extra.append(("exact_file_counts", cfg, soil, n, cfg.NWATER, cfg.NWIND, "spec", pool, k3, w3, fc + " (round-1 headline workload)", True))
                 extra.append((f"{eng_name}_file_counts", cfg, soil, n, cfg.NWATER, cfg.NWIND, eng_name, pool, k3, w3, fc, True))
             for nm, wind in (("configs1_1024_default_hydraulic", 0), ("configs2_1024_default_coupled", 250)):
@@ -714,7 +730,7 @@ def main():
             for (nm, c_, s_, n_, nw_, nd_, e_, pool_, k_, w_, wl_, dflt) in extra:
                 if args.only is not None and nm != args.only:
                     continue
-                if args.only is None and not (dflt or args.full):
+                if args.only is None and not (dflt or args.all_lines):
                     continue
                 rr = measure(c_, s_, n_, 0, nw_, nd_, nd_ > 0, ENG[e_], pool_, local_rank, k_, w_)
                 ln = line_of(rr, nm, wl_, "exact (speculative)" if e_ == "spec" else e_, k_)

@@ -115,6 +115,21 @@ def test_roofline_is_bytes_per_launch_over_the_average_bracketed_launch():
     assert bench.kernel_roofline(1.0, 0.0, 0, 0) is None
 
 
+def test_a_plain_run_times_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` takes the path of --no-lines --no-cpu-baseline; --full runs the CPU baseline, the extra lines,
+    the parity blocks and LBM as before, --all-lines adds the lines --full leaves out, --only NAME measures its line without --full."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (plain.full, plain.all_lines, plain.no_lines, plain.no_cpu_baseline) == (False, False, True, True)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert (full.full, full.all_lines, full.no_lines, full.no_cpu_baseline) == (True, False, False, False)
+    every = bench.parse_args(["--all-lines"])
+    assert (every.full, every.all_lines, every.no_lines, every.no_cpu_baseline) == (True, True, False, False)
+    part = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert (part.no_lines, part.no_cpu_baseline) == (False, True)
+    one = bench.parse_args(["--only", "exact_area_scaled"])
+    assert (one.full, one.no_lines, one.no_cpu_baseline) == (False, False, True)
+
+
 def test_nan_and_inf_do_not_reach_the_line():
     d = _detail()
     d["roofline"]["traffic"] = float("nan")

@@ -66,9 +66,9 @@ for s in "$@"; do
     wetexact)  run wetexact 60 500 python tools/wet_regime.py --engine spec --warm 100 --ticks 20 --cpu 0 ;;
     wetprof)   run wetprof 30 300 env SMX_FLOOD_PROF=1 python tools/wet_regime.py --engine relaxed --warm 100 --ticks 20 --cpu 0; grep -A 40 "soilmx" $out/wetprof.err | cut -c1-400 ;;
     headprof)  run headprof 60 400 env SMX_FLOOD_PROF=1 python bench.py --gpus 1 --steps ${HSTEPS:-5} --warmup 5 --no-lines --no-cpu-baseline ${BENCH_EXTRA:-}; grep -A 40 "soilmx" $out/headprof.err | cut -c1-400 ;;
-    bench)     run bench 60 400 python bench.py; cp $out/bench.log $out/bench.json 2>/dev/null ;;
-    benchdrv)  run benchdrv 120 900 python bench.py --gpus 1 --steps 20 --warmup 5; cp $out/benchdrv.log $out/benchdrv.json 2>/dev/null; cp $root/gpurun_out/bench_detail_n1.json $out/benchdrv_detail.json 2>/dev/null ;;
-    benchfull) run benchfull 120 900 python bench.py --full; cp $out/benchfull.log $out/benchfull.json 2>/dev/null ;;
+    bench)     run bench 60 400 python bench.py --full; cp $out/bench.log $out/bench.json 2>/dev/null ;;
+    benchdrv)  run benchdrv 120 900 env SMX_BENCH_DETAIL_DIR=$out python bench.py --gpus 1 --steps 20 --warmup 5 --full; cp $out/benchdrv.log $out/benchdrv.json 2>/dev/null; mv $out/bench_detail_n1.json $out/benchdrv_detail.json 2>/dev/null ;;
+    benchfull) run benchfull 120 900 python bench.py --all-lines; cp $out/benchfull.log $out/benchfull.json 2>/dev/null ;;
     trace)     run trace 60 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-lines
                python tools/kernel_stats.py $out/trace | tee $out/trace.kernels; python tools/trace_gaps.py $out/trace --last-ticks 5 | tee $out/trace.summary; rm -rf $out/trace ;;
     pmc)       PB="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-lines"
