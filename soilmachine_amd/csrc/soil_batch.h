@@ -604,11 +604,6 @@ SMX_D void batch_wind_epoch(Sim<P>& sim, const BatchShared& bs, uint32_t slot, u
 // `fine_above`: water reserves single cells while more particles than this are running (default: never; the tests lower it).
 struct BSched { int tshift, dilate, maxsteps; };
 
-#ifdef SMX_HOSTSIM
-#define SMX_HD inline
-#else
-#define SMX_HD __host__ __device__ inline
-#endif
 SMX_HD BSched batch_schedule(bool wind, uint32_t nlive, int base_dilate, uint32_t fine_above = 0xFFFFFFFFu) {
   BSched k;
   if (wind) {
@@ -625,6 +620,13 @@ SMX_HD BSched batch_schedule(bool wind, uint32_t nlive, int base_dilate, uint32_
   if (base_dilate > k.dilate) k.dilate = base_dilate;
   return k;
 }
+// A tick's water particles run as k consecutive top-level generations (SMX_WATER_GENERATIONS): generation q's share of the `left`
+// that have not started yet -- n/k each, the remainder goes to the later ones. Takes the share off `left`.
+SMX_HD uint32_t batch_generation_share(uint32_t& left, uint32_t k, uint32_t q) {
+  const uint32_t nq = left / (k - q);
+  left -= nq;
+  return nq;
+}
 // n equal strips, boundaries on multiples of 16 cells (the widest claim tile is 8 cells, the grid tiles are 4)
 SMX_HD BStrips batch_make_strips(int dimx, int n, int a, int b) {
   BStrips st; st.n = n < 1 ? 1 : (n > 8 ? 8 : n); st.a = a; st.b = b;
@@ -636,6 +638,34 @@ SMX_HD void batch_apply_schedule(BatchShared& bs, const DevState& s, const BSche
   bs.tshift = k.tshift; bs.dilate = k.dilate; bs.maxsteps = k.maxsteps;
   bs.ntx = (s.dimx + (1 << k.tshift) - 1) >> k.tshift; bs.nty = (s.dimy + (1 << k.tshift) - 1) >> k.tshift;
   bs.txb = s.x_lo >> k.tshift; bs.txe = ((s.x_hi - 1) >> k.tshift) + 1;
+}
+// What every chunk of a generation starts with, for the library's driver (soilmx.hip run_chunk) and the host build of tests/hostsim
+// alike: is this chunk relaxed (water always; wind while more than `relax_wind_min` particles run -- its tail of a few thousand
+// particles that fly on for up to ~13 000 steps is better served by the exclusive schedule's 32 steps per launch; one switch per
+// generation), do the claim planes start afresh, which kind of chunk is it under column strips. Applies `sc` (chosen by the caller:
+// batch_schedule, or an experiment's override) and the relaxed steps per epoch to `bs`, moves `epoch` / `chunk` on, and returns what the
+// caller acts on. `nlive_sched`: running particles on all strips together. `chunk_epochs` is the default length: without strips the
+// result does not depend on where a generation is cut into chunks, and the library cuts by launch shape; with strips the chunk is the
+// unit of the exchange. `bs` is written before the caller launches anything: kernels take it by value.
+struct BChunkPlan { bool regrain, relaxed_now; int chunk_epochs; };
+SMX_HD BChunkPlan batch_plan_chunk(BatchShared& bs, const DevState& s, const BSched& sc, bool wind, uint32_t nlive_sched, bool relax_gen, uint32_t relax_wind_min,
+                                   int relax_wind_steps, int relax_water_steps, bool first, uint32_t& epoch, uint32_t& chunk) {
+  BChunkPlan p;
+  const bool strips = bs.strips.n > 1;
+  p.relaxed_now = relax_gen && (!wind || nlive_sched > relax_wind_min);
+  p.regrain = sc.tshift != bs.tshift;                      // first chunk, or the claim granularity changes
+  if (relax_gen && !p.relaxed_now && bs.relaxed) { bs.relaxed = 0; p.regrain = true; }   // hand the survivors to the exclusive schedule: fresh reservations
+  batch_apply_schedule(bs, s, sc);
+  bs.sphase = strips ? (int)(chunk & 1u) : STRIP_INTERIOR;   // column strips: INTERIOR and SEAM chunks alternate
+  if (strips && chunk > 0) epoch++;                        // (reservations of the previous chunk must not look current)
+  chunk++;
+  p.chunk_epochs = B_CHUNK;
+  if (p.relaxed_now) {
+    if (!strips && !first) p.chunk_epochs = 8;             // (nested generations live a few steps)
+    bs.rstride = wind ? 2 * relax_wind_steps : (relax_water_steps > 2 ? relax_water_steps : 2);
+    bs.rsteps = wind ? relax_wind_steps : relax_water_steps;
+  }
+  return p;
 }
 
 // ---------------- grid pass: one colour, one tile ----------------

@@ -29,6 +29,11 @@
 #ifndef SMX_D
 #define SMX_D __device__ __forceinline__
 #endif
+#ifdef SMX_HOSTSIM                                         // SMX_HD: what the library's host driver and the kernels share (host builds: all of it)
+#define SMX_HD inline
+#else
+#define SMX_HD __host__ __device__ inline
+#endif
 // Fire-and-forget read-modify-writes (no return value -> the lane never waits for the memory round trip) and the
 // coherent load that goes with them. The exact engines are chains of DEPENDENT accesses on one lane: a plain
 // `word |= bit` costs a full round trip each (load, wait, or, store); the grid pass did 27 of them per water transfer.

@@ -70,6 +70,13 @@ SMX_D void relax_flood_later(const BatchShared& bs, uint32_t slot, uint32_t pari
   const uint32_t k = relax_append(&bs.ctrl[BC_NFLOOD + parity], want);
   if (want) { if (k < bs.list_cap) bs.flist[parity][k] = slot; else SMX_A_ADD(&bs.ctrl[BC_LIST_LOST], 1u); }
 }
+// The lists of epoch parity `par` start empty: flood, flag and run counts and the nine cascade colours. Called by ONE thread while the
+// epoch before runs (the lists' last readers finished an epoch ago); the caller guards and orders it. (k_relax_tail and k_relax_epochs,
+// soilmx.hip, hold the same stores spelled out: keep them equal to this.)
+SMX_D void relax_reset_lists(const BatchShared& bs, uint32_t par) {
+  bs.ctrl[BC_NFLOOD + par] = 0u; bs.ctrl[BC_NFLAG + par] = 0u; bs.ctrl[BC_NRUN + par] = 0u;
+  for (uint32_t q = 0; q < 9u; q++) bs.ctrl[BC_NCASC + 9u * par + q] = 0u;
+}
 // Floods are long, branchy paths (~150 us each on a lane); while nearly everybody is still running, the few particles that ended
 // early wait for every fourth epoch. Once the ended ones are 1/64 of the runners (or nobody runs), every epoch floods.
 // A function of the epoch's own counts: not of chunking, not of how the host drives the epochs.

@@ -296,8 +296,7 @@ static int st_pack_band(smx_ctx* ctx, StripState& S, int cx0, int cx1, int px0, 
   const bool parts = particles && ctx->d_nslots;
   if (parts) {
     const uint32_t nslots = ctx->d_nslots;
-    if (ctx->d_wind) hipLaunchKernelGGL(k_strip_pack_particles<true>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, ctx->bs, nslots, px0, px1, ctx->d_xpart, ctx->xpart_cap, ctx->d_xcur + 1);
-    else hipLaunchKernelGGL(k_strip_pack_particles<false>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, ctx->bs, nslots, px0, px1, ctx->d_xpart, ctx->xpart_cap, ctx->d_xcur + 1);
+    LAUNCH_WIND_WATER(ctx->d_wind, k_strip_pack_particles, dim3((nslots + 255u) / 256u), dim3(256), st, ctx->bs, nslots, px0, px1, ctx->d_xpart, ctx->xpart_cap, ctx->d_xcur + 1);
   }
   HIPCHK(hipMemcpyAsync(c, ctx->d_xcur, 2 * sizeof(XCursor), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st)); S.T->host_syncs++;
@@ -317,8 +316,7 @@ static int st_unpack_band(smx_ctx* ctx, const XBundle& b) {
   }
   if (b.npart) {
     if (b.rs != 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater))) { ctx->err = "strips: particle records of the wrong phase"; return -2; }
-    if (ctx->d_wind) hipLaunchKernelGGL(k_strip_unpack_particles<true>, dim3((b.npart + 255u) / 256u), dim3(256), 0, st, ctx->bs, ctx->d_rpart, b.npart);
-    else hipLaunchKernelGGL(k_strip_unpack_particles<false>, dim3((b.npart + 255u) / 256u), dim3(256), 0, st, ctx->bs, ctx->d_rpart, b.npart);
+    LAUNCH_WIND_WATER(ctx->d_wind, k_strip_unpack_particles, dim3((b.npart + 255u) / 256u), dim3(256), st, ctx->bs, ctx->d_rpart, b.npart);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -465,8 +463,7 @@ int smx_strips_tick(smx_ctx* ctx, int32_t nwater, int32_t nwind, int32_t dowater
       left = 0u;
     }
     for (uint32_t q = 0; q < k && left > 0; q++) {
-      const uint32_t nq = left / (k - q);
-      left -= nq;
+      const uint32_t nq = batch_generation_share(left, k, q);
       if (nq && st_phase(ctx, S, false, nq, {}, false)) return -1;
     }
     roctx_range rg("soilmx:strips:grid");

@@ -47,6 +47,17 @@ using namespace smx;
 static_assert(sizeof(SoilP) == sizeof(smx_soil), "smx_soil layout");
 static_assert(sizeof(Sec) == 32, "Sec must be 32 bytes");
 
+// Environment knobs (experiments; README.md lists them): the variable's value, or `dflt` where it is not set. A call site keeps what it
+// makes of the value in a function-local static: read once per process.
+static const char* env_str(const char* name) { return getenv(name); }
+static long long env_int(const char* name, long long dflt) { const char* e = env_str(name); return e ? atoll(e) : dflt; }
+static bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
+// ... and the knobs that more than one site reads
+static uint32_t flood_prof() { static const uint32_t v = (uint32_t)env_int("SMX_FLOOD_PROF", 0); return v; }   // (not 0: k_relax_floods and k_grid_tiles_flow keep duration histograms, printed by smx_destroy)
+static uint32_t relax_mega_flags() { static const uint32_t v = (uint32_t)env_int("SMX_RELAX_MEGA_FLAGS", 0); return v; }   // (1: every thread fences at a barrier; 2: k_relax_epochs keeps workgroup 0's clock)
+static bool trace_batch() { static const bool on = env_flag("SMX_TRACE_BATCH", false); return on; }
+static bool coop_on() { static const bool on = env_flag("SMX_COOP", true); return on; }                         // (the wave-loop kernels of soil_coop.h)
+
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
@@ -56,65 +67,6 @@ static_assert(sizeof(Sec) == 32, "Sec must be 32 bytes");
   for (uint32_t i_ = threadIdx.x; i_ < s.nsoils * (sizeof(SoilP) / 4); i_ += blockDim.x)            \
     reinterpret_cast<uint32_t*>(sh)[i_] = reinterpret_cast<const uint32_t*>(s.soils)[i_];           \
   __syncthreads();
-
-// The walkers of the exact engine, one lane in reference order. k_*_serial run them on a context's own DevState, the ensemble
-// kernels (k_ens_*) on one member's entry of a device table, one wavefront per member: one definition of the step for both.
-SMX_D void serial_water_walk(const DevState& s, const SoilP* sh, int n) {
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, sh, pol);
-  Frame st[MAX_FRAMES];
-  int depth = 0;
-  for (int i = 0; i < n; i++) {                            // SoilMachine.cpp:288-298
-    int ry, rx;
-    pol.rand2(s, ry, rx);                                  // water.h:13, g++ order: 1st draw -> y, 2nd -> x
-    Water p;
-    sim.water_init(p, rx % s.dimx, ry % s.dimy);
-    sim.water_drive(p, true, true, st, depth);
-  }
-  sim.flush_counters();
-  pol.finish(s);
-}
-
-SMX_D void serial_wind_walk(const DevState& s, const SoilP* sh, int n) {
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, sh, pol);
-  for (int i = 0; i < n; i++) {                            // SoilMachine.cpp:304-307
-    int ry, rx;
-    pol.rand2(s, ry, rx);                                  // wind.h:15
-    Wind p;
-    sim.wind_init(p, rx % s.dimx, ry % s.dimy);
-    sim.wind_run(p);
-  }
-  sim.flush_counters();
-  pol.finish(s);
-}
-
-SMX_D void serial_grid_walk(const DevState& s, const SoilP* sh) {
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, sh, pol);
-  sim.grid_mode = true;
-  Frame st[MAX_FRAMES];
-  int depth = 0;
-  const size_t n = (size_t)s.dimx * s.dimy;
-  size_t c = sim.next_active(0);
-  unsigned long long visited = 0;
-  Water dummy;
-  dummy.pos = {0.f, 0.f}; dummy.speed = {0.f, 0.f}; dummy.volume = 0.0; dummy.sediment = 0.0; dummy.evaprate = 0.0;
-  dummy.spill = 0; dummy.ix = dummy.iy = 0; dummy.friction = 0.f; dummy.surface = dummy.contains = 0;
-  while (c < n) {
-    const int x = (int)(c / s.dimy), y = (int)(c % s.dimy);
-    sim.seep(x, y);                                        // water.h:339
-    sim.push_frame(st, depth, x, y, 3);                    // water.h:340 WaterParticle::cascade(ivec2(x,y), .., 3)
-    sim.water_drive(dummy, false, false, st, depth);
-    visited++;
-    c = sim.next_active(c + 1);
-  }
-  // every non-active cell still "calls" WaterParticle::cascade once in the reference (counter parity)
-  sim.n_wcasc += n - visited;
-  sim.flush_counters();
-  pol.add_counter(s, C_GRID_ACTIVE, visited);
-  pol.finish(s);
-}
 
 __global__ void __launch_bounds__(64) k_water_serial(DevState s, int n) {
   SMX_LOAD_SOILS(sh)
@@ -288,8 +240,7 @@ __global__ void __launch_bounds__(256) k_ens_classify(const EnsEntry* __restrict
 // SIMDs, and one particle step is issue-bound (a few thousand dependent instructions), so one particle per wave
 // is fastest (measured at 1024^2: 1 lane 349 ms, 8 lanes 429 ms, 32 lanes 537 ms per water phase).
 static int spec_lanes() {
-  static int v = 0;
-  if (!v) { const char* e = getenv("SMX_SPEC_LANES"); v = e ? atoi(e) : 1; if (v < 1) v = 1; if (v > 64) v = 64; }
+  static const int v = (int)std::min(64ll, std::max(1ll, env_int("SMX_SPEC_LANES", 1)));
   return v;
 }
 
@@ -414,9 +365,7 @@ __global__ void __launch_bounds__(64) k_relax_apply(DevState s, BatchShared bs, 
   SMX_LOAD_SOILS(sh)
   const uint32_t i = blockIdx.x * 64u + threadIdx.x;
   if (i == 0u) {                                             // the lists of the NEXT epoch start empty (their last readers finished an epoch ago)
-    const uint32_t par = (epoch + 1u) & 1u;
-    bs.ctrl[BC_NFLOOD + par] = 0u; bs.ctrl[BC_NFLAG + par] = 0u; bs.ctrl[BC_NRUN + par] = 0u;
-    for (uint32_t k = 0; k < 9u; k++) bs.ctrl[BC_NCASC + 9u * par + k] = 0u;
+    relax_reset_lists(bs, (epoch + 1u) & 1u);
     bs.ctrl[BC_CASC_CURSOR] = 0u;                            // (this epoch's cascade dataflow starts at its first listed cell)
   }
   if (i >= nlive) return;
@@ -474,7 +423,7 @@ __global__ void __launch_bounds__(64) k_relax_cascade(DevState s, BatchShared bs
 // dynamic cursor guarantees that every dependency belongs to a wavefront that is already running, so only a fault gets there -- raises bs.ctrl[BC_STALLED], every other
 // waiter sees the flag within 1 024 polls and stops waiting too, the kernel drains, and the host fails the call (-9) instead of hanging the stream.
 // SMX_SPIN_BUDGET overrides the number of polls (tests/test_gpu_relaxed.py sets 1 to see the error).
-static uint32_t spin_budget(uint32_t dflt) { static const long v = [] { const char* e = getenv("SMX_SPIN_BUDGET"); return e ? atol(e) : -1L; }(); return v >= 0 ? (uint32_t)v : dflt; }
+static uint32_t spin_budget(uint32_t dflt) { static const long long v = env_int("SMX_SPIN_BUDGET", -1); return v >= 0 ? (uint32_t)v : dflt; }
 __device__ __forceinline__ bool spin_wait_while(const uint32_t* f, uint32_t busy, uint32_t* stalled, uint32_t budget, uint32_t sleep_a, uint32_t naps) {
   uint32_t spins = 0;
   while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == busy) {
@@ -598,6 +547,7 @@ __global__ void __launch_bounds__(256) k_relax_tail(DevState s, BatchShared bs, 
     }
     if (mine) busy = 1u;
     if (threadIdx.x == 0) {                                                                      // the lists of the next epoch start empty
+      // (relax_reset_lists spelled out: through the function the compiler also reorders code elsewhere in this kernel -- profiles/r08_refactor_kernel_diff.md)
       bs.ctrl[BC_NFLOOD + (par ^ 1u)] = 0u; bs.ctrl[BC_NFLAG + (par ^ 1u)] = 0u; bs.ctrl[BC_NRUN + (par ^ 1u)] = 0u;
       for (uint32_t q = 0; q < 9u; q++) bs.ctrl[BC_NCASC + 9u * (par ^ 1u) + q] = 0u;
     }
@@ -738,6 +688,7 @@ __global__ void __launch_bounds__(256) k_relax_epochs(DevState s, BatchShared bs
       }
       if (mine) __hip_atomic_store(&bar->busy[k & 1u], bs.rtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (tags are unique and never 0: nothing to reset)
       if (blockIdx.x == 0 && threadIdx.x == 0) {                                                 // the lists of the next epoch start empty
+        // (relax_reset_lists spelled out, as in k_relax_tail)
         bs.ctrl[BC_NFLOOD + (par ^ 1u)] = 0u; bs.ctrl[BC_NFLAG + (par ^ 1u)] = 0u; bs.ctrl[BC_NRUN + (par ^ 1u)] = 0u;
         for (uint32_t q = 0; q < 9u; q++) bs.ctrl[BC_NCASC + 9u * (par ^ 1u) + q] = 0u;
         bs.ctrl[BC_CASC_CURSOR] = 0u;
@@ -856,7 +807,7 @@ __global__ void __launch_bounds__(256) k_relax_epochs(DevState s, BatchShared bs
 // how many particles share a wavefront: as few as fill `SMX_BATCH_WAVES` wavefronts (default 256 = one per CU; 0 = always 64;
 // measured in profiles/r02_batched_schedules.md, sweep 5). Which lane runs a slot has no influence on results.
 static uint32_t batch_lanes_per_wave(uint32_t nlive) {
-  static const uint32_t waves = [] { const char* e = getenv("SMX_BATCH_WAVES"); return e ? (uint32_t)atoi(e) : 256u; }();
+  static const uint32_t waves = (uint32_t)env_int("SMX_BATCH_WAVES", 256);
   if (!waves) return 64u;
   const uint32_t l = (nlive + waves - 1u) / waves;
   return l < 1u ? 1u : (l > 64u ? 64u : l);
@@ -937,7 +888,6 @@ __global__ void __launch_bounds__(256) k_grid_tiles_init(DevState s, BatchShared
 // (experiments, SMX_FLOOD_PROF=1: where does a sweep go? [0..31] tiles by log2 of their sweep time in 100 MHz ticks, [32..63] their active cells, [72..103] the steps of
 //  their nested particles, [64] tiles, [65] ticks sweeping, [66] ticks waiting for tiles of earlier colours, [67] the longest sweep; printed by smx_destroy)
 __device__ unsigned long long g_tile_prof[104];
-static bool flood_prof_on() { static const bool on = [] { const char* e = getenv("SMX_FLOOD_PROF"); return e && atoi(e) != 0; }(); return on; }
 __global__ void __launch_bounds__(64) k_grid_tiles_flow(DevState s, BatchShared bs, GridTiles g, const uint32_t* __restrict__ order, uint32_t n, uint32_t poll_naps_prof, uint32_t budget) {
   const uint32_t poll_naps = poll_naps_prof & 0x7FFFFFFFu; const bool prof = (poll_naps_prof >> 31) != 0u;
   SMX_LOAD_SOILS(sh)
@@ -1332,7 +1282,9 @@ struct roctx_range {
   explicit roctx_range(const char* name) { g_roctx.load(); on = g_roctx.push != nullptr; if (on) g_roctx.push(name); }
   ~roctx_range() { if (on) g_roctx.pop(); }
 };
-struct EvPair { hipEvent_t a, b; int phase; uint32_t launches; };
+// what a pair of HIP events brackets (smx_timing): a phase of the tick, or kernels inside one
+enum Phase { PH_WATER = 0, PH_GRID, PH_WIND, PH_FREQ, PH_K_WATER, PH_K_WIND, PH_K_CLASSIFY, PH_K_GRIDTILES, PH_K_MAPFREQ, PH_K_TAIL, PH_K_EPOCHS, PH_K_GRID_CHILDREN, PH_K_FLOODS };
+struct EvPair { hipEvent_t a, b; Phase phase; uint32_t launches; };
 // the stream a context (or an ensemble) queues its work on, and the HIP-event brackets of its phases (smx_timing)
 struct EventTimer {
   hipStream_t stream = nullptr;
@@ -1407,6 +1359,13 @@ struct smx_ctx : EventTimer {
     }                                                                                                 \
   } while (0)
 
+// a kernel template over the kind of particle: k<true> for wind, k<false> for water, same launch shape, same arguments
+#define LAUNCH_WIND_WATER(wind, k, grid, block, st, ...)                                              \
+  do {                                                                                                \
+    if (wind) hipLaunchKernelGGL(k<true>, grid, block, 0, st, __VA_ARGS__);                           \
+    else hipLaunchKernelGGL(k<false>, grid, block, 0, st, __VA_ARGS__);                               \
+  } while (0)
+
 static hipEvent_t ev_get(EventTimer* ctx) {
   if (!ctx->evpool.empty()) { hipEvent_t e = ctx->evpool.back(); ctx->evpool.pop_back(); return e; }
   hipEvent_t e; hipEventCreate(&e); return e;
@@ -1416,19 +1375,19 @@ static void drain_events(EventTimer* ctx) {
     hipEventSynchronize(p.b);
     float ms = 0; hipEventElapsedTime(&ms, p.a, p.b);
     switch (p.phase) {
-      case 0: ctx->timing.ms_water += ms; ctx->timing.launches_water++; break;
-      case 1: ctx->timing.ms_grid += ms; ctx->timing.launches_grid++; break;
-      case 2: ctx->timing.ms_wind += ms; ctx->timing.launches_wind++; break;
-      case 4: ctx->timing.ms_kernel_water += ms; ctx->timing.launches_kernel_water += p.launches; break;
-      case 5: ctx->timing.ms_kernel_wind += ms; ctx->timing.launches_kernel_wind += p.launches; break;
-      case 6: ctx->timing.ms_kernel_classify += ms; ctx->timing.launches_kernel_classify += p.launches; break;
-      case 7: ctx->timing.ms_kernel_gridtiles += ms; ctx->timing.launches_kernel_gridtiles += p.launches; break;
-      case 8: ctx->timing.ms_kernel_mapfreq += ms; ctx->timing.launches_kernel_mapfreq += p.launches; break;
-      case 9: ctx->timing.ms_kernel_tail += ms; ctx->timing.launches_kernel_tail++; ctx->timing.epochs_kernel_tail += p.launches; break;          // k_relax_tail (p.launches = its epochs)
-      case 10: ctx->timing.ms_kernel_epochs += ms; ctx->timing.launches_kernel_epochs++; ctx->timing.epochs_kernel_epochs += p.launches; break;   // k_relax_epochs
-      case 11: ctx->timing.ms_kernel_grid_children += ms; ctx->timing.launches_kernel_grid_children += p.launches; break;
-      case 12: ctx->timing.ms_kernel_floods += ms; ctx->timing.launches_kernel_floods += p.launches; break;       // k_relax_floods, the bracketed launches
-      default: ctx->timing.ms_freq += ms; ctx->timing.launches_freq++; break;
+      case PH_WATER: ctx->timing.ms_water += ms; ctx->timing.launches_water++; break;
+      case PH_GRID: ctx->timing.ms_grid += ms; ctx->timing.launches_grid++; break;
+      case PH_WIND: ctx->timing.ms_wind += ms; ctx->timing.launches_wind++; break;
+      case PH_FREQ: ctx->timing.ms_freq += ms; ctx->timing.launches_freq++; break;
+      case PH_K_WATER: ctx->timing.ms_kernel_water += ms; ctx->timing.launches_kernel_water += p.launches; break;
+      case PH_K_WIND: ctx->timing.ms_kernel_wind += ms; ctx->timing.launches_kernel_wind += p.launches; break;
+      case PH_K_CLASSIFY: ctx->timing.ms_kernel_classify += ms; ctx->timing.launches_kernel_classify += p.launches; break;
+      case PH_K_GRIDTILES: ctx->timing.ms_kernel_gridtiles += ms; ctx->timing.launches_kernel_gridtiles += p.launches; break;
+      case PH_K_MAPFREQ: ctx->timing.ms_kernel_mapfreq += ms; ctx->timing.launches_kernel_mapfreq += p.launches; break;
+      case PH_K_TAIL: ctx->timing.ms_kernel_tail += ms; ctx->timing.launches_kernel_tail++; ctx->timing.epochs_kernel_tail += p.launches; break;          // k_relax_tail (p.launches = its epochs)
+      case PH_K_EPOCHS: ctx->timing.ms_kernel_epochs += ms; ctx->timing.launches_kernel_epochs++; ctx->timing.epochs_kernel_epochs += p.launches; break;   // k_relax_epochs
+      case PH_K_GRID_CHILDREN: ctx->timing.ms_kernel_grid_children += ms; ctx->timing.launches_kernel_grid_children += p.launches; break;
+      case PH_K_FLOODS: ctx->timing.ms_kernel_floods += ms; ctx->timing.launches_kernel_floods += p.launches; break;       // k_relax_floods, the bracketed launches
     }
     ctx->evpool.push_back(p.a); ctx->evpool.push_back(p.b);
   }
@@ -1436,7 +1395,7 @@ static void drain_events(EventTimer* ctx) {
 }
 struct PhaseTimer {
   EventTimer* ctx; EvPair p;
-  PhaseTimer(EventTimer* c, int phase, uint32_t launches = 1) : ctx(c) { p.a = ev_get(c); p.b = ev_get(c); p.phase = phase; p.launches = launches; hipEventRecord(p.a, c->stream); }
+  PhaseTimer(EventTimer* c, Phase phase, uint32_t launches = 1) : ctx(c) { p.a = ev_get(c); p.b = ev_get(c); p.phase = phase; p.launches = launches; hipEventRecord(p.a, c->stream); }
   ~PhaseTimer() { hipEventRecord(p.b, ctx->stream); ctx->pending.push_back(p); if (ctx->pending.size() > 512) drain_events(ctx); }
 };
 
@@ -1506,9 +1465,10 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t s
   const smx_soil air = {0, 0, 0, 0, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // surface.h:43-49
   if (smx_set_soils(ctx, &air, 1)) return -1;
   if (smx_srand(ctx, 1)) return -1;
-  if (const char* e = getenv("SMX_RELAX_WIND_MIN")) ctx->relax_wind_min = (uint32_t)atoll(e);   // (experiments)
-  if (const char* e = getenv("SMX_RELAX_WATER_STEPS")) { const int v = atoi(e); if (v >= 1 && v <= R_MAXSTEPS) ctx->relax_water_steps = v; }   // (experiment)
-  if (const char* e = getenv("SMX_RELAX_WIND_STEPS")) { const int v = atoi(e); if (v >= 1 && v <= R_MAXSTEPS) ctx->relax_wind_steps = v; }
+  // (experiments; read at every context creation, and only a variable that is set overrides)
+  if (env_str("SMX_RELAX_WIND_MIN")) ctx->relax_wind_min = (uint32_t)env_int("SMX_RELAX_WIND_MIN", 0);
+  if (const int v = (int)env_int("SMX_RELAX_WATER_STEPS", 0); v >= 1 && v <= R_MAXSTEPS) ctx->relax_water_steps = v;
+  if (const int v = (int)env_int("SMX_RELAX_WIND_STEPS", 0); v >= 1 && v <= R_MAXSTEPS) ctx->relax_wind_steps = v;
   return 0;
 }
 int smx_create(const smx_config* cfg, smx_ctx** out) { return create_range(cfg, 0, cfg ? cfg->dimx : 0, nullptr, out); }
@@ -1527,14 +1487,14 @@ void smx_destroy(smx_ctx* ctx) {
   if (ctx->ensemble) { ctx->err = "smx_destroy: this context is a member of an ensemble; smx_ensemble_destroy frees it (nothing was freed)"; return; }
   strips_free(ctx);
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
-  if (getenv("SMX_FLOOD_PROF") && atoi(getenv("SMX_FLOOD_PROF"))) {
+  if (flood_prof()) {
     unsigned long long h[72];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_flood_prof), sizeof(h)) == hipSuccess && h[64]) {
       fprintf(stderr, "[soilmx] k_relax_floods: %llu floods acted, mean %.1f us; %llu listed floods waited (did not hold their tiles). duration bucket (us): floods, nested steps per flood\n", h[64], 0.01 * (double)h[65] / (double)h[64], h[66]);
       for (int b = 0; b < 32; b++) if (h[b]) fprintf(stderr, "   [%8.1f, %8.1f) %9llu  %7.1f\n", 0.01 * (double)(1ull << b), 0.01 * (double)(2ull << b), h[b], (double)h[32 + b] / (double)h[b]);
     }
   }
-  if (getenv("SMX_FLOOD_PROF") && atoi(getenv("SMX_FLOOD_PROF"))) {
+  if (flood_prof()) {
     unsigned long long h[104];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_prof), sizeof(h)) == hipSuccess && h[64]) {
       fprintf(stderr, "[soilmx] k_grid_tiles_flow: %llu tiles swept, mean %.1f us, longest %.1f us; waiting for earlier colours: mean %.1f us per tile. sweep time bucket (us): tiles, active cells per tile, nested steps per tile, us per active cell\n",
@@ -1552,7 +1512,7 @@ void smx_destroy(smx_ctx* ctx) {
       for (int k = 0; k < 10; k++) if (h[2 * k + 1]) fprintf(stderr, "[soilmx] section %-40s %10llu x %7.2f us = %9.1f ms\n", nm[k], h[2 * k + 1], 0.01 * (double)h[2 * k] / (double)h[2 * k + 1], 1e-5 * (double)h[2 * k]);
   }
 #endif
-  if (ctx->d_gbar && getenv("SMX_RELAX_MEGA_FLAGS") && (atoi(getenv("SMX_RELAX_MEGA_FLAGS")) & 2)) {   // (experiments: where an epoch of k_relax_epochs goes, workgroup 0's clock)
+  if (ctx->d_gbar && (relax_mega_flags() & 2u)) {   // (experiments: where an epoch of k_relax_epochs goes, workgroup 0's clock)
     GridBar hb; if (hipMemcpy(&hb, ctx->d_gbar, sizeof(hb), hipMemcpyDeviceToHost) == hipSuccess && hb.prof[10]) {
       static const char* nm[10] = {"step", "sync", "apply", "sync", "filter", "sync", "colours", "sync", "floods", "sync"};
       fprintf(stderr, "[soilmx] k_relax_epochs, %llu epochs, microseconds per epoch (100 MHz clock):", hb.prof[10]);
@@ -1666,18 +1626,7 @@ void* smx_stream(smx_ctx* ctx) { return (void*)ctx->stream; }
 
 int smx_srand(smx_ctx* ctx, uint32_t seed) {   // glibc srandom_r, TYPE_3 (stdlib/random_r.c)
   RandState r;
-  if (seed == 0) seed = 1;
-  int32_t word = (int32_t)seed;
-  r.ring[0] = (uint32_t)word;
-  for (int i = 1; i < 31; i++) {
-    long hi = word / 127773, lo = word % 127773;
-    word = (int32_t)(16807 * lo - 2836 * hi);
-    if (word < 0) word += 2147483647;
-    r.ring[i] = (uint32_t)word;
-  }
-  uint32_t idx = 34;
-  for (int i = 0; i < 310; i++) { uint32_t v = r.ring[idx % 31] + r.ring[(idx - 3) % 31]; r.ring[idx % 31] = v; idx++; }
-  r.idx = idx; r.calls = 0;
+  rand_seed(r, seed);
   HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -1709,7 +1658,7 @@ int smx_rand_advance(smx_ctx* ctx, uint64_t ndraws) {
   RandState r;
   HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (uint64_t i = 0; i < ndraws; i++) { uint32_t v = r.ring[r.idx % 31] + r.ring[(r.idx - 3) % 31]; r.ring[r.idx % 31] = v; r.idx++; }
+  rand_skip(r, ndraws);
   r.calls += ndraws;
   HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2035,7 +1984,7 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
   // nested-particle slots of a sub-phase: 8192 on the device (21 KB of per-slot records each: 170 MB). With the 1 024 of round 3 a
   // sub-phase of 4 096 particles at the headline's density was cut -- everything in flight rolled back on one lane and run again --
   // after ~650 committed particles (profiles/r04_exact_subphases.md)
-  static const uint32_t maxnest = [] { const char* e = getenv("SMX_SPEC_MAXNEST"); const int v = e ? atoi(e) : 8192; return (uint32_t)(v < 128 ? 128 : (v > 60000 ? 60000 : v)); }();
+  static const uint32_t maxnest = (uint32_t)std::min(60000ll, std::max(128ll, env_int("SMX_SPEC_MAXNEST", 8192)));
   sh.maxnest = ctx->spec_maxnest ? ctx->spec_maxnest : maxnest;
   const uint32_t slots = cap + sh.maxnest;                  // per-slot records (soil_spec.h "rand() SLOTS")
   HIPCHK(hipMalloc(&sh.part, (size_t)slots * sizeof(SpecPart)));
@@ -2063,27 +2012,23 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
 static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed, int* outcome) {
   // engine mode per phase: water = blocked-filter + suspend/resume, wind = suspend/resume only (long wind particles
   // are nearly always "blocked somewhere": better to let them run up to the contested cell) -- host-sim measurements
-  static const uint32_t mode_water = [] { const char* e = getenv("SMX_SPEC_MODE"); return e ? (uint32_t)atoi(e) : 3u; }();
-  static const uint32_t mode_wind = [] { const char* e = getenv("SMX_SPEC_MODE_WIND"); return e ? (uint32_t)atoi(e) : 2u; }();
+  static const uint32_t mode_water = (uint32_t)env_int("SMX_SPEC_MODE", 3);
+  static const uint32_t mode_wind = (uint32_t)env_int("SMX_SPEC_MODE_WIND", 2);
   ctx->sh.mode = wind ? mode_wind : mode_water;
   const SpecShared& sh = ctx->sh;
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemsetAsync(sh.stamp, 0, ctx->ncells * 4, st));
   hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, st, ctx->d, sh, (uint32_t)n);
   const uint32_t L = (uint32_t)spec_lanes();
-  static const bool wind_scout = [] { const char* e = getenv("SMX_WIND_SCOUT"); return e ? atoi(e) != 0 : true; }();
-  static const bool coop_scout = [] { const char* e = getenv("SMX_COOP"); return e ? atoi(e) != 0 : true; }();
+  static const bool wind_scout = env_flag("SMX_WIND_SCOUT", true);
   const uint32_t ns = (uint32_t)n + SPEC_SCOUT_MARGIN;       // scouted slots
-  if (coop_scout) {
-    if (!wind) hipLaunchKernelGGL(k_spec_scout_coop<false>, dim3(ns), dim3(64), 0, st, ctx->d, sh);
-    else if (wind_scout) hipLaunchKernelGGL(k_spec_scout_coop<true>, dim3(ns), dim3(64), 0, st, ctx->d, sh);
-  } else {
-    if (!wind) hipLaunchKernelGGL(k_spec_scout<false>, dim3((ns + L - 1) / L), dim3(64), 0, st, ctx->d, sh, L);
-    else if (wind_scout) hipLaunchKernelGGL(k_spec_scout<true>, dim3((ns + L - 1) / L), dim3(64), 0, st, ctx->d, sh, L);
+  if (!wind || wind_scout) {
+    if (coop_on()) LAUNCH_WIND_WATER(wind, k_spec_scout_coop, dim3(ns), dim3(64), st, ctx->d, sh);
+    else LAUNCH_WIND_WATER(wind, k_spec_scout, dim3((ns + L - 1) / L), dim3(64), st, ctx->d, sh, L);
   }
   uint32_t np = (uint32_t)n > SPEC_WINDOW ? SPEC_WINDOW : (uint32_t)n, last_base = 0, stall = 0;
   *outcome = 0;
-  static const bool trace_rounds = [] { const char* e = getenv("SMX_TRACE_ROUNDS"); return e && atoi(e) != 0; }();
+  static const bool trace_rounds = env_flag("SMX_TRACE_ROUNDS", false);
   uint32_t prev_exec = 0, prev_sum = 0;
   if (trace_rounds) HIPCHK(hipStreamSynchronize(st));
   auto t_round = std::chrono::steady_clock::now();
@@ -2092,15 +2037,9 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
     hipLaunchKernelGGL(k_spec_claim, dim3(np), dim3(64), 0, st, sh);
     if (sh.mode & 1u) hipLaunchKernelGGL(k_spec_select, dim3(np), dim3(64), 0, st, sh);
     {
-      PhaseTimer tk(ctx, wind ? 5 : 4);
-      static const bool coop = [] { const char* e = getenv("SMX_COOP"); return e ? atoi(e) != 0 : true; }();
-      if (coop) {
-        if (wind) hipLaunchKernelGGL(k_spec_exec_coop<true>, dim3(np), dim3(64), 0, st, ctx->d, sh);
-        else hipLaunchKernelGGL(k_spec_exec_coop<false>, dim3(np), dim3(64), 0, st, ctx->d, sh);
-      } else {
-        if (wind) hipLaunchKernelGGL(k_spec_exec<true>, dim3((np + L - 1) / L), dim3(64), 0, st, ctx->d, sh, L);
-        else hipLaunchKernelGGL(k_spec_exec<false>, dim3((np + L - 1) / L), dim3(64), 0, st, ctx->d, sh, L);
-      }
+      PhaseTimer tk(ctx, wind ? PH_K_WIND : PH_K_WATER);
+      if (coop_on()) LAUNCH_WIND_WATER(wind, k_spec_exec_coop, dim3(np), dim3(64), st, ctx->d, sh);
+      else LAUNCH_WIND_WATER(wind, k_spec_exec, dim3((np + L - 1) / L), dim3(64), st, ctx->d, sh, L);
     }
     hipLaunchKernelGGL(k_spec_boundary, dim3(1), dim3(1024), 0, st, ctx->d, sh);
     HIPCHK(hipMemcpyAsync(ctx->h_ctrl, sh.ctrl, SC_COUNT * 4, hipMemcpyDeviceToHost, st));
@@ -2146,13 +2085,13 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
 // committed: 0.4 M steps/s on the headline workload). Only what the speculation cannot do at all goes to the serial walker.
 static int spec_phase(smx_ctx* ctx, int32_t n, bool wind) {
   if (n <= 0) return 0;
-  static const uint32_t SPEC_SUB_ENV = [] { const char* e = getenv("SMX_SPEC_SUB"); const int v = e ? atoi(e) : 4096; return (uint32_t)(v < 64 ? 64 : v); }();
+  static const uint32_t SPEC_SUB_ENV = (uint32_t)std::max(64ll, env_int("SMX_SPEC_SUB", 4096));
   const uint32_t SPEC_SUB = ctx->spec_sub ? ctx->spec_sub : SPEC_SUB_ENV;
   if (spec_alloc(ctx, std::min<uint32_t>((uint32_t)n, SPEC_SUB))) return -1;
   hipStream_t st = ctx->stream;
   uint32_t remaining = (uint32_t)n;
   auto serial = [&](uint32_t k) {                            // the reference's order on one lane, from the state as it stands
-    PhaseTimer tk(ctx, wind ? 5 : 4);
+    PhaseTimer tk(ctx, wind ? PH_K_WIND : PH_K_WATER);
     if (wind) hipLaunchKernelGGL(k_wind_serial, dim3(1), dim3(64), 0, st, ctx->d, (int)k);
     else hipLaunchKernelGGL(k_water_serial, dim3(1), dim3(64), 0, st, ctx->d, (int)k);
   };
@@ -2173,7 +2112,7 @@ static int spec_phase(smx_ctx* ctx, int32_t n, bool wind) {
 
 
 static void launch_classify(smx_ctx* ctx);
-// ---------------- batched engine: host driver (mirrored for the CPU by tests/hostsim/hostsim.cpp batch_generations) ----------------
+// ---------------- batched engine: host driver (tests/hostsim/hostsim.cpp batch_generations drives the same headers on host threads) ----------------
 static int batch_alloc(smx_ctx* ctx, uint32_t nslots, bool wind) {
   BatchShared& bs = ctx->bs;
   if (!bs.ctrl) {
@@ -2273,6 +2212,17 @@ static int sort_children(smx_ctx* ctx, uint32_t nc) {       // bs.children[0, nc
   hipLaunchKernelGGL(k_child_gather, dim3(nb), dim3(256), 0, st, ctx->bs.children, ctx->d_sidx[1], nc, ctx->d_kids);
   return 0;
 }
+// What the batch control block, as last copied to ctx->h_bctrl, says about the generation (or the grid pass) that just ended: work that
+// was dropped is an error; `nc` = the children it left, as many as the buffer holds.
+static int batch_check_ctrl(smx_ctx* ctx, uint32_t& nc) {
+  nc = ctx->h_bctrl[BC_NCHILD];
+  if (ctx->h_bctrl[BC_CHILD_LOST]) ctx->batch_children_lost += ctx->h_bctrl[BC_CHILD_LOST];
+  if (ctx->h_bctrl[BC_FREED_LOST]) { ctx->err = "batched engine: freed-node list overflow (pool nodes leaked)"; return -6; }
+  if (ctx->h_bctrl[BC_LIST_LOST]) { ctx->err = "relaxed schedule: flood / cascade list overflow (work was dropped)"; return -6; }
+  if (ctx->h_bctrl[BC_STALLED]) { ctx->err = "throughput schedule: a device-side wait ran out of its spin budget (a dataflow dependency or a barrier was never released)"; return -9; }
+  if (nc > ctx->bs.child_cap) nc = ctx->bs.child_cap;
+  return 0;
+}
 // `nepochs` dense epochs of the running relaxed water generation as one persistent cooperative launch (k_relax_epochs). 0 = launched.
 static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uint32_t nepochs) {
   hipStream_t st = ctx->stream;
@@ -2286,7 +2236,7 @@ static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uin
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax_epochs, 256, 0) != hipSuccess) per_cu = 0;
-    static const int want = [] { const char* e = getenv("SMX_RELAX_MEGA_BLOCKS"); return e ? atoi(e) : 0; }();   // (0: one workgroup per CU)
+    static const int want = (int)env_int("SMX_RELAX_MEGA_BLOCKS", 0);   // (0: one workgroup per CU)
     int nb = want > 0 ? want : ncu;
     if (nb > ncu * per_cu) nb = ncu * per_cu;
     if (!coop || nb < 1) {
@@ -2298,11 +2248,10 @@ static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uin
   BatchShared bs = ctx->bs;
   uint32_t tag0 = ctx->relax_tag + 1u;
   GridBar* bar = ctx->d_gbar;
-  static const uint32_t dense_waves_env = [] { const char* e = getenv("SMX_RELAX_MEGA_WAVES"); return e ? (uint32_t)atoi(e) : 0u; }();   // (0: one wavefront per workgroup)
-  static const uint32_t flags_env = [] { const char* e = getenv("SMX_RELAX_MEGA_FLAGS"); return e ? (uint32_t)atoi(e) : 0u; }();          // (1: every thread fences at a barrier)
-  uint32_t dense_waves = dense_waves_env ? dense_waves_env : (uint32_t)ctx->mega_blocks, flags = flags_env;
+  static const uint32_t dense_waves_env = (uint32_t)env_int("SMX_RELAX_MEGA_WAVES", 0);   // (0: one wavefront per workgroup)
+  uint32_t dense_waves = dense_waves_env ? dense_waves_env : (uint32_t)ctx->mega_blocks, flags = relax_mega_flags();
   void* args[] = {(void*)&ctx->d, (void*)&bs, (void*)&nlive, (void*)&epoch, (void*)&nepochs, (void*)&tag0, (void*)&bar, (void*)&dense_waves, (void*)&flags};
-  PhaseTimer tk(ctx, 10, nepochs);
+  PhaseTimer tk(ctx, PH_K_EPOCHS, nepochs);
   const hipError_t e = hipLaunchCooperativeKernel((const void*)k_relax_epochs, dim3((unsigned)ctx->mega_blocks), dim3(256), args, 0, st);
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -2318,13 +2267,13 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
                      int* epochs_run) {
   hipStream_t st = ctx->stream;
   const BatchShared& bs = ctx->bs;
-  static const int CHUNK = [] { const char* e = getenv("SMX_BATCH_CHUNK"); int v = e ? atoi(e) : B_CHUNK; return v < 1 ? 1 : v; }();
+  static const int CHUNK = (int)std::max(1ll, env_int("SMX_BATCH_CHUNK", B_CHUNK));
   BSched sc = batch_schedule(wind, nlive_sched, ctx->batch_dilate);
   {   // experiments only: SMX_BATCH_SCHED="tshift,dilate,maxsteps" (water) / SMX_BATCH_SCHED_WIND pins the schedule
-    static const char* ew = getenv("SMX_BATCH_SCHED"); static const char* ed = getenv("SMX_BATCH_SCHED_WIND");
+    static const char* ew = env_str("SMX_BATCH_SCHED"); static const char* ed = env_str("SMX_BATCH_SCHED_WIND");
     const char* e = wind ? ed : ew; int a, d, k;
     if (e && sscanf(e, "%d,%d,%d", &a, &d, &k) == 3) { sc.tshift = a; sc.dilate = d; sc.maxsteps = k; }
-    static const char* etw = getenv("SMX_BATCH_SCHED_TAIL"); static const char* etd = getenv("SMX_BATCH_SCHED_TAIL_WIND");   // "thr:tshift,dilate,maxsteps[;thr2:...]" (ascending thr): first thr >= nlive wins
+    static const char* etw = env_str("SMX_BATCH_SCHED_TAIL"); static const char* etd = env_str("SMX_BATCH_SCHED_TAIL_WIND");   // "thr:tshift,dilate,maxsteps[;thr2:...]" (ascending thr): first thr >= nlive wins
     const char* et = wind ? etd : etw;
     if (et) {
       const char* q = et; unsigned thr;
@@ -2335,39 +2284,29 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
     }
   }
   const bool strips = bs.strips.n > 1;
-  // relaxed schedule (SMX_ENGINE_RELAXED): water always; wind while many particles run -- its tail (a few thousand particles that
-  // fly on for up to ~13 000 steps) is better served by the exclusive schedule's 32 steps per launch. One switch per generation.
-  const bool relaxed_now = relax_gen && (!wind || nlive_sched > ctx->relax_wind_min);
-  bool regrain = sc.tshift != bs.tshift;                   // first chunk, or the claim granularity changes
-  if (relax_gen && !relaxed_now && ctx->bs.relaxed) { ctx->bs.relaxed = 0; regrain = true; }   // hand the survivors to the exclusive schedule: fresh reservations
-  batch_apply_schedule(ctx->bs, ctx->d, sc);               // (bs aliases ctx->bs: passed by value per launch)
-  ctx->bs.sphase = strips ? (int)(chunk & 1u) : STRIP_INTERIOR;   // column strips: INTERIOR and SEAM chunks alternate
-  if (strips && chunk > 0) epoch++;                        // (reservations of the previous chunk must not look current)
-  chunk++;
+  // (bs aliases ctx->bs, passed by value per launch: the plan is written before the first one)
+  const BChunkPlan plan = batch_plan_chunk(ctx->bs, ctx->d, sc, wind, nlive_sched, relax_gen, ctx->relax_wind_min, ctx->relax_wind_steps, ctx->relax_water_steps, first, epoch, chunk);
+  const bool regrain = plan.regrain;
   if (regrain) {                                           // (the planes hold the tile columns of the context's range)
     const size_t nt = (size_t)(((ctx->d.x_hi - 1) >> bs.tshift) - (ctx->d.x_lo >> bs.tshift) + 1) * bs.nty;
     HIPCHK(hipMemsetAsync(bs.claim[0], 0, nt * 8, st)); HIPCHK(hipMemsetAsync(bs.claim[1], 0, nt * 8, st));
   }
-  if ((regrain || strips) && nlive) {                      // under strips every chunk starts with fresh reservations
-    if (wind) hipLaunchKernelGGL(k_batch_reclaim<true>, dim3((nlive + 63u) / 64u), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
-    else hipLaunchKernelGGL(k_batch_reclaim<false>, dim3((nlive + 63u) / 64u), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
-  }
+  if ((regrain || strips) && nlive)                        // under strips every chunk starts with fresh reservations
+    LAUNCH_WIND_WATER(wind, k_batch_reclaim, dim3((nlive + 63u) / 64u), dim3(64), st, ctx->d, bs, nlive, epoch);
   int chunk_epochs = CHUNK;
-  if (relaxed_now) {
+  if (plan.relaxed_now) {
     // relaxed schedule: per epoch one step of every running particle, the queued edits per cell, the nine cascade colours,
-    // then one flood epoch behind claim tiles. Nested generations live a few steps: shorter chunks there (without strips the
-    // result does not depend on where a generation is cut into chunks; with strips the chunk is the unit of the exchange).
-    static const int RCHUNK_KIDS = [] { const char* e = getenv("SMX_RELAX_CHUNK_KIDS"); int v = e ? atoi(e) : 8; return v < 1 ? 1 : v; }();
-    static const bool use_tail = [] { const char* e = getenv("SMX_RELAX_TAIL"); return e ? atoi(e) != 0 : true; }();
-    static const uint32_t tail_at_env = [] { const char* e = getenv("SMX_RELAX_TAIL_AT"); return e ? (uint32_t)atoi(e) : RELAX_TAIL; }();
+    // then one flood epoch behind claim tiles. Without strips the chunk lengths are the launch shape's to choose (batch_plan_chunk).
+    static const int RCHUNK_KIDS = (int)std::max(1ll, env_int("SMX_RELAX_CHUNK_KIDS", 8));
+    static const bool use_tail = env_flag("SMX_RELAX_TAIL", true);
+    static const uint32_t tail_at_env = (uint32_t)env_int("SMX_RELAX_TAIL_AT", RELAX_TAIL);
     const uint32_t tail_at = ctx->relax_tail_at >= 0 ? (uint32_t)ctx->relax_tail_at : tail_at_env;
     const bool tail = !wind && use_tail && nlive <= tail_at;
-    static const bool use_mega_env = [] { const char* e = getenv("SMX_RELAX_MEGA"); return e ? atoi(e) != 0 : false; }();   // (off by default: measured slower, see k_relax_epochs)
+    static const bool use_mega_env = env_flag("SMX_RELAX_MEGA", false);   // (off by default: measured slower, see k_relax_epochs)
     const bool use_mega = ctx->relax_persistent >= 0 ? ctx->relax_persistent != 0 : use_mega_env;
-    static const int mega_chunk = [] { const char* e = getenv("SMX_RELAX_MEGA_CHUNK"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : v; }();   // (0: the chunk lengths of the per-phase launches)
+    static const int mega_chunk = (int)std::max(0ll, env_int("SMX_RELAX_MEGA_CHUNK", 0));   // (0: the chunk lengths of the per-phase launches)
     const bool mega = !wind && !tail && use_mega && !ctx->mega_off && bs.cstate != nullptr;
-    chunk_epochs = strips ? B_CHUNK : (tail ? 64 : (mega && mega_chunk ? mega_chunk : (first ? CHUNK : RCHUNK_KIDS)));
-    ctx->bs.rstride = wind ? 2 * ctx->relax_wind_steps : std::max(2, ctx->relax_water_steps); ctx->bs.rsteps = wind ? ctx->relax_wind_steps : ctx->relax_water_steps;
+    chunk_epochs = strips ? plan.chunk_epochs : (tail ? 64 : (mega && mega_chunk ? mega_chunk : (first ? CHUNK : RCHUNK_KIDS)));
     if (ctx->relax_tag > 0x7FFF0000u) { ctx->relax_tag = 0; HIPCHK(hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, st)); HIPCHK(hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, st)); }   // (tags never repeat; 2 * tag + 1 fits 32 bits)
     if (strips) HIPCHK(hipMemsetAsync(bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // (the epoch skipped between two chunks breaks the lists' parity hand-over)
     if (strips && !wind) {                                   // who waits for a flood on this device right now?
@@ -2375,7 +2314,7 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
     }
     if (nlive == 0) { epoch += (uint32_t)chunk_epochs; ctx->relax_tag += (uint32_t)chunk_epochs; }   // (a strip with nobody home this chunk)
     else if (tail) {                                         // few particles left: whole epochs inside one workgroup (k_relax_tail)
-      PhaseTimer tk(ctx, 9, (uint32_t)chunk_epochs);
+      PhaseTimer tk(ctx, PH_K_TAIL, (uint32_t)chunk_epochs);
       hipLaunchKernelGGL(k_relax_tail, dim3(1), dim3(256), 0, st, ctx->d, bs, nlive, epoch, (uint32_t)chunk_epochs, ctx->relax_tag + 1u);
       ctx->relax_tag += (uint32_t)chunk_epochs; epoch += (uint32_t)chunk_epochs;
     } else if (mega && relax_epochs_launch(ctx, nlive, epoch, (uint32_t)chunk_epochs) == 0) {   // the chunk's dense epochs as ONE persistent launch (k_relax_epochs)
@@ -2384,26 +2323,23 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
       const uint32_t lpw = batch_lanes_per_wave(nlive);
       const unsigned nbl = (nlive + lpw - 1u) / lpw, nb64 = (nlive + 63u) / 64u;
       const unsigned ncb = (unsigned)(((size_t)nlive * (size_t)(wind ? ctx->bs.rstride : ctx->bs.rsteps) + 63u) / 64u);   // worst case of the flagged / one cascade list
-      static const unsigned fb_min = [] { const char* e = getenv("SMX_RELAX_FLOOD_BLOCKS"); return e ? (unsigned)atoi(e) : 1024u; }();
+      static const unsigned fb_min = (unsigned)env_int("SMX_RELAX_FLOOD_BLOCKS", 1024);
       const unsigned nfb = std::max(fb_min, (unsigned)((nslots + 63u) / 64u));   // floods: at least 1024 wavefronts to spread over
       for (int k = 0; k < chunk_epochs; k++, epoch++) {
         ctx->bs.rtag = ++ctx->relax_tag;
         {
           // the step kernel between its own pair of events -- every `sample`-th launch (an event pair costs a few microseconds of an epoch
           // that lasts a few hundred; the average launch duration bench.py reports is over the bracketed launches only)
-          static const int sample = [] { const char* e = getenv("SMX_STEP_EVENT_SAMPLE"); const int v = e ? atoi(e) : 8; return v < 0 ? 0 : v; }();
+          static const int sample = (int)std::max(0ll, env_int("SMX_STEP_EVENT_SAMPLE", 8));
           const bool timed = sample > 0 && (k % sample) == 0;
           if (wind) ctx->timing.launches_step_wind++; else ctx->timing.launches_step_water++;   // (every launch, bracketed or not)
-          if (timed) { PhaseTimer tk(ctx, wind ? 5 : 4, 1u);
-            if (wind) hipLaunchKernelGGL(k_relax_step<true>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-            else hipLaunchKernelGGL(k_relax_step<false>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-          } else if (wind) hipLaunchKernelGGL(k_relax_step<true>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-          else hipLaunchKernelGGL(k_relax_step<false>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
+          if (timed) { PhaseTimer tk(ctx, wind ? PH_K_WIND : PH_K_WATER, 1u); LAUNCH_WIND_WATER(wind, k_relax_step, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw); }
+          else LAUNCH_WIND_WATER(wind, k_relax_step, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
         }
         hipLaunchKernelGGL(k_relax_apply, dim3(nb64), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
         hipLaunchKernelGGL(k_relax_filter, dim3(ncb), dim3(64), 0, st, ctx->d, bs, epoch);
-        static const unsigned casc_blocks = [] { const char* e = getenv("SMX_RELAX_CASC_BLOCKS"); return e ? (unsigned)atoi(e) : 64u; }();
-        static const unsigned casc_flow = [] { const char* e = getenv("SMX_RELAX_CASC_FLOW"); return e ? (unsigned)atoi(e) : 1024u; }();   // 0: nine launches (round 4)
+        static const unsigned casc_blocks = (unsigned)env_int("SMX_RELAX_CASC_BLOCKS", 64);
+        static const unsigned casc_flow = (unsigned)env_int("SMX_RELAX_CASC_FLOW", 1024);   // 0: nine launches (round 4)
         if (casc_flow && bs.cstate) hipLaunchKernelGGL(k_relax_cascade_flow, dim3(std::min(ncb, casc_flow)), dim3(64), 0, st, ctx->d, bs, epoch, spin_budget(1u << 24));
         else {
           const unsigned ncc = std::min(ncb, std::max(1u, casc_blocks));
@@ -2411,27 +2347,24 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
         }
         if (!wind) {                                         // (bracketed every 7th launch of the context: a stride coprime to the every-4th-epoch rule of relax_floods_due)
           ctx->timing.launches_floods_all++;
-          static const uint32_t fprof = [] { const char* e = getenv("SMX_FLOOD_PROF"); return e ? (uint32_t)atoi(e) : 0u; }();
-          if (ctx->flood_launch_no++ % 7u == 0u) { PhaseTimer tk(ctx, 12, 1u); hipLaunchKernelGGL(k_relax_floods, dim3(nfb), dim3(64), 0, st, ctx->d, bs, epoch, fprof); }
+          const uint32_t fprof = flood_prof();
+          if (ctx->flood_launch_no++ % 7u == 0u) { PhaseTimer tk(ctx, PH_K_FLOODS, 1u); hipLaunchKernelGGL(k_relax_floods, dim3(nfb), dim3(64), 0, st, ctx->d, bs, epoch, fprof); }
           else hipLaunchKernelGGL(k_relax_floods, dim3(nfb), dim3(64), 0, st, ctx->d, bs, epoch, fprof);
         }
       }
     }
   } else if (nlive) {
-    PhaseTimer tk(ctx, wind ? 5 : 4, (uint32_t)CHUNK);   // CHUNK back-to-back launches of the epoch kernel, nothing else
+    PhaseTimer tk(ctx, wind ? PH_K_WIND : PH_K_WATER, (uint32_t)CHUNK);   // CHUNK back-to-back launches of the epoch kernel, nothing else
     if (wind) ctx->timing.launches_step_wind += (uint64_t)CHUNK; else ctx->timing.launches_step_water += (uint64_t)CHUNK;
     const uint32_t lpw = batch_lanes_per_wave(nlive);
     const unsigned nbl = (nlive + lpw - 1u) / lpw;
     // more wavefronts than SIMDs (> 65 536 running particles): the 256-register build, two wavefronts per SIMD -- +5 % at 16384^2,
     // nothing below (profiles/r02_batched_schedules.md); results do not depend on it
-    static const uint32_t occ2_above = [] { const char* e = getenv("SMX_BATCH_OCC2_ABOVE"); return e ? (uint32_t)atoll(e) : 65536u; }();
+    static const uint32_t occ2_above = (uint32_t)env_int("SMX_BATCH_OCC2_ABOVE", 65536);
     const bool occ2 = nlive > occ2_above;
     for (int k = 0; k < CHUNK; k++, epoch++) {
-      if (occ2) {
-        if (wind) hipLaunchKernelGGL(k_batch_epoch2<true>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-        else hipLaunchKernelGGL(k_batch_epoch2<false>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-      } else if (wind) hipLaunchKernelGGL(k_batch_epoch<true>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
-      else hipLaunchKernelGGL(k_batch_epoch<false>, dim3(nbl), dim3(64), 0, st, ctx->d, bs, nlive, epoch, lpw);
+      if (occ2) LAUNCH_WIND_WATER(wind, k_batch_epoch2, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
+      else LAUNCH_WIND_WATER(wind, k_batch_epoch, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
     }
   } else epoch += (uint32_t)CHUNK;
   hipLaunchKernelGGL(k_batch_merge_freed, dim3(1), dim3(256), 0, st, ctx->d, bs);   // frees of the chunk go back on the stack
@@ -2455,9 +2388,8 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
     const BatchShared& bs = ctx->bs;
     if (first) {                                              // (suspended nested particles carry their state: no draws)
       for (uint32_t i = 0; i < 2u * nslots; i++) {
-        const uint32_t v = r.ring[r.idx % 31] + r.ring[(r.idx - 3) % 31];
-        r.ring[r.idx % 31] = v; r.idx++; r.calls++;
-        ctx->h_draws[i] = v >> 1;
+        ctx->h_draws[i] = rand_step(r) >> 1;
+        r.calls++;
       }
       HIPCHK(hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)2u * nslots * 4, hipMemcpyHostToDevice, st));
     }
@@ -2467,19 +2399,17 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
     if (relax_gen) HIPCHK(hipMemsetAsync(ctx->bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // flood, flag and cascade lists start empty
     const BChild* dk = first ? nullptr : ctx->d_kids;        // (sorted there by sort_children)
     const unsigned nb = (nslots + 63u) / 64u;
-    if (wind) hipLaunchKernelGGL(k_batch_spawn<true>, dim3(nb), dim3(64), 0, st, ctx->d, bs, nslots, dk, (const uint32_t*)nullptr);
-    else hipLaunchKernelGGL(k_batch_spawn<false>, dim3(nb), dim3(64), 0, st, ctx->d, bs, nslots, dk, (const uint32_t*)nullptr);
+    LAUNCH_WIND_WATER(wind, k_batch_spawn, dim3(nb), dim3(64), st, ctx->d, bs, nslots, dk, (const uint32_t*)nullptr);
     hipLaunchKernelGGL(k_batch_iota, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs.live, nslots);
     uint32_t nlive = nslots, epoch = 0, chunk = 0;
-    static const bool trace = [] { const char* e = getenv("SMX_TRACE_BATCH"); return e && atoi(e) != 0; }();
+    const bool trace = trace_batch();
     while (nlive > 0) {
       const auto t_chunk = std::chrono::steady_clock::now();
       const uint32_t live_in = nlive;
       int chunk_epochs = 0;
       if (run_chunk(ctx, wind, nlive, nlive, nslots, first, relax_gen, epoch, chunk, &chunk_epochs)) return -1;
       HIPCHK(hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
-      if (wind) hipLaunchKernelGGL(k_batch_compact<true>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs, nslots);
-      else hipLaunchKernelGGL(k_batch_compact<false>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs, nslots);
+      LAUNCH_WIND_WATER(wind, k_batch_compact, dim3((nslots + 255u) / 256u), dim3(256), st, bs, nslots);
       HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       nlive = ctx->h_bctrl[BC_NLIVE];
@@ -2487,16 +2417,11 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
       if (trace) fprintf(stderr, "[soilmx] batched %s gen-slots %u epochs %u..%u live %u -> %u grain %d dilate %d maxsteps %d  %.3f ms\n", wind ? "wind " : "water", nslots,
                          epoch - chunk_epochs, epoch, live_in, nlive, 1 << bs.tshift, bs.dilate, bs.maxsteps, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count());
     }
-    if (wind) hipLaunchKernelGGL(k_batch_counters<true>, dim3(64), dim3(256), 0, st, ctx->d, bs, nslots);
-    else hipLaunchKernelGGL(k_batch_counters<false>, dim3(64), dim3(256), 0, st, ctx->d, bs, nslots);
+    LAUNCH_WIND_WATER(wind, k_batch_counters, dim3(64), dim3(256), st, ctx->d, bs, nslots);
     ctx->batch_generations++;
     // children -> the next generation, in key order (the order decides slot numbers = priorities and rand() draws)
-    uint32_t nc = ctx->h_bctrl[BC_NCHILD];
-    if (ctx->h_bctrl[BC_CHILD_LOST]) ctx->batch_children_lost += ctx->h_bctrl[BC_CHILD_LOST];
-    if (ctx->h_bctrl[BC_FREED_LOST]) { ctx->err = "batched engine: freed-node list overflow (pool nodes leaked)"; return -6; }
-    if (ctx->h_bctrl[BC_LIST_LOST]) { ctx->err = "relaxed schedule: flood / cascade list overflow (work was dropped)"; return -6; }
-    if (ctx->h_bctrl[BC_STALLED]) { ctx->err = "throughput schedule: a device-side wait ran out of its spin budget (a dataflow dependency or a barrier was never released)"; return -9; }
-    if (nc > bs.child_cap) nc = bs.child_cap;
+    uint32_t nc = 0;
+    if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
     if (wind) nc = 0;
     if (nc && sort_children(ctx, nc)) return -1;             // -> ctx->d_kids, on the device
     HIPCHK(hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));   // NCHILD, CHILD_LOST
@@ -2536,7 +2461,7 @@ static int grid_sweep(smx_ctx* ctx, int phase, int tx_lo, int tx_hi) {
   HIPCHK(hipMemcpyAsync(ctx->h_tcount, ctx->d_tcount, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const uint32_t n = ctx->h_tcount[0];
-  static const bool trace = [] { const char* e = getenv("SMX_TRACE_BATCH"); return e && atoi(e) != 0; }();
+  const bool trace = trace_batch();
   const auto t_sweep = std::chrono::steady_clock::now();
   if (n > 0) {
     // the tiles with work in (colour, tile) order (the init kernel appended them as its wavefronts came); entries are unique
@@ -2550,9 +2475,9 @@ static int grid_sweep(smx_ctx* ctx, int phase, int tx_lo, int tx_hi) {
     size_t tb = ctx->tsort_bytes;
     HIPCHK(rocprim::radix_sort_keys(ctx->d_tsort, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)n, 0u, 32u, st));
     HIPCHK(hipMemsetAsync(ctx->d_tcount + 1, 0, 4, st));     // the cursor of the dataflow kernel
-    static const unsigned flow_waves = [] { const char* e = getenv("SMX_GRID_FLOW_WAVES"); const int v = e ? atoi(e) : 2048; return (unsigned)(v < 1 ? 1 : v); }();
-    static const uint32_t poll_naps = [] { const char* e = getenv("SMX_GRID_POLL_NAPS"); return e ? (uint32_t)atoi(e) : 2u; }();   // (x 3.4 us between two polls of a waiting tile)
-    { PhaseTimer tk(ctx, 7); hipLaunchKernelGGL(k_grid_tiles_flow, dim3(std::min<unsigned>(n, flow_waves)), dim3(64), 0, st, ctx->d, bs, g, ctx->d_tpend[1], n, poll_naps | (flood_prof_on() ? 0x80000000u : 0u), spin_budget(1u << 22)); }
+    static const unsigned flow_waves = (unsigned)std::max(1ll, env_int("SMX_GRID_FLOW_WAVES", 2048));
+    static const uint32_t poll_naps = (uint32_t)env_int("SMX_GRID_POLL_NAPS", 2);   // (x 3.4 us between two polls of a waiting tile)
+    { PhaseTimer tk(ctx, PH_K_GRIDTILES); hipLaunchKernelGGL(k_grid_tiles_flow, dim3(std::min<unsigned>(n, flow_waves)), dim3(64), 0, st, ctx->d, bs, g, ctx->d_tpend[1], n, poll_naps | (flood_prof() ? 0x80000000u : 0u), spin_budget(1u << 22)); }
     hipLaunchKernelGGL(k_batch_merge_freed, dim3(1), dim3(256), 0, st, ctx->d, bs);
     HIPCHK(hipStreamSynchronize(st));
     ctx->grid_passes++;
@@ -2576,21 +2501,17 @@ static int batch_grid(smx_ctx* ctx) {
   hipLaunchKernelGGL(k_batch_grid_finish, dim3(1), dim3(1), 0, st, ctx->d, v0);
   HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  uint32_t nc = ctx->h_bctrl[BC_NCHILD];
-  if (ctx->h_bctrl[BC_CHILD_LOST]) ctx->batch_children_lost += ctx->h_bctrl[BC_CHILD_LOST];
-  if (ctx->h_bctrl[BC_FREED_LOST]) { ctx->err = "batched engine: freed-node list overflow (pool nodes leaked)"; return -6; }
-  if (ctx->h_bctrl[BC_LIST_LOST]) { ctx->err = "relaxed schedule: flood / cascade list overflow (work was dropped)"; return -6; }
-  if (ctx->h_bctrl[BC_STALLED]) { ctx->err = "throughput schedule: a device-side wait ran out of its spin budget (a dataflow dependency or a barrier was never released)"; return -9; }
-  if (nc > bs.child_cap) nc = bs.child_cap;
+  uint32_t nc = 0;
+  if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
   if (nc && sort_children(ctx, nc)) return -1;
   HIPCHK(hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));
-  if (nc) { PhaseTimer tk(ctx, 11); return batch_generations(ctx, false, 0, nc); }   // the nested particles that left their tile's region
+  if (nc) { PhaseTimer tk(ctx, PH_K_GRID_CHILDREN); return batch_generations(ctx, false, 0, nc); }   // the nested particles that left their tile's region
   return 0;
 }
 
 static void launch_classify(smx_ctx* ctx) {                  // which cells can the grid pass change at all? (one flag byte per cell in, one bit out)
-  PhaseTimer tk(ctx, 6);
-  static const bool scalar = [] { const char* e = getenv("SMX_CLASSIFY_SCALAR"); return e && atoi(e) != 0; }();
+  PhaseTimer tk(ctx, PH_K_CLASSIFY);
+  static const bool scalar = env_flag("SMX_CLASSIFY_SCALAR", false);
   if (ctx->cfg.dimy % 8 == 0 && ctx->lcells % 64 == 0 && ctx->c_lo % 64 == 0 && !scalar)
     hipLaunchKernelGGL(k_grid_classify8, dim3((unsigned)((ctx->lcells / 8 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d);
   else
@@ -2619,9 +2540,8 @@ int smx_d_gen_begin(smx_ctx* ctx, int32_t wind, uint32_t nslots, const void* kid
   HIPCHK(hipStreamSynchronize(st));
   const uint32_t ndraw = kids_host ? 0u : 2u * nslots;          // (suspended nested particles carry their state: no draws)
   for (uint32_t i = 0; i < ndraw; i++) {
-    const uint32_t v = r.ring[r.idx % 31] + r.ring[(r.idx - 3) % 31];
-    r.ring[r.idx % 31] = v; r.idx++; r.calls++;
-    ctx->h_draws[i] = v >> 1;
+    ctx->h_draws[i] = rand_step(r) >> 1;
+    r.calls++;
   }
   HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, st));
   if (ndraw) HIPCHK(hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)ndraw * 4, hipMemcpyHostToDevice, st));
@@ -2644,10 +2564,7 @@ int smx_d_gen_begin(smx_ctx* ctx, int32_t wind, uint32_t nslots, const void* kid
 static int d_compact(smx_ctx* ctx, uint32_t* nlive) {
   hipStream_t st = ctx->stream; const BatchShared& bs = ctx->bs; const uint32_t nslots = ctx->d_nslots;
   HIPCHK(hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
-  if (nslots) {
-    if (ctx->d_wind) hipLaunchKernelGGL(k_batch_compact<true>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs, nslots);
-    else hipLaunchKernelGGL(k_batch_compact<false>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs, nslots);
-  }
+  if (nslots) LAUNCH_WIND_WATER(ctx->d_wind, k_batch_compact, dim3((nslots + 255u) / 256u), dim3(256), st, bs, nslots);
   HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   *nlive = ctx->h_bctrl[BC_NLIVE];
@@ -2675,18 +2592,13 @@ int smx_d_chunk(smx_ctx* ctx, uint32_t nlive_global, uint32_t* nlive_local) {
 static int d_gen_end_impl(smx_ctx* ctx, void* children_out, uint32_t cap, uint32_t* n, std::vector<BChild>* vec) {
   hipStream_t st = ctx->stream; const BatchShared& bs = ctx->bs; const uint32_t nslots = ctx->d_nslots;
   if (nslots) {
-    if (ctx->d_wind) hipLaunchKernelGGL(k_batch_counters<true>, dim3(64), dim3(256), 0, st, ctx->d, bs, nslots);
-    else hipLaunchKernelGGL(k_batch_counters<false>, dim3(64), dim3(256), 0, st, ctx->d, bs, nslots);
+    LAUNCH_WIND_WATER(ctx->d_wind, k_batch_counters, dim3(64), dim3(256), st, ctx->d, bs, nslots);
     ctx->d_nslots = 0;                                       // (the slots' counters are committed once, whatever happens below)
   }
   HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  uint32_t nc = ctx->h_bctrl[BC_NCHILD];
-  if (ctx->h_bctrl[BC_CHILD_LOST]) ctx->batch_children_lost += ctx->h_bctrl[BC_CHILD_LOST];
-  if (ctx->h_bctrl[BC_FREED_LOST]) { ctx->err = "batched engine: freed-node list overflow (pool nodes leaked)"; return -6; }
-  if (ctx->h_bctrl[BC_LIST_LOST]) { ctx->err = "relaxed schedule: flood / cascade list overflow (work was dropped)"; return -6; }
-  if (ctx->h_bctrl[BC_STALLED]) { ctx->err = "throughput schedule: a device-side wait ran out of its spin budget (a dataflow dependency or a barrier was never released)"; return -9; }
-  if (nc > bs.child_cap) nc = bs.child_cap;
+  uint32_t nc = 0;
+  if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
   if (vec) { vec->resize(nc); children_out = vec->data(); cap = nc; }
   if (nc > cap) { ctx->err = "smx_d_gen_end: children buffer too small (call again with room for *n records)"; *n = nc; return -2; }
   if (nc) HIPCHK(hipMemcpyAsync(children_out, bs.children, (size_t)nc * sizeof(BChild), hipMemcpyDeviceToHost, st));
@@ -2749,10 +2661,7 @@ int smx_d_pack_particles(smx_ctx* ctx, int32_t x0, int32_t x1, void* host_buf, u
   const uint32_t nslots = ctx->d_nslots;
   const uint64_t rs = 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater));
   HIPCHK(hipMemsetAsync(ctx->d_xcur, 0, sizeof(XCursor), st));
-  if (nslots) {
-    if (ctx->d_wind) hipLaunchKernelGGL(k_strip_pack_particles<true>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, ctx->bs, nslots, x0, x1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xcur);
-    else hipLaunchKernelGGL(k_strip_pack_particles<false>, dim3((nslots + 255u) / 256u), dim3(256), 0, st, ctx->bs, nslots, x0, x1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xcur);
-  }
+  if (nslots) LAUNCH_WIND_WATER(ctx->d_wind, k_strip_pack_particles, dim3((nslots + 255u) / 256u), dim3(256), st, ctx->bs, nslots, x0, x1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xcur);
   XCursor c;
   HIPCHK(hipMemcpyAsync(&c, ctx->d_xcur, sizeof(c), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -2774,8 +2683,7 @@ int smx_d_unpack_particles(smx_ctx* ctx, const void* host_buf, uint64_t bytes) {
   const uint64_t rs = 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater));
   if (4 + n * rs > bytes || n * rs > ctx->xdata_cap) { ctx->err = "smx_d_unpack_particles: bad buffer"; return -2; }
   HIPCHK(hipMemcpyAsync(ctx->d_xdata, hb + 4, n * rs, hipMemcpyHostToDevice, st));
-  if (ctx->d_wind) hipLaunchKernelGGL(k_strip_unpack_particles<true>, dim3((n + 255u) / 256u), dim3(256), 0, st, ctx->bs, ctx->d_xdata, n);
-  else hipLaunchKernelGGL(k_strip_unpack_particles<false>, dim3((n + 255u) / 256u), dim3(256), 0, st, ctx->bs, ctx->d_xdata, n);
+  LAUNCH_WIND_WATER(ctx->d_wind, k_strip_unpack_particles, dim3((n + 255u) / 256u), dim3(256), st, ctx->bs, ctx->d_xdata, n);
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
@@ -2803,7 +2711,7 @@ extern "C" {
 int smx_tick_water(smx_ctx* ctx, int32_t nwater) {
   FULLMAP("smx_tick_water (a strip ticks with smx_strips_tick)")
   roctx_range rr("soilmx:water");
-  PhaseTimer t(ctx, 0);
+  PhaseTimer t(ctx, PH_WATER);
   if (is_batched(ctx)) {
     // throughput engines: the phase's particles as `water_generations` consecutive top-level generations of n/k (smx_set_water_generations;
     // default 1). Particles of one generation advance together and do not see the water the same generation adds; k > 1 trades
@@ -2820,14 +2728,13 @@ int smx_tick_water(smx_ctx* ctx, int32_t nwater) {
       return rc;
     }
     for (uint32_t q = 0; q < k && left > 0; q++) {
-      const uint32_t nq = left / (k - q);
-      left -= nq;
+      const uint32_t nq = batch_generation_share(left, k, q);
       if (nq) { const int rc = batch_generations(ctx, false, nq, 0u); if (rc) return rc; }
     }
     return 0;
   }
   if (ctx->cfg.engine == SMX_ENGINE_SPECULATIVE) return spec_phase(ctx, nwater, false);
-  PhaseTimer tk(ctx, 4);
+  PhaseTimer tk(ctx, PH_K_WATER);
   hipLaunchKernelGGL(k_water_serial, dim3(1), dim3(64), 0, ctx->stream, ctx->d, nwater);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2835,7 +2742,7 @@ int smx_tick_water(smx_ctx* ctx, int32_t nwater) {
 int smx_grid_pass(smx_ctx* ctx) {
   FULLMAP("smx_grid_pass (a strip ticks with smx_strips_tick)")
   roctx_range rr("soilmx:grid");
-  PhaseTimer t(ctx, 1);
+  PhaseTimer t(ctx, PH_GRID);
   if (is_batched(ctx)) return batch_grid(ctx);
   HIPCHK(hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, ctx->stream));
@@ -2847,27 +2754,27 @@ int smx_grid_pass(smx_ctx* ctx) {
 int smx_tick_wind(smx_ctx* ctx, int32_t nwind) {
   FULLMAP("smx_tick_wind (a strip ticks with smx_strips_tick)")
   roctx_range rr("soilmx:wind");
-  PhaseTimer t(ctx, 2);
+  PhaseTimer t(ctx, PH_WIND);
   if (is_batched(ctx)) return batch_generations(ctx, true, nwind > 0 ? (uint32_t)nwind : 0u, 0u);
   if (ctx->cfg.engine == SMX_ENGINE_SPECULATIVE) return spec_phase(ctx, nwind, true);
-  PhaseTimer tk(ctx, 5);
+  PhaseTimer tk(ctx, PH_K_WIND);
   hipLaunchKernelGGL(k_wind_serial, dim3(1), dim3(64), 0, ctx->stream, ctx->d, nwind);
   HIPCHK(hipGetLastError());
   return 0;
 }
 int smx_map_frequency(smx_ctx* ctx) {
   roctx_range rr("soilmx:frequency");
-  PhaseTimer t(ctx, 3);
+  PhaseTimer t(ctx, PH_FREQ);
   const size_t n = ctx->ncells, n4 = n / 4;
   unsigned nb = (unsigned)((n4 + 255) / 256);
   if (nb > 2048) nb = 2048;
   if (nb == 0) nb = 1;
-  { PhaseTimer tk(ctx, 8); hipLaunchKernelGGL(k_map_frequency, dim3(nb), dim3(256), 0, ctx->stream, ctx->d.wfreq, ctx->d.wtrack, n4, n); }
+  { PhaseTimer tk(ctx, PH_K_MAPFREQ); hipLaunchKernelGGL(k_map_frequency, dim3(nb), dim3(256), 0, ctx->stream, ctx->d.wfreq, ctx->d.wtrack, n4, n); }
   HIPCHK(hipGetLastError());
   return 0;
 }
 int smx_reset_frequency(smx_ctx* ctx) {
-  PhaseTimer t(ctx, 3);
+  PhaseTimer t(ctx, PH_FREQ);
   HIPCHK(hipMemsetAsync(ctx->d.wtrack, 0, ctx->ncells * 4, ctx->stream));
   return 0;
 }
@@ -3035,25 +2942,25 @@ int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwi
   const EnsEntry* tab = e->d_tab;
   if (dowater) {
     {
-      PhaseTimer t(e, 0);
-      PhaseTimer tk(e, 4);
+      PhaseTimer t(e, PH_WATER);
+      PhaseTimer tk(e, PH_K_WATER);
       hipLaunchKernelGGL(k_ens_water, dim3(nm), dim3(64), 0, st, tab);
     }
     {
-      PhaseTimer t(e, 1);
+      PhaseTimer t(e, PH_GRID);
       hipLaunchKernelGGL(k_ens_grid_clear, dim3(nm), dim3(256), 0, st, tab);
-      { PhaseTimer tk(e, 6); hipLaunchKernelGGL(k_ens_classify, dim3((unsigned)cls_blocks, nm), dim3(256), 0, st, tab); }
+      { PhaseTimer tk(e, PH_K_CLASSIFY); hipLaunchKernelGGL(k_ens_classify, dim3((unsigned)cls_blocks, nm), dim3(256), 0, st, tab); }
       hipLaunchKernelGGL(k_ens_grid, dim3(nm), dim3(64), 0, st, tab);
     }
   }
   if (dowind) {
-    PhaseTimer t(e, 2);
-    PhaseTimer tk(e, 5);
+    PhaseTimer t(e, PH_WIND);
+    PhaseTimer tk(e, PH_K_WIND);
     hipLaunchKernelGGL(k_ens_wind, dim3(nm), dim3(64), 0, st, tab);
   }
   if (dowater) {
-    PhaseTimer t(e, 3);
-    PhaseTimer tk(e, 8);
+    PhaseTimer t(e, PH_FREQ);
+    PhaseTimer tk(e, PH_K_MAPFREQ);
     hipLaunchKernelGGL(k_ens_frequency, dim3((unsigned)freq_blocks, nm), dim3(256), 0, st, tab);
   }
   EHIPCHK(hipGetLastError());
@@ -3270,10 +3177,7 @@ int smx_lbm_step(smx_lbm* l, int32_t n) {
   LBMCHK(hipSetDevice(l->device));
   if (n <= 0) return 0;
   LBMCHK(hipEventRecord(l->ev0, l->stream));
-  static const int variant = [] {                             // measured switches (profiles/r02_lbm_bench.log); results do not depend on them
-    const char* a = getenv("SMX_LBM_NT"); const char* b = getenv("SMX_LBM_XCD");
-    return ((a ? atoi(a) != 0 : false) ? 1 : 0) | ((b ? atoi(b) != 0 : false) ? 2 : 0);
-  }();
+  static const int variant = (env_flag("SMX_LBM_NT", false) ? 1 : 0) | (env_flag("SMX_LBM_XCD", false) ? 2 : 0);   // measured switches (profiles/r02_lbm_bench.log); results do not depend on them
   for (int s = 0; s < n; s++) {
     const dim3 g(lbm_grid(l)), t(256);
     float *fa = l->f[l->cur], *fb = l->f[l->cur ^ 1];

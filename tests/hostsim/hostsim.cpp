@@ -80,25 +80,10 @@ hs_ctx* hs_create(int dimx, int dimy, int scale, uint64_t cap) {
 }
 void hs_destroy(hs_ctx* c) { delete c; }
 void hs_set_soils(hs_ctx* c, const SoilP* s, int n) { c->soils.assign(s, s + n); rebind(c); }
-void hs_srand(hs_ctx* c, unsigned seed) {
-  RandState& r = c->rnd;
-  if (seed == 0) seed = 1;
-  int32_t word = (int32_t)seed;
-  r.ring[0] = (uint32_t)word;
-  for (int i = 1; i < 31; i++) {
-    long hi = word / 127773, lo = word % 127773;
-    word = (int32_t)(16807 * lo - 2836 * hi);
-    if (word < 0) word += 2147483647;
-    r.ring[i] = (uint32_t)word;
-  }
-  uint32_t idx = 34;
-  for (int i = 0; i < 310; i++) { uint32_t v = r.ring[idx % 31] + r.ring[(idx - 3) % 31]; r.ring[idx % 31] = v; idx++; }
-  r.idx = idx; r.calls = 0;
-}
+void hs_srand(hs_ctx* c, unsigned seed) { rand_seed(c->rnd, seed); }
 void hs_rand_advance(hs_ctx* c, uint64_t nd) {
-  RandState& r = c->rnd;
-  for (uint64_t i = 0; i < nd; i++) { uint32_t v = r.ring[r.idx % 31] + r.ring[(r.idx - 3) % 31]; r.ring[r.idx % 31] = v; r.idx++; }
-  r.calls += nd;
+  rand_skip(c->rnd, nd);
+  c->rnd.calls += nd;
 }
 int hs_import(hs_ctx* c, const uint32_t* count, const uint32_t* type, const double* size, const double* floor,
               const double* sat, const float* wfreq, const float* wtrack, const float* windfreq) {
@@ -137,31 +122,10 @@ void hs_export(hs_ctx* c, uint32_t* count, uint32_t* type, double* size, double*
 }
 void hs_counters(hs_ctx* c, unsigned long long* out, uint64_t* rand_calls) { memcpy(out, c->ctr, sizeof(c->ctr)); *rand_calls = c->rnd.calls; }
 
-// ---- the "kernels" (bodies mirror soilmx.hip; keep in sync) ----
-void hs_water(hs_ctx* c, int n) {
-  const DevState& s = c->d;
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, s.soils, pol);
-  Frame st[MAX_FRAMES]; int depth = 0;
-  for (int i = 0; i < n; i++) {
-    int ry, rx; pol.rand2(s, ry, rx);
-    Water p; sim.water_init(p, rx % s.dimx, ry % s.dimy);
-    sim.water_drive(p, true, true, st, depth);
-  }
-  sim.flush_counters(); pol.finish(s);
-}
-void hs_wind(hs_ctx* c, int n) {
-  const DevState& s = c->d;
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, s.soils, pol);
-  for (int i = 0; i < n; i++) {
-    int ry, rx; pol.rand2(s, ry, rx);
-    Wind p; sim.wind_init(p, rx % s.dimx, ry % s.dimy);
-    sim.wind_run(p);
-  }
-  sim.flush_counters(); pol.finish(s);
-}
-static void grid_classify(hs_ctx* c) {                      // k_grid_classify
+// ---- the "kernels": the walkers of soil_serial.h on a host thread, the soil table read in place ----
+void hs_water(hs_ctx* c, int n) { serial_water_walk(c->d, c->d.soils, n); }
+void hs_wind(hs_ctx* c, int n) { serial_wind_walk(c->d, c->d.soils, n); }
+static void grid_classify(hs_ctx* c) {                      // k_grid_classify (the two summary levels: read by serial_grid_walk only)
   const DevState& s = c->d;
   const size_t n = c->n;
   std::fill(c->a0.begin(), c->a0.end(), 0); std::fill(c->a1.begin(), c->a1.end(), 0); std::fill(c->a2.begin(), c->a2.end(), 0);
@@ -176,28 +140,8 @@ static void grid_classify(hs_ctx* c) {                      // k_grid_classify
   }
 }
 void hs_grid(hs_ctx* c) {
-  const DevState& s = c->d;
-  const size_t n = c->n;
   grid_classify(c);
-  SerialPolicy pol(s);
-  Sim<SerialPolicy> sim(s, s.soils, pol);
-  sim.grid_mode = true;
-  Frame st[MAX_FRAMES]; int depth = 0;
-  size_t cc = sim.next_active(0);
-  unsigned long long visited = 0;
-  Water dummy; memset(&dummy, 0, sizeof(dummy));
-  while (cc < n) {
-    const int x = (int)(cc / s.dimy), y = (int)(cc % s.dimy);
-    sim.seep(x, y);
-    sim.push_frame(st, depth, x, y, 3);
-    sim.water_drive(dummy, false, false, st, depth);
-    visited++;
-    cc = sim.next_active(cc + 1);
-  }
-  sim.n_wcasc += n - visited;
-  sim.flush_counters();
-  pol.add_counter(s, C_GRID_ACTIVE, visited);
-  pol.finish(s);
+  serial_grid_walk(c->d, c->d.soils);
 }
 void hs_freq(hs_ctx* c) {
   const float lrate = 0.01f, K = 50.0f;
@@ -304,7 +248,7 @@ static int g_boundary_threads = 1;
 extern "C" void hs_set_boundary_threads(int n) { g_boundary_threads = n < 1 ? 1 : n; }
 static uint32_t g_spec_sub = 4096;                          // top-level particles per sub-phase (soilmx.hip spec_phase: SPEC_SUB)
 extern "C" void hs_set_spec_sub(int n) { g_spec_sub = n < 1 ? 1u : (uint32_t)n; }
-// one sub-phase (mirrors soilmx.hip spec_subphase): returns 0 = all n committed, 1 = cut (nested slots used up), 2 = give the rest to the serial walker
+// one sub-phase (mirrors soilmx.hip spec_subphase on purpose -- host orchestration of launches, not a kernel body): returns 0 = all n committed, 1 = cut (nested slots used up), 2 = give the rest to the serial walker
 template <bool WIND>
 static int spec_subphase(hs_ctx* c, uint32_t n, int nthreads, int scout, unsigned shuffle, uint32_t* stats, uint32_t* committed) {
   const DevState& s = c->d;
@@ -378,7 +322,7 @@ static int spec_subphase(hs_ctx* c, uint32_t n, int nthreads, int scout, unsigne
   *committed = n;
   return 0;
 }
-// a particle phase in sub-phases of at most g_spec_sub top-level particles (mirrors soilmx.hip spec_phase); returns 1 if any part of the
+// a particle phase in sub-phases of at most g_spec_sub top-level particles (mirrors soilmx.hip spec_phase, likewise on purpose); returns 1 if any part of the
 // phase went to the serial walker. stats[3] = (sub-phases cut << 16) | phases handed to the serial walker | single serial particles << 8
 template <bool WIND>
 static int spec_phase(hs_ctx* c, uint32_t n, int nthreads, int scout, unsigned shuffle, uint32_t* stats) {
@@ -410,7 +354,8 @@ void hs_spec_tick(hs_ctx* c, int nwater, int nwind, int dowater, int dowind, int
 }
 }  // extern "C"
 
-// ---------------- batched engine (soil_batch.h), emulated: the host driver below mirrors soilmx.hip batch_* ----------
+// ---------------- batched engine (soil_batch.h), emulated: the host driver below runs what soilmx.hip batch_* launches as loops over host threads;
+// what decides results between the launches -- schedule, plan of a chunk, the lists' reset, the generations' shares -- is the headers' own code ----------
 static int g_batch_dilate = 0;
 static uint32_t g_batch_cell_above = 0xFFFFFFFFu;
 static int g_strips_n = 1, g_strips_a = 16, g_strips_b = 48;
@@ -468,9 +413,8 @@ static void batch_setup(hs_ctx* c, BatchBuffers& b, uint32_t nslots, bool wind) 
 static void batch_draw(hs_ctx* c, BatchBuffers& b, uint32_t nslots) {   // the next 2*nslots rand() values (host-side generator)
   RandState& r = c->rnd;
   for (uint32_t i = 0; i < 2 * nslots; i++) {
-    const uint32_t v = r.ring[r.idx % 31] + r.ring[(r.idx - 3) % 31];
-    r.ring[r.idx % 31] = v; r.idx++; r.calls++;
-    b.draws[i] = v >> 1;
+    b.draws[i] = rand_step(r) >> 1;
+    r.calls++;
   }
 }
 static void batch_merge_freed(hs_ctx* c, BatchBuffers& b) {
@@ -505,13 +449,8 @@ static void batch_generations(hs_ctx* c, BatchBuffers& b, bool wind, uint32_t n,
       if (const char* e = getenv("HS_SCHED")) { int a, d, k; if (sscanf(e, "%d,%d,%d", &a, &d, &k) == 3) { sc.tshift = a; sc.dilate = d; sc.maxsteps = k; } }   // exploration only
       if (const char* e = wind ? nullptr : getenv("HS_SCHED_WATER")) { int a, d, k; if (sscanf(e, "%d,%d,%d", &a, &d, &k) == 3) { sc.tshift = a; sc.dilate = d; sc.maxsteps = k; } }   // ... water (floods) only
       const bool strips = b.bs.strips.n > 1;
-      const bool relaxed_now = relax_gen && (!wind || nlive > g_relax_wind_min);
-      bool regrain = sc.tshift != b.bs.tshift;               // first chunk, or the claim granularity changes
-      if (relax_gen && !relaxed_now && b.bs.relaxed) { b.bs.relaxed = 0; regrain = true; }   // survivors go on under the exclusive schedule
-      batch_apply_schedule(b.bs, s, sc);
-      b.bs.sphase = strips ? (int)(chunk & 1u) : STRIP_INTERIOR;   // column strips: INTERIOR and SEAM chunks alternate
-      if (strips && chunk > 0) epoch++;                      // (reservations of the previous chunk must not look current)
-      chunk++;
+      const BChunkPlan plan = batch_plan_chunk(b.bs, s, sc, wind, nlive, relax_gen, g_relax_wind_min, g_relax_wind_steps, g_relax_water_steps, first, epoch, chunk);
+      const bool regrain = plan.regrain;
       if (regrain || strips) {                               // under strips every chunk starts with fresh reservations: eligibility changed
         if (regrain) { std::fill(b.claim0.begin(), b.claim0.end(), 0ull); std::fill(b.claim1.begin(), b.claim1.end(), 0ull); }
         parallel_for(nlive, nthreads, [&](uint32_t i) {
@@ -521,10 +460,8 @@ static void batch_generations(hs_ctx* c, BatchBuffers& b, bool wind, uint32_t n,
       }
       static FILE* estats = getenv("HS_EPOCH_STATS") ? fopen(getenv("HS_EPOCH_STATS"), "w") : nullptr;   // analysis only
       std::vector<uint32_t> pc, ps; std::vector<uint32_t> pst;
-      int chunk_epochs = B_CHUNK;
-      if (relaxed_now) {                                     // mirrors soilmx.hip: step, apply, nine cascade colours, floods
-        chunk_epochs = strips ? B_CHUNK : (first ? B_CHUNK : 8);   // (with strips the chunk is the unit of the exchange: soilmx.hip run_chunk)
-        b.bs.rstride = wind ? 2 * g_relax_wind_steps : (g_relax_water_steps > 2 ? g_relax_water_steps : 2); b.bs.rsteps = wind ? g_relax_wind_steps : g_relax_water_steps;
+      const int chunk_epochs = plan.chunk_epochs;
+      if (plan.relaxed_now) {                                // the launches of soilmx.hip run_chunk as loops: step, apply, nine cascade colours, floods
         if (strips) for (uint32_t q = BC_NFLOOD; q < (uint32_t)BC_LISTS_END; q++) b.ctrl[q] = 0u;   // (the epoch skipped between two chunks breaks the lists' parity hand-over)
         if (strips && !wind) {                                // k_relax_rebuild_floods
           for (uint32_t i = 0; i < nslots; i++) relax_flood_later(bs, i, epoch & 1u, b.water[i].state == B_ENDED);
@@ -535,7 +472,7 @@ static void batch_generations(hs_ctx* c, BatchBuffers& b, bool wind, uint32_t n,
             BatchPolicy pol(s, bs); Sim<BatchPolicy> sim(s, s.soils, pol);
             if (wind) relax_wind_step(sim, bs, bs.live[i], epoch); else relax_water_step(sim, bs, bs.live[i], epoch);
           }, shuffle ? shuffle + 11 + epoch : 0);
-          { const uint32_t par = (epoch + 1u) & 1u; b.ctrl[BC_NFLOOD + par] = 0u; b.ctrl[BC_NFLAG + par] = 0u; b.ctrl[BC_NRUN + par] = 0u; for (uint32_t q = 0; q < 9u; q++) b.ctrl[BC_NCASC + 9u * par + q] = 0u; }
+          relax_reset_lists(bs, (epoch + 1u) & 1u);
           parallel_for(nlive, nthreads, [&](uint32_t i) {                                       // k_relax_apply
             BatchPolicy pol(s, bs); Sim<BatchPolicy> sim(s, s.soils, pol);
             relax_apply_slot(sim, bs, bs.live[i]);
@@ -687,16 +624,7 @@ static unsigned long long grid_sweep(hs_ctx* c, BatchBuffers& b, int phase, int 
 void hs_batched_grid(hs_ctx* c, int nthreads, unsigned shuffle) {
   const DevState& s = c->d;
   const size_t n = c->n;
-  std::fill(c->a0.begin(), c->a0.end(), 0); std::fill(c->a1.begin(), c->a1.end(), 0); std::fill(c->a2.begin(), c->a2.end(), 0);
-  for (size_t cc = 0; cc < n; cc++) {                       // k_grid_classify
-    const int x = (int)(cc / s.dimy), y = (int)(cc % s.dimy);
-    bool act = (s.flags[cc] & F_SAT) != 0;
-    for (int dx = -1; dx <= 1 && !act; dx++) for (int dy = -1; dy <= 1; dy++) {
-      int nx = x + dx, ny = y + dy; if (nx < 0 || ny < 0 || nx >= s.dimx || ny >= s.dimy) continue;
-      if (s.flags[(size_t)nx * s.dimy + ny] & F_AIR) { act = true; break; }
-    }
-    if (act) c->a0[cc >> 6] |= 1ull << (cc & 63);
-  }
+  grid_classify(c);
   BatchBuffers b; batch_setup(c, b, 0, false);
   const int gtx = (s.dimx + (1 << GRID_SHIFT) - 1) >> GRID_SHIFT;
   unsigned long long visited = 0;
@@ -714,7 +642,7 @@ void hs_batched_tick(hs_ctx* c, int nwater, int nwind, int dowater, int dowind, 
   if (dowater) {                                              // smx_tick_water: k consecutive top-level generations of n/k -- or ONE staggered phase (smx_set_water_stagger)
     uint32_t left = nwater > 0 ? (uint32_t)nwater : 0u;
     if (g_relaxed && g_stagger_gap > 0u && stagger_k() > 1u && left > 0u) { hs_batched_water(c, (int)left, nthreads, shuffle); left = 0u; }
-    for (uint32_t q = 0, k = (uint32_t)g_water_generations; q < k && left > 0; q++) { const uint32_t nq = left / (k - q); left -= nq; if (nq) hs_batched_water(c, (int)nq, nthreads, shuffle); }
+    for (uint32_t q = 0, k = (uint32_t)g_water_generations; q < k && left > 0; q++) { const uint32_t nq = batch_generation_share(left, k, q); if (nq) hs_batched_water(c, (int)nq, nthreads, shuffle); }
     hs_batched_grid(c, nthreads, shuffle);
   }
   if (dowind) hs_batched_wind(c, nwind, nthreads, shuffle);
@@ -761,11 +689,8 @@ void hs_d_chunk(hs_ctx* c, uint32_t nlive_global, uint32_t* nlive_local) {
   uint32_t nlive = 0;                                        // residents that run: rebuild the list (particles may have arrived / left)
   for (uint32_t i = 0; i < d.nslots; i++) { const uint32_t st = d.wind ? b.wind[i].state : b.water[i].state; if (st != B_DONE && st != B_AWAY) b.live[nlive++] = i; }
   const BSched sc = batch_schedule(d.wind, nlive_global, g_batch_dilate, g_batch_cell_above);
-  const bool strips = b.bs.strips.n > 1, regrain = sc.tshift != b.bs.tshift;
-  batch_apply_schedule(b.bs, s, sc);
-  b.bs.sphase = strips ? (int)(d.chunk & 1u) : STRIP_INTERIOR;
-  if (strips && d.chunk > 0) d.epoch++;
-  d.chunk++;
+  const bool strips = b.bs.strips.n > 1;
+  const bool regrain = batch_plan_chunk(b.bs, s, sc, d.wind, nlive_global, false, 0u, 0, 0, d.first, d.epoch, d.chunk).regrain;   // (relax_gen false: the exclusive schedule only)
   if (regrain) { std::fill(b.claim0.begin(), b.claim0.end(), 0ull); std::fill(b.claim1.begin(), b.claim1.end(), 0ull); }
   if (regrain || strips)
     for (uint32_t i = 0; i < nlive; i++) {
@@ -878,17 +803,7 @@ void hs_d_unpack_particles(hs_ctx* c, const uint8_t* buf, uint64_t bytes) {
 }
 // grid pass, strip by strip: classification, then one sweep (9 colours) over the 8x8 tiles of the columns [x_lo, x_hi) that belong to `phase`
 void hs_d_grid_begin(hs_ctx* c) {
-  const DevState& s = c->d; const size_t n = c->n;
-  std::fill(c->a0.begin(), c->a0.end(), 0);
-  for (size_t cc = 0; cc < n; cc++) {
-    const int x = (int)(cc / s.dimy), y = (int)(cc % s.dimy);
-    bool act = (s.flags[cc] & F_SAT) != 0;
-    for (int dx = -1; dx <= 1 && !act; dx++) for (int dy = -1; dy <= 1; dy++) {
-      int nx = x + dx, ny = y + dy; if (nx < 0 || ny < 0 || nx >= s.dimx || ny >= s.dimy) continue;
-      if (s.flags[(size_t)nx * s.dimy + ny] & F_AIR) { act = true; break; }
-    }
-    if (act) c->a0[cc >> 6] |= 1ull << (cc & 63);
-  }
+  grid_classify(c);
   DPhase& d = dp_of(c);
   d.wind = false; d.nslots = 0; d.first = true;
   batch_setup(c, d.b, 0, false);
