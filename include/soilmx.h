@@ -202,6 +202,41 @@ int smx_ensemble_sync(smx_ensemble* e);                                         
  * _mapfreq fields), written as smx_get_timing_sized does */
 int smx_ensemble_get_timing(smx_ensemble* e, smx_timing* out, uint64_t struct_size);
 int smx_ensemble_timing_reset(smx_ensemble* e);
+/* ---- an ensemble observed as one thing: per-member figures and cross-member statistics of a plane ----
+ * Both calls run on the ensemble's stream (they see every tick queued before them), launch a fixed number of kernels whatever the
+ * member count (one table upload, k_ens_figures or k_ens_plane_stats, one copy of the RESULTS back), synchronise once before they
+ * return and change no member state. Layermap::height(ivec2) = floor + size of the top section, 0 for an empty column
+ * (layermap.h:422-425); Layermap::surface(ivec2) = the top section's type, 0 (Air) for an empty column (layermap.h:417-420) -- a wet
+ * cell is a NON-EMPTY column whose top section is Air.
+ * Every field is bit-identical to what the per-member path gives on the same state: sumh / nsec / typehash to the digest of the
+ * "observability" block below, rand_calls and live_sections to their getters, the water fields to the same folds over exported columns. */
+typedef struct smx_member_figures {      /* 80 bytes; a caller passes sizeof(ITS struct) and gets that prefix */
+  double   sumh;          /* sum of Layermap::height over the cells in index order x*dimy+y, sequential f64 accumulation  */
+  uint64_t nsec;          /* number of sections                                                                          */
+  uint64_t typehash;      /* h = (h ^ type) * 1099511628211 from 1469598103934665603: cells in index order, top -> bottom */
+  uint64_t wet_cells;     /* cells whose top section is water (type Air = 0)                                             */
+  double   water_volume;  /* sum of the sizes of those top sections, cells in index order, sequential f64 accumulation   */
+  double   hmin, hmax;    /* extremes of Layermap::height (an empty column counts as 0)                                  */
+  uint64_t empty_cells;
+  uint64_t rand_calls;    /* rand() draws since the member's last srand (`calls` of the generator state)                 */
+  uint64_t live_sections; /* the context's own section counter; equals nsec on a sound map                               */
+} smx_member_figures;
+/* one entry per member in member order, entry i at byte i * struct_size. An empty ensemble: 0, nothing written. A section chain that
+ * leaves the pool or has more links than the member's pool holds: -5, the error text names the member, nothing written. */
+int smx_ensemble_figures(smx_ensemble* e, smx_member_figures* out, uint64_t struct_size);
+/* Per cell c, over the n members which[0..n) IN THAT ORDER (which == NULL: all members in member order, n ignored), with v_i =
+ *   SMX_PLANE_HEIGHT    floor + size of member i's top section in c (0 for an empty column: Layermap::height)
+ *   SMX_PLANE_WATER     that section's size if its type is Air, else 0
+ *   SMX_PLANE_WFREQ / _WINDFREQ   the f32 value of the water / wind frequency plane, widened to f64:
+ *   mean = (((v_0 + v_1) + ...) + v_{n-1}) / n and var = (((v_0 - mean)^2 + (v_1 - mean)^2) + ...) / n (population variance, a second
+ *   pass, run only where var != NULL) in f64 without contraction, so that a host loop `acc += v[i]` over the members gives the same
+ *   bits; vmin / vmax; nonzero = members with v_i != 0 (on WATER: in how many runs the cell holds water). A NULL output is skipped.
+ * Outputs hold dimx*dimy values in the plane's own indexing: x*dimy+y for HEIGHT / WATER (as the heights reader), y*dimx+x for the
+ * frequency planes (as the frequency reader). The selected members must have equal dimx and dimy; unequal dims, an index out of
+ * range, a repeated index or n == 0 return -2 and the error text names the offender. */
+enum { SMX_PLANE_HEIGHT = 0, SMX_PLANE_WATER = 1, SMX_PLANE_WFREQ = 2, SMX_PLANE_WINDFREQ = 3 };
+int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* which, int32_t n,
+                             double* mean, double* var, double* vmin, double* vmax, uint32_t* nonzero);
 
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */

@@ -68,6 +68,22 @@ class Timing(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MemberFigures(C.Structure):
+    """smx_member_figures: one member's entry of smx_ensemble_figures (80 bytes)."""
+    _fields_ = [("sumh", C.c_double), ("nsec", C.c_uint64), ("typehash", C.c_uint64), ("wet_cells", C.c_uint64),
+                ("water_volume", C.c_double), ("hmin", C.c_double), ("hmax", C.c_double), ("empty_cells", C.c_uint64),
+                ("rand_calls", C.c_uint64), ("live_sections", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["typehash"] = f"{int(self.typehash):016x}"          # as Snapshot.digest() and tests/golden/digests.json spell it
+        return d
+
+
+PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
+PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
+
+
 # every symbol include/soilmx.h declares (tests/test_capi_symbols.py checks the library exports them all)
 SYMBOLS = [
     "smx_create", "smx_create_strip", "smx_destroy", "smx_last_error", "smx_set_soils", "smx_set_scale", "smx_srand", "smx_rand", "smx_rand_advance", "smx_get_rand_state", "smx_set_rand_state",
@@ -82,6 +98,7 @@ SYMBOLS = [
     "smx_lbm_step", "smx_lbm_read", "smx_lbm_write_f", "smx_lbm_move", "smx_lbm_get_timing",
     "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
+    "smx_ensemble_figures", "smx_ensemble_plane_stats",
 ]
 
 ENSEMBLE_MAX_MEMBERS = 4096    # SMX_ENSEMBLE_MAX_MEMBERS
@@ -197,6 +214,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_sync.argtypes = [vp]
     L.smx_ensemble_get_timing.argtypes = [vp, C.POINTER(Timing), u64]
     L.smx_ensemble_timing_reset.argtypes = [vp]
+    L.smx_ensemble_figures.argtypes = [vp, vp, u64]
+    L.smx_ensemble_plane_stats.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("smx_destroy", "smx_last_error", "smx_stream", "smx_lbm_destroy", "smx_lbm_last_error",

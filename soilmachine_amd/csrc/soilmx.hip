@@ -10,6 +10,8 @@
 //   k_map_frequency / k_reset_frequency   water.h:353-365, float4-vectorised streaming kernels
 //   k_ens_*                          ensembles (smx_ensemble_*): the walkers above, one wavefront per member of a device
 //                                    table, and the streaming kernels of the serial tick with the member in blockIdx.y
+//   k_ens_figures / k_ens_plane_stats   an ensemble observed in one call (soil_observe.h): one workgroup per member folds its
+//                                    digest and water figures; one thread per cell folds a plane over the selected members
 //   k_init_terrain                   Layermap::initialize (layermap.h:163-216): FBm OpenSimplex2 per cell + column build
 //   k_heights / k_surface / k_normals / k_bilinear   whole-map read-side primitives (layermap.h:341-439)
 //   k_fill_vertices                  Layermap::update(Vertexpool&) (layermap.h:475-555): the 44-byte vertex stream
@@ -39,6 +41,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_batch.h"
 #include "soil_relax.h"
 #include "soil_lbm.h"
+#include "soil_observe.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
 
@@ -233,6 +236,41 @@ __global__ void __launch_bounds__(256) k_ens_classify(const EnsEntry* __restrict
     if ((size_t)blockIdx.x * 256 >= n) return;
     grid_classify_block(s, blockIdx.x);
   }
+}
+
+// ---------------- an ensemble observed as one thing (smx_ensemble_figures / smx_ensemble_plane_stats; bodies: soil_observe.h) ----------------
+struct ObsGroup {   // a workgroup as soil_observe.h sees it: this thread is one lane
+  SMX_D uint32_t lanes() const { return blockDim.x; }
+  SMX_D uint32_t lo() const { return threadIdx.x; }
+  SMX_D uint32_t hi() const { return threadIdx.x + 1u; }
+  SMX_D void barrier() const { __syncthreads(); }
+};
+// 256 cells per tile and 8 staged buried types per cell: two tiles + the partials are 41 KB of LDS, three workgroups per CU
+constexpr int FIG_TILE = 256, FIG_K = 8, FIG_LANES = 256;
+// one workgroup per member (blockIdx.x): wavefront 0 folds the type hash, wavefront 1 the two f64 sums, wavefronts 2-3 stage the next tile
+__global__ void __launch_bounds__(FIG_LANES) k_ens_figures(const EnsEntry* __restrict__ tab_, ObsFigures* __restrict__ out) {
+  EnsTab* tab = ens_tab(tab_);
+  __shared__ FigShared<FIG_TILE, FIG_K, FIG_LANES> sh;
+  const DevState s = tab[blockIdx.x].s;
+  ObsGroup g;
+  figures_group<FIG_TILE, FIG_K, FIG_LANES>(s, g, sh, out + blockIdx.x);
+}
+// the table holds the SELECTED members in fold order (smx_ensemble_plane_stats uploads it so): entry i is member which[i]
+struct ObsMembers {
+  EnsTab* tab;
+  SMX_D const Sec* cells(uint32_t i) const { return tab[i].s.cells; }
+  SMX_D const float* wfreq(uint32_t i) const { return tab[i].s.wfreq; }
+  SMX_D const float* windfreq(uint32_t i) const { return tab[i].s.windfreq; }
+};
+// one thread per cell of the plane (its own index), a loop over the selected members: adjacent lanes read adjacent records of one member
+template <int PLANE>
+__global__ void __launch_bounds__(256) k_ens_plane_stats(const EnsEntry* __restrict__ tab_, uint32_t n, size_t cells, double* __restrict__ mean,
+                                                         double* __restrict__ var, double* __restrict__ vmin, double* __restrict__ vmax,
+                                                         uint32_t* __restrict__ nonzero) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= cells) return;
+  const ObsMembers m{ens_tab(tab_)};
+  plane_stats_cell<PLANE>(m, n, c, mean, var, vmin, vmax, nonzero);
 }
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
@@ -2808,6 +2846,9 @@ struct smx_ensemble : EventTimer {
   hipEvent_t h_free[ENS_RING] = {};       // recorded after the upload out of ring slot k
   bool h_used[ENS_RING] = {};
   int slot = 0;
+  // smx_ensemble_figures / smx_ensemble_plane_stats: results on the device and their pinned landing place (grown on demand, kept)
+  void* d_obs = nullptr; size_t d_obs_cap = 0;
+  void* h_obs = nullptr; size_t h_obs_cap = 0;
 };
 
 #define EHIPCHK(call)                                                                                 \
@@ -2866,6 +2907,8 @@ void smx_ensemble_destroy(smx_ensemble* e) {
   for (hipEvent_t ev : e->evpool) hipEventDestroy(ev);
   for (int k = 0; k < ENS_RING; k++) if (e->h_free[k]) hipEventDestroy(e->h_free[k]);
   ens_free_tables(e);
+  hipFree(e->d_obs);
+  if (e->h_obs) hipHostFree(e->h_obs);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2984,6 +3027,126 @@ int smx_ensemble_timing_reset(smx_ensemble* e) {
   EHIPCHK(hipStreamSynchronize(e->stream));
   drain_events(e);
   memset(&e->timing, 0, sizeof(e->timing));
+  return 0;
+}
+
+// ---------------- an ensemble observed in one call ----------------
+// Both calls: one table upload (the ring protocol of smx_ensemble_tick), the kernels, one copy back, one synchronisation -- whatever
+// the member count. They read the members' states on the ensemble's stream, behind every tick queued before them.
+static_assert(sizeof(smx_member_figures) == 80 && offsetof(ObsFigures, corrupt) == sizeof(smx_member_figures), "smx_member_figures layout");
+static_assert(SMX_PLANE_HEIGHT == OBS_PLANE_HEIGHT && SMX_PLANE_WATER == OBS_PLANE_WATER && SMX_PLANE_WFREQ == OBS_PLANE_WFREQ &&
+              SMX_PLANE_WINDFREQ == OBS_PLANE_WINDFREQ, "SMX_PLANE_*");
+
+// the members sel[0..n) as entries 0..n-1 of the device table
+static int ens_upload_selection(smx_ensemble* e, const uint32_t* sel, uint32_t n) {
+  const int k = e->slot;
+  e->slot = (e->slot + 1) % ENS_RING;
+  if (e->h_used[k]) EHIPCHK(hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
+  EnsEntry* h = e->h_tab + (size_t)k * e->cap;
+  for (uint32_t i = 0; i < n; i++) {
+    EnsEntry& t = h[i];
+    t.s = e->members[sel ? sel[i] : i]->d;
+    t.nwater = 0; t.nwind = 0; t.on = 0; t.classify8 = 0;
+  }
+  EHIPCHK(hipMemcpyAsync(e->d_tab, h, (size_t)n * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
+  EHIPCHK(hipEventRecord(e->h_free[k], e->stream));
+  e->h_used[k] = true;
+  return 0;
+}
+static int ens_obs_reserve(smx_ensemble* e, size_t bytes) {
+  if (bytes <= e->d_obs_cap && bytes <= e->h_obs_cap) return 0;
+  size_t cap = e->d_obs_cap ? e->d_obs_cap : 4096;
+  while (cap < bytes) cap *= 2;
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  void* d = nullptr; void* h = nullptr;
+  if (hipMalloc(&d, cap) != hipSuccess || hipHostMalloc(&h, cap, hipHostMallocDefault) != hipSuccess) {
+    hipFree(d);
+    (void)hipGetLastError();
+    e->err = "out of memory for the observation scratch (" + std::to_string(cap) + " bytes)";
+    return -1;
+  }
+  hipFree(e->d_obs);
+  if (e->h_obs) hipHostFree(e->h_obs);
+  e->d_obs = d; e->h_obs = h; e->d_obs_cap = cap; e->h_obs_cap = cap;
+  return 0;
+}
+
+int smx_ensemble_figures(smx_ensemble* e, smx_member_figures* out, uint64_t struct_size) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_figures: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!out) { e->err = "smx_ensemble_figures: out is null (one entry per member)"; return -2; }
+  roctx_range rr("soilmx:ensemble_figures");
+  if (int rc = ens_obs_reserve(e, (size_t)nm * sizeof(ObsFigures))) { e->err = "smx_ensemble_figures: " + e->err; return rc; }
+  if (int rc = ens_upload_selection(e, nullptr, nm)) return rc;
+  hipLaunchKernelGGL(k_ens_figures, dim3(nm), dim3(FIG_LANES), 0, e->stream, e->d_tab, (ObsFigures*)e->d_obs);
+  EHIPCHK(hipGetLastError());
+  EHIPCHK(hipMemcpyAsync(e->h_obs, e->d_obs, (size_t)nm * sizeof(ObsFigures), hipMemcpyDeviceToHost, e->stream));
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  const ObsFigures* r = (const ObsFigures*)e->h_obs;
+  for (uint32_t i = 0; i < nm; i++)
+    if (r[i].corrupt) { e->err = "smx_ensemble_figures: corrupt section chain in member " + std::to_string(i); return -5; }
+  const size_t take = struct_size < sizeof(smx_member_figures) ? (size_t)struct_size : sizeof(smx_member_figures);
+  for (uint32_t i = 0; i < nm; i++) memcpy(reinterpret_cast<char*>(out) + (size_t)i * struct_size, &r[i], take);
+  return 0;
+}
+
+int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* which, int32_t n, double* mean, double* var, double* vmin,
+                             double* vmax, uint32_t* nonzero) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_plane_stats: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (plane < SMX_PLANE_HEIGHT || plane > SMX_PLANE_WINDFREQ) { e->err = "smx_ensemble_plane_stats: unknown plane " + std::to_string(plane); return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (!which) n = (int32_t)nm;
+  if (n <= 0) { e->err = which ? "smx_ensemble_plane_stats: n = " + std::to_string(n) + ": no member selected" : std::string("smx_ensemble_plane_stats: the ensemble has no members"); return -2; }
+  if ((uint32_t)n > nm) { e->err = "smx_ensemble_plane_stats: n = " + std::to_string(n) + " members selected, the ensemble has " + std::to_string(nm) + " (no member may be selected twice)"; return -2; }
+  std::vector<uint32_t> sel((size_t)n);
+  std::vector<char> seen(nm, 0);
+  for (int32_t i = 0; i < n; i++) {
+    const int64_t w = which ? (int64_t)which[i] : (int64_t)i;
+    if (w < 0 || w >= (int64_t)nm) { e->err = "smx_ensemble_plane_stats: which[" + std::to_string(i) + "] = " + std::to_string(w) + " is not a member index (the ensemble has " + std::to_string(nm) + ")"; return -2; }
+    if (seen[(size_t)w]) { e->err = "smx_ensemble_plane_stats: member " + std::to_string(w) + " is selected twice (which[" + std::to_string(i) + "])"; return -2; }
+    seen[(size_t)w] = 1;
+    sel[(size_t)i] = (uint32_t)w;
+  }
+  const smx_config& c0 = e->members[sel[0]]->cfg;
+  for (int32_t i = 1; i < n; i++) {
+    const smx_config& c = e->members[sel[(size_t)i]]->cfg;
+    if (c.dimx != c0.dimx || c.dimy != c0.dimy) {
+      e->err = "smx_ensemble_plane_stats: member " + std::to_string(sel[(size_t)i]) + " is " + std::to_string(c.dimx) + "x" + std::to_string(c.dimy) + ", member " +
+               std::to_string(sel[0]) + " is " + std::to_string(c0.dimx) + "x" + std::to_string(c0.dimy) + ": the selected members must have equal dims";
+      return -2;
+    }
+  }
+  const size_t cells = (size_t)c0.dimx * c0.dimy;
+  // the wanted outputs, one after the other in the scratch (f64 planes first: all offsets stay 8-byte aligned)
+  double** const want[4] = {&mean, &var, &vmin, &vmax};
+  size_t off[5], bytes = 0;
+  for (int k = 0; k < 4; k++) { off[k] = bytes; if (*want[k]) bytes += cells * sizeof(double); }
+  off[4] = bytes;
+  if (nonzero) bytes += cells * sizeof(uint32_t);
+  if (bytes == 0) return 0;
+  roctx_range rr("soilmx:ensemble_plane_stats");
+  if (int rc = ens_obs_reserve(e, bytes)) { e->err = "smx_ensemble_plane_stats: " + e->err; return rc; }
+  if (int rc = ens_upload_selection(e, sel.data(), (uint32_t)n)) return rc;
+  char* d = (char*)e->d_obs;
+  double* dp[4];
+  for (int k = 0; k < 4; k++) dp[k] = *want[k] ? reinterpret_cast<double*>(d + off[k]) : nullptr;
+  uint32_t* dnz = nonzero ? reinterpret_cast<uint32_t*>(d + off[4]) : nullptr;
+  const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
+  switch (plane) {
+    case SMX_PLANE_HEIGHT: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_HEIGHT>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
+    case SMX_PLANE_WATER: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_WATER>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
+    case SMX_PLANE_WFREQ: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_WFREQ>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
+    default: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_WINDFREQ>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
+  }
+  EHIPCHK(hipGetLastError());
+  EHIPCHK(hipMemcpyAsync(e->h_obs, e->d_obs, bytes, hipMemcpyDeviceToHost, e->stream));
+  EHIPCHK(hipStreamSynchronize(e->stream));
+  const char* h = (const char*)e->h_obs;
+  for (int k = 0; k < 4; k++) if (*want[k]) memcpy(*want[k], h + off[k], cells * sizeof(double));
+  if (nonzero) memcpy(nonzero, h + off[4], cells * sizeof(uint32_t));
   return 0;
 }
 

@@ -145,6 +145,59 @@ class Ensemble:
     def sync(self):
         self._chk(self.L.smx_ensemble_sync(self.h))
 
+    # -- the ensemble observed as one thing --
+    def _check_members(self):
+        if self.size() != len(self.members):
+            raise SoilmxError(f"ensemble: the library holds {self.size()} members, this object lists {len(self.members)}")
+
+    def figures(self) -> list:
+        """One dict per member, in member order (``smx_ensemble_figures``: one launch for all members): the digest ``sumh`` /
+        ``nsec`` / ``typehash`` (formatted as ``Snapshot.digest()``), ``wet_cells``, ``water_volume``, ``hmin``, ``hmax``,
+        ``empty_cells``, ``rand_calls``, ``live_sections`` -- each bit-identical to the per-member readers on the same state. Sees
+        every tick queued before it; no sync needed."""
+        self._check_members()
+        n = len(self.members)
+        out = (capi.MemberFigures * n)()
+        self._chk(self.L.smx_ensemble_figures(self.h, out, C.sizeof(capi.MemberFigures)))
+        return [f.as_dict() for f in out]
+
+    def plane_stats(self, plane: str = "height", members=None, *, var: bool = True, minmax: bool = True, nonzero: bool = True) -> dict:
+        """Per-cell statistics of one plane ACROSS members (``smx_ensemble_plane_stats``): ``plane`` is "height", "water" (the top
+        section's size where it is water, else 0), "wfreq" or "windfreq"; ``members`` a list of members or indices, folded in that
+        order (None: all). Returns ``mean`` and, as asked, ``var`` (population variance), ``vmin`` / ``vmax``, ``nonzero`` (members
+        with a value != 0) as flat arrays of dimx*dimy values in the plane's own indexing: x*dimy + y for the cell planes, like
+        ``Layermap.heights()``, and y*dimx + x for the frequency planes, like ``Layermap.frequency()``. The selected members must
+        have equal dims."""
+        self._check_members()
+        if plane not in capi.PLANES:
+            raise ValueError(f"plane: one of {sorted(capi.PLANES)}")
+        if members is None:
+            idx = list(range(len(self.members)))
+        else:
+            idx = []
+            for m in members:
+                if isinstance(m, (int, np.integer)):
+                    idx.append(int(m))
+                else:
+                    k = next((k for k, x in enumerate(self.members) if x is m), None)
+                    if k is None:
+                        raise ValueError("plane_stats: not a member of this ensemble")
+                    idx.append(k)
+        which = np.array(idx or [0], np.int32)
+        # (the library checks the selection and names the offender; the shape comes from the first member it accepts)
+        first = self.members[idx[0]] if idx and 0 <= idx[0] < len(self.members) else None
+        cells = first.dimx * first.dimy if first else 1
+        out = {"mean": np.zeros(cells)}
+        if var:
+            out["var"] = np.zeros(cells)
+        if minmax:
+            out["vmin"] = np.zeros(cells); out["vmax"] = np.zeros(cells)
+        if nonzero:
+            out["nonzero"] = np.zeros(cells, np.uint32)
+        self._chk(self.L.smx_ensemble_plane_stats(self.h, capi.PLANES[plane], None if members is None else capi.ptr(which), len(idx), capi.ptr(out["mean"]), capi.ptr(out.get("var")),
+                                                  capi.ptr(out.get("vmin")), capi.ptr(out.get("vmax")), capi.ptr(out.get("nonzero"))))
+        return out
+
     def timing(self) -> dict:
         t = capi.Timing()
         self._chk(self.L.smx_ensemble_get_timing(self.h, C.byref(t), C.sizeof(t)))
