@@ -271,6 +271,12 @@ int smx_digest(smx_ctx* ctx, double* sumh, uint64_t* nsec, uint64_t* typehash);
  * against. The unsized ones keep the layouts they were introduced with (smx_counters: the first 16 words, i.e. without
  * spec_subphases_cut / spec_serial_particles; smx_timing: the first 144 bytes) so that older binaries are never written past their
  * struct -- an ABI note for callers of rounds 1-4: INTEGRATION.md "ABI notes". */
+/* The run-time switches (environment variables SMX_*, read once per process; README.md "Run-time switches") as text, one line per
+ * switch: "NAME=value default class\n" -- the value this process read (the default where the variable is not set; "-" = not set and no
+ * default), the default, and the class: neutral (selects code or a launch shape, results bit-identical), changes_results (part of a
+ * schedule's definition) or diagnostic (tracing, profiling, poll pacing, the spin budget). Read-only; needs no context and no device.
+ * Writes a NUL-terminated string of *needed bytes (needed may be NULL); -2 and nothing written where cap is smaller (or buf NULL). */
+int smx_switches(char* buf, uint64_t cap, uint64_t* needed);
 int smx_get_counters_sized(smx_ctx* ctx, smx_counters* out, uint64_t struct_size);
 int smx_get_timing_sized(smx_ctx* ctx, smx_timing* out, uint64_t struct_size);
 int smx_get_counters(smx_ctx* ctx, smx_counters* out);

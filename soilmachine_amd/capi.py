@@ -99,6 +99,7 @@ SYMBOLS = [
     "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
     "smx_ensemble_figures", "smx_ensemble_plane_stats",
+    "smx_switches",
 ]
 
 ENSEMBLE_MAX_MEMBERS = 4096    # SMX_ENSEMBLE_MAX_MEMBERS
@@ -216,6 +217,7 @@ def load() -> C.CDLL:
     L.smx_ensemble_timing_reset.argtypes = [vp]
     L.smx_ensemble_figures.argtypes = [vp, vp, u64]
     L.smx_ensemble_plane_stats.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("smx_destroy", "smx_last_error", "smx_stream", "smx_lbm_destroy", "smx_lbm_last_error",
@@ -223,6 +225,24 @@ def load() -> C.CDLL:
             f.restype = C.c_int
     _lib = L
     return L
+
+
+def switches() -> dict:
+    """The library's run-time switches (smx_switches): name -> {"value", "default", "class"} as this process read them; "-" = not set
+    and no default. Needs no device."""
+    L = load()
+    need = C.c_uint64()
+    L.smx_switches(None, 0, C.byref(need))
+    buf = C.create_string_buffer(int(need.value))
+    rc = L.smx_switches(buf, need.value, None)
+    if rc != 0:
+        raise RuntimeError(f"smx_switches failed (rc={rc})")
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, rest = line.split("=", 1)
+        value, default, cls = rest.rsplit(" ", 2)
+        out[name] = {"value": value, "default": default, "class": cls}
+    return out
 
 
 def ptr(a):

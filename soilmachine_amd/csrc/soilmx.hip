@@ -50,16 +50,89 @@ using namespace smx;
 static_assert(sizeof(SoilP) == sizeof(smx_soil), "smx_soil layout");
 static_assert(sizeof(Sec) == 32, "Sec must be 32 bytes");
 
-// Environment knobs (experiments; README.md lists them): the variable's value, or `dflt` where it is not set. A call site keeps what it
-// makes of the value in a function-local static: read once per process.
-static const char* env_str(const char* name) { return getenv(name); }
-static long long env_int(const char* name, long long dflt) { const char* e = env_str(name); return e ? atoll(e) : dflt; }
-static bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
-// ... and the knobs that more than one site reads
-static uint32_t flood_prof() { static const uint32_t v = (uint32_t)env_int("SMX_FLOOD_PROF", 0); return v; }   // (not 0: k_relax_floods and k_grid_tiles_flow keep duration histograms, printed by smx_destroy)
-static uint32_t relax_mega_flags() { static const uint32_t v = (uint32_t)env_int("SMX_RELAX_MEGA_FLAGS", 0); return v; }   // (1: every thread fences at a barrier; 2: k_relax_epochs keeps workgroup 0's clock)
-static bool trace_batch() { static const bool on = env_flag("SMX_TRACE_BATCH", false); return on; }
-static bool coop_on() { static const bool on = env_flag("SMX_COOP", true); return on; }                         // (the wave-loop kernels of soil_coop.h)
+// Environment switches (experiments; README.md lists them). ONE table, read once per process -- at the first look-up or the first
+// smx_switches call, whichever comes first: name, default, class and the value this process read. A call site names its switch
+// (env_int / env_flag / env_str) and keeps what it makes of the value -- clamps included -- in a function-local static; a name that is not in
+// the table aborts. Classes: NEUTRAL selects code or a launch shape and leaves results bit-identical (tests/test_gpu_switches.py holds every
+// one of them to that); CHANGES is part of a schedule's definition (the restatement in oracle/ and tests/hostsim depend on the value:
+// SMX_BATCH_CHUNK is the oracle's B_CHUNK -- the batched schedule looks at the number of running particles once per chunk --, the
+// schedule pins and the relaxed steps per epoch); DIAGNOSTIC is tracing, profiling, poll pacing and the spin budget.
+// A default of nullptr: the switch acts only where the variable is set.
+enum { SW_NEUTRAL = 0, SW_CHANGES = 1, SW_DIAGNOSTIC = 2 };
+struct EnvSwitch { const char* name; const char* dflt; int cls; };
+static const EnvSwitch ENV_SWITCHES[] = {
+  // exact (speculative) engine
+  {"SMX_COOP", "1", SW_NEUTRAL},                      // (0: one particle per lane instead of the wave-loop kernels of soil_coop.h)
+  {"SMX_SPEC_LANES", "1", SW_NEUTRAL},                // (particles per wavefront under SMX_COOP=0, 1..64)
+  {"SMX_SPEC_MODE", "3", SW_NEUTRAL},                 // (bit0 blocked-particle filter, bit1 suspend/resume: water)
+  {"SMX_SPEC_MODE_WIND", "2", SW_NEUTRAL},
+  {"SMX_WIND_SCOUT", "1", SW_NEUTRAL},
+  {"SMX_SPEC_SUB", "4096", SW_NEUTRAL},               // (top-level particles of a sub-phase, >= 64)
+  {"SMX_SPEC_MAXNEST", "8192", SW_NEUTRAL},           // (nested-particle slots of a sub-phase, 128..60000)
+  {"SMX_TRACE_ROUNDS", "0", SW_DIAGNOSTIC},
+  // grid pass
+  {"SMX_CLASSIFY_SCALAR", "0", SW_NEUTRAL},           // (1: k_grid_classify also where k_grid_classify8 fits)
+  {"SMX_GRID_FLOW_WAVES", "2048", SW_NEUTRAL},        // (wavefronts of k_grid_tiles_flow, >= 1)
+  {"SMX_GRID_POLL_NAPS", "2", SW_DIAGNOSTIC},         // (x 3.4 us between two polls of a waiting tile)
+  // throughput engines: launch shapes
+  {"SMX_BATCH_WAVES", "256", SW_NEUTRAL},             // (wavefronts the running particles are spread over; 0 = 64 per wavefront)
+  {"SMX_BATCH_OCC2_ABOVE", "65536", SW_NEUTRAL},      // (running particles above which k_batch_epoch2 runs)
+  {"SMX_RELAX_CHUNK_KIDS", "8", SW_NEUTRAL},          // (epochs per chunk of a nested relaxed generation: without strips the result does not depend on where a generation is cut)
+  {"SMX_RELAX_TAIL", "1", SW_NEUTRAL},
+  {"SMX_RELAX_TAIL_AT", "256", SW_NEUTRAL},           // (RELAX_TAIL)
+  {"SMX_RELAX_MEGA", "0", SW_NEUTRAL},                // (off by default: measured slower, see k_relax_epochs)
+  {"SMX_RELAX_MEGA_BLOCKS", "0", SW_NEUTRAL},         // (0: one workgroup per CU)
+  {"SMX_RELAX_MEGA_WAVES", "0", SW_NEUTRAL},          // (0: one wavefront per workgroup)
+  {"SMX_RELAX_MEGA_CHUNK", "0", SW_NEUTRAL},          // (0: the chunk lengths of the per-phase launches)
+  {"SMX_RELAX_MEGA_FLAGS", "0", SW_NEUTRAL},          // (1: every thread fences at a barrier; 2: k_relax_epochs keeps workgroup 0's clock)
+  {"SMX_RELAX_FLOOD_BLOCKS", "1024", SW_NEUTRAL},     // (floods: at least this many wavefronts to spread over)
+  {"SMX_RELAX_CASC_FLOW", "1024", SW_NEUTRAL},        // (wavefronts of k_relax_cascade_flow; 0: nine launches of k_relax_cascade)
+  {"SMX_RELAX_CASC_BLOCKS", "64", SW_NEUTRAL},        // (wavefronts of each of the nine launches)
+  // throughput engines: the schedule itself
+  {"SMX_BATCH_CHUNK", "32", SW_CHANGES},              // (B_CHUNK)
+  {"SMX_BATCH_SCHED", nullptr, SW_CHANGES},           // "tshift,dilate,maxsteps" pins the water schedule
+  {"SMX_BATCH_SCHED_WIND", nullptr, SW_CHANGES},
+  {"SMX_BATCH_SCHED_TAIL", nullptr, SW_CHANGES},      // "thr:tshift,dilate,maxsteps[;thr2:...]" (ascending thr): first thr >= nlive wins
+  {"SMX_BATCH_SCHED_TAIL_WIND", nullptr, SW_CHANGES},
+  {"SMX_RELAX_WIND_MIN", nullptr, SW_CHANGES},        // (running wind particles above which the wind phase is relaxed)
+  {"SMX_RELAX_WATER_STEPS", "0", SW_CHANGES},         // (1..R_MAXSTEPS; 0: the context's own)
+  {"SMX_RELAX_WIND_STEPS", "0", SW_CHANGES},
+  // diagnostics
+  {"SMX_TRACE_BATCH", "0", SW_DIAGNOSTIC},
+  {"SMX_FLOOD_PROF", "0", SW_DIAGNOSTIC},             // (not 0: k_relax_floods and k_grid_tiles_flow keep duration histograms, printed by smx_destroy)
+  {"SMX_STEP_EVENT_SAMPLE", "8", SW_DIAGNOSTIC},      // (every n-th launch of the relaxed step kernel sits between a pair of events)
+  {"SMX_SPIN_BUDGET", "-1", SW_DIAGNOSTIC},           // (polls a dataflow wait may last; < 0: the kernels' own)
+  // LBM wind
+  {"SMX_LBM_NT", "0", SW_NEUTRAL},
+  {"SMX_LBM_XCD", "0", SW_NEUTRAL},
+};
+constexpr int N_ENV_SWITCHES = (int)(sizeof(ENV_SWITCHES) / sizeof(ENV_SWITCHES[0]));
+static_assert(B_CHUNK == 32, "the default of SMX_BATCH_CHUNK in ENV_SWITCHES is B_CHUNK");
+struct EnvValues { const char* v[N_ENV_SWITCHES]; };          // what the process read: the variable's text, or the default where it is not set
+static const EnvValues& env_values() {
+  static const EnvValues vals = [] {
+    EnvValues r;
+    for (int i = 0; i < N_ENV_SWITCHES; i++) {
+      const char* e = getenv(ENV_SWITCHES[i].name);
+      r.v[i] = e ? strdup(e) : ENV_SWITCHES[i].dflt;          // (a copy: a later setenv does not reach a switch that was read)
+    }
+    return r;
+  }();
+  return vals;
+}
+static const char* env_str(const char* name) {
+  for (int i = 0; i < N_ENV_SWITCHES; i++)
+    if (!strcmp(ENV_SWITCHES[i].name, name)) return env_values().v[i];
+  fprintf(stderr, "[soilmx] %s is not in ENV_SWITCHES\n", name);
+  abort();
+}
+static long long env_int(const char* name) { const char* e = env_str(name); return e ? atoll(e) : 0; }
+static bool env_flag(const char* name) { return env_int(name) != 0; }
+// ... and the switches that more than one site reads
+static uint32_t flood_prof() { static const uint32_t v = (uint32_t)env_int("SMX_FLOOD_PROF"); return v; }
+static uint32_t relax_mega_flags() { static const uint32_t v = (uint32_t)env_int("SMX_RELAX_MEGA_FLAGS"); return v; }
+static bool trace_batch() { static const bool on = env_flag("SMX_TRACE_BATCH"); return on; }
+static bool coop_on() { static const bool on = env_flag("SMX_COOP"); return on; }
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -278,7 +351,7 @@ __global__ void __launch_bounds__(256) k_ens_plane_stats(const EnsEntry* __restr
 // SIMDs, and one particle step is issue-bound (a few thousand dependent instructions), so one particle per wave
 // is fastest (measured at 1024^2: 1 lane 349 ms, 8 lanes 429 ms, 32 lanes 537 ms per water phase).
 static int spec_lanes() {
-  static const int v = (int)std::min(64ll, std::max(1ll, env_int("SMX_SPEC_LANES", 1)));
+  static const int v = (int)std::min(64ll, std::max(1ll, env_int("SMX_SPEC_LANES")));
   return v;
 }
 
@@ -461,7 +534,7 @@ __global__ void __launch_bounds__(64) k_relax_cascade(DevState s, BatchShared bs
 // dynamic cursor guarantees that every dependency belongs to a wavefront that is already running, so only a fault gets there -- raises bs.ctrl[BC_STALLED], every other
 // waiter sees the flag within 1 024 polls and stops waiting too, the kernel drains, and the host fails the call (-9) instead of hanging the stream.
 // SMX_SPIN_BUDGET overrides the number of polls (tests/test_gpu_relaxed.py sets 1 to see the error).
-static uint32_t spin_budget(uint32_t dflt) { static const long long v = env_int("SMX_SPIN_BUDGET", -1); return v >= 0 ? (uint32_t)v : dflt; }
+static uint32_t spin_budget(uint32_t dflt) { static const long long v = env_int("SMX_SPIN_BUDGET"); return v >= 0 ? (uint32_t)v : dflt; }
 __device__ __forceinline__ bool spin_wait_while(const uint32_t* f, uint32_t busy, uint32_t* stalled, uint32_t budget, uint32_t sleep_a, uint32_t naps) {
   uint32_t spins = 0;
   while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == busy) {
@@ -567,6 +640,7 @@ __global__ void __launch_bounds__(64) k_relax_floods(DevState s, BatchShared bs,
 // workgroup barriers where the dense schedule has kernel boundaries. Same phases, same order, same results; no launch per phase.
 constexpr uint32_t RELAX_TAIL = 256;                          // running particles up to which the tail kernel takes over (one per thread of its
                                                               // workgroup; round 3: 1 024 = four per thread -- 2.6 % slower on the headline, r04 sweep)
+static_assert(RELAX_TAIL == 256, "the default of SMX_RELAX_TAIL_AT in ENV_SWITCHES is RELAX_TAIL");
 __global__ void __launch_bounds__(256) k_relax_tail(DevState s, BatchShared bs, uint32_t nlive, uint32_t epoch0, uint32_t nepochs, uint32_t tag0) {
   SMX_LOAD_SOILS(sh)
   __shared__ uint32_t busy;
@@ -845,7 +919,7 @@ __global__ void __launch_bounds__(256) k_relax_epochs(DevState s, BatchShared bs
 // how many particles share a wavefront: as few as fill `SMX_BATCH_WAVES` wavefronts (default 256 = one per CU; 0 = always 64;
 // measured in profiles/r02_batched_schedules.md, sweep 5). Which lane runs a slot has no influence on results.
 static uint32_t batch_lanes_per_wave(uint32_t nlive) {
-  static const uint32_t waves = (uint32_t)env_int("SMX_BATCH_WAVES", 256);
+  static const uint32_t waves = (uint32_t)env_int("SMX_BATCH_WAVES");
   if (!waves) return 64u;
   const uint32_t l = (nlive + waves - 1u) / waves;
   return l < 1u ? 1u : (l > 64u ? 64u : l);
@@ -1503,10 +1577,25 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t s
   const smx_soil air = {0, 0, 0, 0, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // surface.h:43-49
   if (smx_set_soils(ctx, &air, 1)) return -1;
   if (smx_srand(ctx, 1)) return -1;
-  // (experiments; read at every context creation, and only a variable that is set overrides)
-  if (env_str("SMX_RELAX_WIND_MIN")) ctx->relax_wind_min = (uint32_t)env_int("SMX_RELAX_WIND_MIN", 0);
-  if (const int v = (int)env_int("SMX_RELAX_WATER_STEPS", 0); v >= 1 && v <= R_MAXSTEPS) ctx->relax_water_steps = v;
-  if (const int v = (int)env_int("SMX_RELAX_WIND_STEPS", 0); v >= 1 && v <= R_MAXSTEPS) ctx->relax_wind_steps = v;
+  // (experiments; only a variable that is set overrides)
+  if (env_str("SMX_RELAX_WIND_MIN")) ctx->relax_wind_min = (uint32_t)env_int("SMX_RELAX_WIND_MIN");
+  if (const int v = (int)env_int("SMX_RELAX_WATER_STEPS"); v >= 1 && v <= R_MAXSTEPS) ctx->relax_water_steps = v;
+  if (const int v = (int)env_int("SMX_RELAX_WIND_STEPS"); v >= 1 && v <= R_MAXSTEPS) ctx->relax_wind_steps = v;
+  return 0;
+}
+// The switch table as text, one line per switch: "NAME=value default class" (value: what this process read; an unset switch without a
+// default shows "-"). Needs neither a context nor a device.
+int smx_switches(char* buf, uint64_t cap, uint64_t* needed) {
+  static const char* const cls[] = {"neutral", "changes_results", "diagnostic"};
+  std::string t;
+  const EnvValues& ev = env_values();
+  for (int i = 0; i < N_ENV_SWITCHES; i++) {
+    const EnvSwitch& w = ENV_SWITCHES[i];
+    t += w.name; t += '='; t += ev.v[i] ? ev.v[i] : "-"; t += ' '; t += w.dflt ? w.dflt : "-"; t += ' '; t += cls[w.cls]; t += '\n';
+  }
+  if (needed) *needed = (uint64_t)t.size() + 1u;
+  if (!buf || cap < t.size() + 1u) return -2;
+  memcpy(buf, t.c_str(), t.size() + 1u);
   return 0;
 }
 int smx_create(const smx_config* cfg, smx_ctx** out) { return create_range(cfg, 0, cfg ? cfg->dimx : 0, nullptr, out); }
@@ -2022,7 +2111,7 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
   // nested-particle slots of a sub-phase: 8192 on the device (21 KB of per-slot records each: 170 MB). With the 1 024 of round 3 a
   // sub-phase of 4 096 particles at the headline's density was cut -- everything in flight rolled back on one lane and run again --
   // after ~650 committed particles (profiles/r04_exact_subphases.md)
-  static const uint32_t maxnest = (uint32_t)std::min(60000ll, std::max(128ll, env_int("SMX_SPEC_MAXNEST", 8192)));
+  static const uint32_t maxnest = (uint32_t)std::min(60000ll, std::max(128ll, env_int("SMX_SPEC_MAXNEST")));
   sh.maxnest = ctx->spec_maxnest ? ctx->spec_maxnest : maxnest;
   const uint32_t slots = cap + sh.maxnest;                  // per-slot records (soil_spec.h "rand() SLOTS")
   HIPCHK(hipMalloc(&sh.part, (size_t)slots * sizeof(SpecPart)));
@@ -2050,15 +2139,15 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
 static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed, int* outcome) {
   // engine mode per phase: water = blocked-filter + suspend/resume, wind = suspend/resume only (long wind particles
   // are nearly always "blocked somewhere": better to let them run up to the contested cell) -- host-sim measurements
-  static const uint32_t mode_water = (uint32_t)env_int("SMX_SPEC_MODE", 3);
-  static const uint32_t mode_wind = (uint32_t)env_int("SMX_SPEC_MODE_WIND", 2);
+  static const uint32_t mode_water = (uint32_t)env_int("SMX_SPEC_MODE");
+  static const uint32_t mode_wind = (uint32_t)env_int("SMX_SPEC_MODE_WIND");
   ctx->sh.mode = wind ? mode_wind : mode_water;
   const SpecShared& sh = ctx->sh;
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemsetAsync(sh.stamp, 0, ctx->ncells * 4, st));
   hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, st, ctx->d, sh, (uint32_t)n);
   const uint32_t L = (uint32_t)spec_lanes();
-  static const bool wind_scout = env_flag("SMX_WIND_SCOUT", true);
+  static const bool wind_scout = env_flag("SMX_WIND_SCOUT");
   const uint32_t ns = (uint32_t)n + SPEC_SCOUT_MARGIN;       // scouted slots
   if (!wind || wind_scout) {
     if (coop_on()) LAUNCH_WIND_WATER(wind, k_spec_scout_coop, dim3(ns), dim3(64), st, ctx->d, sh);
@@ -2066,7 +2155,7 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
   }
   uint32_t np = (uint32_t)n > SPEC_WINDOW ? SPEC_WINDOW : (uint32_t)n, last_base = 0, stall = 0;
   *outcome = 0;
-  static const bool trace_rounds = env_flag("SMX_TRACE_ROUNDS", false);
+  static const bool trace_rounds = env_flag("SMX_TRACE_ROUNDS");
   uint32_t prev_exec = 0, prev_sum = 0;
   if (trace_rounds) HIPCHK(hipStreamSynchronize(st));
   auto t_round = std::chrono::steady_clock::now();
@@ -2123,7 +2212,7 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
 // committed: 0.4 M steps/s on the headline workload). Only what the speculation cannot do at all goes to the serial walker.
 static int spec_phase(smx_ctx* ctx, int32_t n, bool wind) {
   if (n <= 0) return 0;
-  static const uint32_t SPEC_SUB_ENV = (uint32_t)std::max(64ll, env_int("SMX_SPEC_SUB", 4096));
+  static const uint32_t SPEC_SUB_ENV = (uint32_t)std::max(64ll, env_int("SMX_SPEC_SUB"));
   const uint32_t SPEC_SUB = ctx->spec_sub ? ctx->spec_sub : SPEC_SUB_ENV;
   if (spec_alloc(ctx, std::min<uint32_t>((uint32_t)n, SPEC_SUB))) return -1;
   hipStream_t st = ctx->stream;
@@ -2274,7 +2363,7 @@ static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uin
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax_epochs, 256, 0) != hipSuccess) per_cu = 0;
-    static const int want = (int)env_int("SMX_RELAX_MEGA_BLOCKS", 0);   // (0: one workgroup per CU)
+    static const int want = (int)env_int("SMX_RELAX_MEGA_BLOCKS");   // (0: one workgroup per CU)
     int nb = want > 0 ? want : ncu;
     if (nb > ncu * per_cu) nb = ncu * per_cu;
     if (!coop || nb < 1) {
@@ -2286,7 +2375,7 @@ static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uin
   BatchShared bs = ctx->bs;
   uint32_t tag0 = ctx->relax_tag + 1u;
   GridBar* bar = ctx->d_gbar;
-  static const uint32_t dense_waves_env = (uint32_t)env_int("SMX_RELAX_MEGA_WAVES", 0);   // (0: one wavefront per workgroup)
+  static const uint32_t dense_waves_env = (uint32_t)env_int("SMX_RELAX_MEGA_WAVES");   // (0: one wavefront per workgroup)
   uint32_t dense_waves = dense_waves_env ? dense_waves_env : (uint32_t)ctx->mega_blocks, flags = relax_mega_flags();
   void* args[] = {(void*)&ctx->d, (void*)&bs, (void*)&nlive, (void*)&epoch, (void*)&nepochs, (void*)&tag0, (void*)&bar, (void*)&dense_waves, (void*)&flags};
   PhaseTimer tk(ctx, PH_K_EPOCHS, nepochs);
@@ -2305,7 +2394,7 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
                      int* epochs_run) {
   hipStream_t st = ctx->stream;
   const BatchShared& bs = ctx->bs;
-  static const int CHUNK = (int)std::max(1ll, env_int("SMX_BATCH_CHUNK", B_CHUNK));
+  static const int CHUNK = (int)std::max(1ll, env_int("SMX_BATCH_CHUNK"));
   BSched sc = batch_schedule(wind, nlive_sched, ctx->batch_dilate);
   {   // experiments only: SMX_BATCH_SCHED="tshift,dilate,maxsteps" (water) / SMX_BATCH_SCHED_WIND pins the schedule
     static const char* ew = env_str("SMX_BATCH_SCHED"); static const char* ed = env_str("SMX_BATCH_SCHED_WIND");
@@ -2335,14 +2424,14 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
   if (plan.relaxed_now) {
     // relaxed schedule: per epoch one step of every running particle, the queued edits per cell, the nine cascade colours,
     // then one flood epoch behind claim tiles. Without strips the chunk lengths are the launch shape's to choose (batch_plan_chunk).
-    static const int RCHUNK_KIDS = (int)std::max(1ll, env_int("SMX_RELAX_CHUNK_KIDS", 8));
-    static const bool use_tail = env_flag("SMX_RELAX_TAIL", true);
-    static const uint32_t tail_at_env = (uint32_t)env_int("SMX_RELAX_TAIL_AT", RELAX_TAIL);
+    static const int RCHUNK_KIDS = (int)std::max(1ll, env_int("SMX_RELAX_CHUNK_KIDS"));
+    static const bool use_tail = env_flag("SMX_RELAX_TAIL");
+    static const uint32_t tail_at_env = (uint32_t)env_int("SMX_RELAX_TAIL_AT");
     const uint32_t tail_at = ctx->relax_tail_at >= 0 ? (uint32_t)ctx->relax_tail_at : tail_at_env;
     const bool tail = !wind && use_tail && nlive <= tail_at;
-    static const bool use_mega_env = env_flag("SMX_RELAX_MEGA", false);   // (off by default: measured slower, see k_relax_epochs)
+    static const bool use_mega_env = env_flag("SMX_RELAX_MEGA");   // (off by default: measured slower, see k_relax_epochs)
     const bool use_mega = ctx->relax_persistent >= 0 ? ctx->relax_persistent != 0 : use_mega_env;
-    static const int mega_chunk = (int)std::max(0ll, env_int("SMX_RELAX_MEGA_CHUNK", 0));   // (0: the chunk lengths of the per-phase launches)
+    static const int mega_chunk = (int)std::max(0ll, env_int("SMX_RELAX_MEGA_CHUNK"));   // (0: the chunk lengths of the per-phase launches)
     const bool mega = !wind && !tail && use_mega && !ctx->mega_off && bs.cstate != nullptr;
     chunk_epochs = strips ? plan.chunk_epochs : (tail ? 64 : (mega && mega_chunk ? mega_chunk : (first ? CHUNK : RCHUNK_KIDS)));
     if (ctx->relax_tag > 0x7FFF0000u) { ctx->relax_tag = 0; HIPCHK(hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, st)); HIPCHK(hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, st)); }   // (tags never repeat; 2 * tag + 1 fits 32 bits)
@@ -2361,14 +2450,14 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
       const uint32_t lpw = batch_lanes_per_wave(nlive);
       const unsigned nbl = (nlive + lpw - 1u) / lpw, nb64 = (nlive + 63u) / 64u;
       const unsigned ncb = (unsigned)(((size_t)nlive * (size_t)(wind ? ctx->bs.rstride : ctx->bs.rsteps) + 63u) / 64u);   // worst case of the flagged / one cascade list
-      static const unsigned fb_min = (unsigned)env_int("SMX_RELAX_FLOOD_BLOCKS", 1024);
+      static const unsigned fb_min = (unsigned)env_int("SMX_RELAX_FLOOD_BLOCKS");
       const unsigned nfb = std::max(fb_min, (unsigned)((nslots + 63u) / 64u));   // floods: at least 1024 wavefronts to spread over
       for (int k = 0; k < chunk_epochs; k++, epoch++) {
         ctx->bs.rtag = ++ctx->relax_tag;
         {
           // the step kernel between its own pair of events -- every `sample`-th launch (an event pair costs a few microseconds of an epoch
           // that lasts a few hundred; the average launch duration bench.py reports is over the bracketed launches only)
-          static const int sample = (int)std::max(0ll, env_int("SMX_STEP_EVENT_SAMPLE", 8));
+          static const int sample = (int)std::max(0ll, env_int("SMX_STEP_EVENT_SAMPLE"));
           const bool timed = sample > 0 && (k % sample) == 0;
           if (wind) ctx->timing.launches_step_wind++; else ctx->timing.launches_step_water++;   // (every launch, bracketed or not)
           if (timed) { PhaseTimer tk(ctx, wind ? PH_K_WIND : PH_K_WATER, 1u); LAUNCH_WIND_WATER(wind, k_relax_step, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw); }
@@ -2376,8 +2465,8 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
         }
         hipLaunchKernelGGL(k_relax_apply, dim3(nb64), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
         hipLaunchKernelGGL(k_relax_filter, dim3(ncb), dim3(64), 0, st, ctx->d, bs, epoch);
-        static const unsigned casc_blocks = (unsigned)env_int("SMX_RELAX_CASC_BLOCKS", 64);
-        static const unsigned casc_flow = (unsigned)env_int("SMX_RELAX_CASC_FLOW", 1024);   // 0: nine launches (round 4)
+        static const unsigned casc_blocks = (unsigned)env_int("SMX_RELAX_CASC_BLOCKS");
+        static const unsigned casc_flow = (unsigned)env_int("SMX_RELAX_CASC_FLOW");   // 0: nine launches (round 4)
         if (casc_flow && bs.cstate) hipLaunchKernelGGL(k_relax_cascade_flow, dim3(std::min(ncb, casc_flow)), dim3(64), 0, st, ctx->d, bs, epoch, spin_budget(1u << 24));
         else {
           const unsigned ncc = std::min(ncb, std::max(1u, casc_blocks));
@@ -2398,7 +2487,7 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
     const unsigned nbl = (nlive + lpw - 1u) / lpw;
     // more wavefronts than SIMDs (> 65 536 running particles): the 256-register build, two wavefronts per SIMD -- +5 % at 16384^2,
     // nothing below (profiles/r02_batched_schedules.md); results do not depend on it
-    static const uint32_t occ2_above = (uint32_t)env_int("SMX_BATCH_OCC2_ABOVE", 65536);
+    static const uint32_t occ2_above = (uint32_t)env_int("SMX_BATCH_OCC2_ABOVE");
     const bool occ2 = nlive > occ2_above;
     for (int k = 0; k < CHUNK; k++, epoch++) {
       if (occ2) LAUNCH_WIND_WATER(wind, k_batch_epoch2, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
@@ -2513,8 +2602,8 @@ static int grid_sweep(smx_ctx* ctx, int phase, int tx_lo, int tx_hi) {
     size_t tb = ctx->tsort_bytes;
     HIPCHK(rocprim::radix_sort_keys(ctx->d_tsort, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)n, 0u, 32u, st));
     HIPCHK(hipMemsetAsync(ctx->d_tcount + 1, 0, 4, st));     // the cursor of the dataflow kernel
-    static const unsigned flow_waves = (unsigned)std::max(1ll, env_int("SMX_GRID_FLOW_WAVES", 2048));
-    static const uint32_t poll_naps = (uint32_t)env_int("SMX_GRID_POLL_NAPS", 2);   // (x 3.4 us between two polls of a waiting tile)
+    static const unsigned flow_waves = (unsigned)std::max(1ll, env_int("SMX_GRID_FLOW_WAVES"));
+    static const uint32_t poll_naps = (uint32_t)env_int("SMX_GRID_POLL_NAPS");   // (x 3.4 us between two polls of a waiting tile)
     { PhaseTimer tk(ctx, PH_K_GRIDTILES); hipLaunchKernelGGL(k_grid_tiles_flow, dim3(std::min<unsigned>(n, flow_waves)), dim3(64), 0, st, ctx->d, bs, g, ctx->d_tpend[1], n, poll_naps | (flood_prof() ? 0x80000000u : 0u), spin_budget(1u << 22)); }
     hipLaunchKernelGGL(k_batch_merge_freed, dim3(1), dim3(256), 0, st, ctx->d, bs);
     HIPCHK(hipStreamSynchronize(st));
@@ -2549,7 +2638,7 @@ static int batch_grid(smx_ctx* ctx) {
 
 static void launch_classify(smx_ctx* ctx) {                  // which cells can the grid pass change at all? (one flag byte per cell in, one bit out)
   PhaseTimer tk(ctx, PH_K_CLASSIFY);
-  static const bool scalar = env_flag("SMX_CLASSIFY_SCALAR", false);
+  static const bool scalar = env_flag("SMX_CLASSIFY_SCALAR");
   if (ctx->cfg.dimy % 8 == 0 && ctx->lcells % 64 == 0 && ctx->c_lo % 64 == 0 && !scalar)
     hipLaunchKernelGGL(k_grid_classify8, dim3((unsigned)((ctx->lcells / 8 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d);
   else
@@ -3340,7 +3429,7 @@ int smx_lbm_step(smx_lbm* l, int32_t n) {
   LBMCHK(hipSetDevice(l->device));
   if (n <= 0) return 0;
   LBMCHK(hipEventRecord(l->ev0, l->stream));
-  static const int variant = (env_flag("SMX_LBM_NT", false) ? 1 : 0) | (env_flag("SMX_LBM_XCD", false) ? 2 : 0);   // measured switches (profiles/r02_lbm_bench.log); results do not depend on them
+  static const int variant = (env_flag("SMX_LBM_NT") ? 1 : 0) | (env_flag("SMX_LBM_XCD") ? 2 : 0);   // measured switches (profiles/r02_lbm_bench.log); results do not depend on them
   for (int s = 0; s < n; s++) {
     const dim3 g(lbm_grid(l)), t(256);
     float *fa = l->f[l->cur], *fb = l->f[l->cur ^ 1];
