@@ -237,6 +237,26 @@ int smx_ensemble_figures(smx_ensemble* e, smx_member_figures* out, uint64_t stru
 enum { SMX_PLANE_HEIGHT = 0, SMX_PLANE_WATER = 1, SMX_PLANE_WFREQ = 2, SMX_PLANE_WINDFREQ = 3 };
 int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* which, int32_t n,
                              double* mean, double* var, double* vmin, double* vmax, uint32_t* nonzero);
+/* ---- forking: a map that already exists becomes the state of another context, or of n new ensemble members, on the device ----
+ * smx_copy_state leaves dst in the state that smx_save(src, f); smx_set_soils(dst, <src's table>); smx_load(dst, f) == 0 leaves it in:
+ * the columns, the three frequency planes, the rand() generator (ring, index, draw count), SCALE, the soil table, the flag plane
+ * as smx_load builds it (water on top, any saturation in the column, OR src's sticky "has held a saturation" bit) and the live-section
+ * count. dst's other counters, its engine and its engine settings stay as they are. dst's pool is laid out as smx_import_columns lays
+ * it out -- buried sections at pool indices 0..used-1 in cell order, bottom -> top within a column, freelist[i] = cap-1-i -- whatever
+ * src's pool looks like, so the two may differ in pool_capacity. Nothing but a few words (totals, an error flag) crosses the host: the
+ * source is counted (k_fork_count), the counts are scanned, the sections are scattered (k_fork_scatter), the planes copied
+ * (k_fork_planes). The call is ordered behind the work queued on src's stream by an event and synchronises before it returns.
+ * smx_ensemble_fork appends n new members to e, each with src's dims and SCALE, the SERIAL engine, pool_capacity sections (0 = src's
+ * own capacity), the smx_copy_state state and every counter zero but the live sections. seeds == NULL: every member continues src's
+ * generator exactly (identical copies, the caller's to perturb); otherwise member i is as after smx_srand(member_i, seeds[i]). src
+ * is any full-map context on the ensemble's device -- standalone of any engine, a member of e or of another ensemble -- and is only
+ * read. The source is counted and scanned once and all members are written by the same two launches, whatever n.
+ * Errors leave dst / e, its members and src exactly as they were: -2 a null argument, n <= 0, more than SMX_ENSEMBLE_MAX_MEMBERS,
+ * dst == src, unequal dims (copy_state), another device, a strip context; -4 src holds more live sections (tops included) than the
+ * destination's pool_capacity; -5 a chain of src leaves its pool or has more links than the pool holds (the text names the cell); a
+ * fork that runs out of device memory returns < 0 and frees every member it had made. */
+int smx_copy_state(smx_ctx* dst, smx_ctx* src);
+int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_capacity, const uint32_t* seeds, smx_ctx** members /* n handles out */);
 
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */

@@ -98,7 +98,7 @@ SYMBOLS = [
     "smx_lbm_step", "smx_lbm_read", "smx_lbm_write_f", "smx_lbm_move", "smx_lbm_get_timing",
     "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
-    "smx_ensemble_figures", "smx_ensemble_plane_stats",
+    "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
     "smx_switches",
 ]
 
@@ -217,6 +217,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_timing_reset.argtypes = [vp]
     L.smx_ensemble_figures.argtypes = [vp, vp, u64]
     L.smx_ensemble_plane_stats.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.smx_copy_state.argtypes = [vp, vp]
+    L.smx_ensemble_fork.argtypes = [vp, vp, i32, u64, vp, C.POINTER(vp)]
     L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)

@@ -42,6 +42,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_relax.h"
 #include "soil_lbm.h"
 #include "soil_observe.h"
+#include "soil_fork.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
 
@@ -344,6 +345,25 @@ __global__ void __launch_bounds__(256) k_ens_plane_stats(const EnsEntry* __restr
   if (c >= cells) return;
   const ObsMembers m{ens_tab(tab_)};
   plane_stats_cell<PLANE>(m, n, c, mean, var, vmin, vmax, nonzero);
+}
+
+// ---------------- forking a map on the device (smx_copy_state / smx_ensemble_fork; bodies: soil_fork.h) ----------------
+// one lane per cell, adjacent lanes on adjacent 32-byte cell records
+__global__ void __launch_bounds__(FORK_LANES) k_fork_count(ForkSrc s, uint32_t* __restrict__ buried, uint8_t* __restrict__ flag, ForkTotals* __restrict__ tot) {
+  __shared__ ForkShared sh;
+  ObsGroup g;
+  fork_count_group(s, g, blockIdx.x, sh, buried, flag, tot);
+}
+// destination blockIdx.y of the table (tab == null: the one destination `one`), workgroup blockIdx.x of its cells
+__global__ void __launch_bounds__(FORK_LANES) k_fork_scatter(ForkSrc s, const uint32_t* __restrict__ buried, const uint32_t* __restrict__ base,
+                                                             const uint8_t* __restrict__ flag, ForkTotals tot, const ForkDst* __restrict__ tab, ForkDst one) {
+  const ForkDst d = tab ? tab[blockIdx.y] : one;
+  ObsGroup g;
+  fork_scatter_group(s, d, g, blockIdx.x, gridDim.x, buried, base, flag, tot);
+}
+__global__ void __launch_bounds__(256) k_fork_planes(ForkSrc s, const ForkDst* __restrict__ tab, ForkDst one) {
+  const ForkDst d = tab ? tab[blockIdx.y] : one;
+  fork_planes_lane(s, d, (uint64_t)blockIdx.x * 256 + threadIdx.x, (uint64_t)gridDim.x * 256);
 }
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
@@ -1405,6 +1425,15 @@ struct EventTimer {
   smx_timing timing{};
 };
 
+// smx_copy_state / smx_ensemble_fork: per-cell counts, their scan, the derived flag bytes, the totals, rocPRIM's temporary storage and
+// the destination table (grown on demand, kept with the destination context or the ensemble)
+struct ForkScratch {
+  uint32_t* buried = nullptr; uint32_t* base = nullptr; uint8_t* flag = nullptr; size_t cells = 0;
+  ForkTotals* tot = nullptr;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  ForkDst* tab = nullptr; uint32_t tab_cap = 0;
+};
+
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
@@ -1460,6 +1489,7 @@ struct smx_ctx : EventTimer {
   struct StripState* strip = nullptr;
   uint32_t* d_tdone = nullptr; uint32_t* d_tpend[2] = {nullptr, nullptr}; uint32_t* d_tcount = nullptr; uint32_t* h_tcount = nullptr; void* d_tsort = nullptr; size_t tsort_bytes = 0; uint32_t tsort_cap = 0;   // grid pass: tile states, pending lists
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
+  ForkScratch fork;                   // smx_copy_state into this context
 };
 
 #define HIPCHK(call)                                                                                  \
@@ -1528,7 +1558,8 @@ extern "C" {
 const char* smx_last_error(smx_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 // stream: queue the context's work on this stream, which the caller owns (smx_ensemble_add); null = a stream of its own
-static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t stream, smx_ctx** out) {
+// bare: leave cells, pool, free list, soil table and generator unwritten -- smx_ensemble_fork fills every one of them on the device
+static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t stream, smx_ctx** out, bool bare = false) {
   if (!cfg || !out || cfg->dimx <= 0 || cfg->dimy <= 0 || cfg->pool_capacity == 0 || cfg->pool_capacity >= 0x7FFFFFFFull) return -2;
   if (x_lo < 0 || x_hi > cfg->dimx || x_lo >= x_hi) return -2;
   smx_ctx* ctx = new smx_ctx();
@@ -1567,16 +1598,18 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t s
   HIPCHK(hipMemsetAsync(d.windfreq, 0, n * 4, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->flags_alloc, 0, ln + 8, ctx->stream));
   HIPCHK(hipMemsetAsync(d.ctr, 0, C_COUNT * 8, ctx->stream));
-  {   // all columns empty
+  if (!bare) {   // all columns empty
     std::vector<Sec> empty(ln);
     for (size_t i = 0; i < ln; i++) { empty[i].size = 0; empty[i].floor = 0; empty[i].sat = 0; empty[i].type = EMPTY; empty[i].prev = NIL; }
     HIPCHK(hipMemcpyAsync(ctx->cells_alloc, empty.data(), ln * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  if (reset_pool(ctx)) return -1;
-  const smx_soil air = {0, 0, 0, 0, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // surface.h:43-49
-  if (smx_set_soils(ctx, &air, 1)) return -1;
-  if (smx_srand(ctx, 1)) return -1;
+  if (!bare) {
+    if (reset_pool(ctx)) return -1;
+    const smx_soil air = {0, 0, 0, 0, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // surface.h:43-49
+    if (smx_set_soils(ctx, &air, 1)) return -1;
+    if (smx_srand(ctx, 1)) return -1;
+  }
   // (experiments; only a variable that is set overrides)
   if (env_str("SMX_RELAX_WIND_MIN")) ctx->relax_wind_min = (uint32_t)env_int("SMX_RELAX_WIND_MIN");
   if (const int v = (int)env_int("SMX_RELAX_WATER_STEPS"); v >= 1 && v <= R_MAXSTEPS) ctx->relax_water_steps = v;
@@ -1609,6 +1642,7 @@ int smx_create_strip(const smx_config* cfg, int32_t x_lo, int32_t x_hi, smx_ctx*
   if (ctx->partial()) { ctx->err = what ": not available on a strip context (smx_create_strip): it holds only a part of the map"; return -2; }
 
 static void strips_free(smx_ctx* ctx);
+static void fork_free(ForkScratch& f);
 void smx_destroy(smx_ctx* ctx) {
   if (!ctx) return;
   if (ctx->ensemble) { ctx->err = "smx_destroy: this context is a member of an ensemble; smx_ensemble_destroy frees it (nothing was freed)"; return; }
@@ -1654,6 +1688,7 @@ void smx_destroy(smx_ctx* ctx) {
   hipFree(d.wfreq); hipFree(d.wtrack); hipFree(d.windfreq); hipFree(d.rnd); hipFree(d.ctr);
   hipFree(d.active); hipFree(d.active1); hipFree(d.active2); hipFree(ctx->d_scratch); hipFree(ctx->d_soils);
   hipFree(ctx->d_vtx); hipFree(ctx->d_vcol); hipFree(ctx->d_plane);
+  fork_free(ctx->fork);
   if (ctx->sh.stamp) {
     SpecShared& sh = ctx->sh;
     hipFree(sh.stamp); hipFree(sh.claim); hipFree(sh.ctrl); hipFree(sh.reclaim); hipHostFree(ctx->h_ctrl);
@@ -2938,6 +2973,7 @@ struct smx_ensemble : EventTimer {
   // smx_ensemble_figures / smx_ensemble_plane_stats: results on the device and their pinned landing place (grown on demand, kept)
   void* d_obs = nullptr; size_t d_obs_cap = 0;
   void* h_obs = nullptr; size_t h_obs_cap = 0;
+  ForkScratch fork;                       // smx_ensemble_fork
 };
 
 #define EHIPCHK(call)                                                                                 \
@@ -2998,6 +3034,7 @@ void smx_ensemble_destroy(smx_ensemble* e) {
   ens_free_tables(e);
   hipFree(e->d_obs);
   if (e->h_obs) hipHostFree(e->h_obs);
+  fork_free(e->fork);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3236,6 +3273,188 @@ int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* whic
   const char* h = (const char*)e->h_obs;
   for (int k = 0; k < 4; k++) if (*want[k]) memcpy(*want[k], h + off[k], cells * sizeof(double));
   if (nonzero) memcpy(nonzero, h + off[4], cells * sizeof(uint32_t));
+  return 0;
+}
+
+// ---------------- forking a map on the device (smx_copy_state / smx_ensemble_fork; kernels: soil_fork.h) ----------------
+// Both calls: k_fork_count, rocPRIM's exclusive scan and one 24-byte copy back decide -4 / -5 before anything is written or allocated;
+// then k_fork_scatter and k_fork_planes write every destination (blockIdx.y) -- the same launches whatever the member count.
+static void fork_free(ForkScratch& f) {
+  hipFree(f.buried); hipFree(f.base); hipFree(f.flag); hipFree(f.tot); hipFree(f.temp); hipFree(f.tab);
+  f = ForkScratch();
+}
+static int fork_reserve(ForkScratch& f, size_t ncells, uint32_t ntab, hipStream_t st, std::string& err) {
+  bool ok = true;
+  if (ncells > f.cells || !f.tot) {
+    if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+    hipFree(f.buried); hipFree(f.base); hipFree(f.flag); hipFree(f.temp); hipFree(f.tot);
+    f.buried = f.base = nullptr; f.flag = nullptr; f.temp = nullptr; f.tot = nullptr; f.cells = 0; f.temp_bytes = 0;
+    size_t tb = 0;
+    ok = ok && rocprim::exclusive_scan(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    ok = ok && hipMalloc(&f.buried, ncells * 4) == hipSuccess && hipMalloc(&f.base, ncells * 4) == hipSuccess && hipMalloc(&f.flag, ncells) == hipSuccess &&
+         hipMalloc(&f.tot, sizeof(ForkTotals)) == hipSuccess && hipMalloc(&f.temp, tb ? tb : 8) == hipSuccess;
+    if (ok) { f.cells = ncells; f.temp_bytes = tb; }
+  }
+  if (ok && ntab > f.tab_cap) {
+    if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+    hipFree(f.tab); f.tab = nullptr; f.tab_cap = 0;
+    ok = ok && hipMalloc(&f.tab, (size_t)ntab * sizeof(ForkDst)) == hipSuccess;
+    if (ok) f.tab_cap = ntab;
+  }
+  if (!ok) { (void)hipGetLastError(); fork_free(f); err = "out of device memory for the fork scratch"; return -1; }
+  return 0;
+}
+static ForkSrc fork_src(const smx_ctx* src) {
+  ForkSrc s;
+  s.cells = src->d.cells; s.pool = src->d.pool; s.flags = src->d.flags;
+  s.wfreq = src->d.wfreq; s.wtrack = src->d.wtrack; s.windfreq = src->d.windfreq;
+  s.soils = src->d_soils; s.rnd = src->d.rnd;
+  s.cap = src->cfg.pool_capacity; s.ncells = src->ncells; s.nsoils = (uint32_t)src->nsoils;
+  return s;
+}
+static ForkDst fork_dst(const smx_ctx* c, bool seeded, uint32_t seed) {
+  ForkDst d;
+  d.cells = c->d.cells; d.pool = c->d.pool; d.freelist = c->d.freelist; d.free_count = c->d.free_count; d.flags = c->d.flags;
+  d.wfreq = c->d.wfreq; d.wtrack = c->d.wtrack; d.windfreq = c->d.windfreq;
+  d.soils = c->d_soils; d.rnd = c->d.rnd; d.ctr = c->d.ctr;
+  d.cap = c->cfg.pool_capacity; d.seeded = seeded ? 1u : 0u; d.seed = seed;
+  return d;
+}
+// the work queued on src's stream happens before what `st` is given from here on
+static int fork_order(smx_ctx* src, hipStream_t st, std::string& err) {
+  if (src->stream == st) return 0;
+  hipEvent_t ev;
+  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreateWithFlags failed"; return -1; }
+  const bool ok = hipEventRecord(ev, src->stream) == hipSuccess && hipStreamWaitEvent(st, ev, 0) == hipSuccess;
+  hipEventDestroy(ev);   // (released once the wait has passed it)
+  if (!ok) { err = "could not order the copy behind the source's stream"; return -1; }
+  return 0;
+}
+// count + scan on `st`, the totals back, the verdict for a destination pool of dst_cap sections (the text goes to err)
+static int fork_measure(const char* who, smx_ctx* src, ForkScratch& f, hipStream_t st, uint64_t dst_cap, ForkTotals& tot, std::string& err) {
+  const ForkSrc s = fork_src(src);
+  const ForkTotals zero = {0ull, 0ull, FORK_NONE};
+  const unsigned nb = (unsigned)((s.ncells + FORK_LANES - 1) / FORK_LANES);
+  bool ok = hipMemcpyAsync(f.tot, &zero, sizeof(zero), hipMemcpyHostToDevice, st) == hipSuccess;
+  hipLaunchKernelGGL(k_fork_count, dim3(nb), dim3(FORK_LANES), 0, st, s, f.buried, f.flag, f.tot);
+  size_t tb = 0;   // (what THIS size needs: the scratch was sized for the largest map so far)
+  ok = ok && rocprim::exclusive_scan(nullptr, tb, f.buried, f.base, 0u, (size_t)s.ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  if (ok && tb > f.temp_bytes) {
+    ok = hipStreamSynchronize(st) == hipSuccess;
+    hipFree(f.temp); f.temp = nullptr; f.temp_bytes = 0;
+    ok = ok && hipMalloc(&f.temp, tb) == hipSuccess;
+    if (ok) f.temp_bytes = tb;
+  }
+  ok = ok && rocprim::exclusive_scan(f.temp, tb, f.buried, f.base, 0u, (size_t)s.ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(&tot, f.tot, sizeof(tot), hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess;
+  if (!ok) { err = std::string(who) + ": counting the source's sections failed on the device"; return -1; }
+  const int v = fork_verdict(tot, dst_cap);
+  if (v == -5) {
+    const unsigned long long c = tot.bad;
+    err = std::string(who) + ": corrupt section chain in the source, cell " + std::to_string(c) + " (x " + std::to_string(c / (unsigned long long)src->cfg.dimy) + ", y " +
+          std::to_string(c % (unsigned long long)src->cfg.dimy) + "): it leaves the pool or has more links than the pool holds";
+  } else if (v == -4) {
+    err = std::string(who) + ": the source holds " + std::to_string(tot.used + tot.nonempty) + " live sections, more than the destination's pool_capacity " + std::to_string(dst_cap);
+  }
+  return v;
+}
+// scatter + planes for ntab destinations of the table (tab == null: `one`); asynchronous on `st`
+static void fork_write(smx_ctx* src, const ForkScratch& f, hipStream_t st, const ForkTotals& tot, const ForkDst* tab, uint32_t ntab, const ForkDst& one) {
+  const ForkSrc s = fork_src(src);
+  const unsigned nb = (unsigned)((s.ncells + FORK_LANES - 1) / FORK_LANES);
+  hipLaunchKernelGGL(k_fork_scatter, dim3(nb, ntab), dim3(FORK_LANES), 0, st, s, f.buried, f.base, f.flag, tot, tab, one);
+  const unsigned pb = (unsigned)std::min<size_t>(2048, (s.ncells / 4 + 255) / 256 + 1);
+  hipLaunchKernelGGL(k_fork_planes, dim3(pb, ntab), dim3(256), 0, st, s, tab, one);
+}
+static void fork_adopt(smx_ctx* dst, const smx_ctx* src) {   // what smx_set_soils and smx_load leave in the host's copy
+  dst->nsoils = src->nsoils; dst->d.nsoils = src->d.nsoils;
+  dst->d.scale = src->d.scale; dst->cfg.scale = src->d.scale;
+}
+
+int smx_copy_state(smx_ctx* dst, smx_ctx* src) {
+  if (!dst) return -2;
+  smx_ctx* ctx = dst;
+  if (!src) { ctx->err = "smx_copy_state: src is null"; return -2; }
+  if (dst == src) { ctx->err = "smx_copy_state: dst and src are the same context"; return -2; }
+  if (src->partial() || dst->partial()) { ctx->err = "smx_copy_state: not available on a strip context (smx_create_strip): it holds only a part of the map"; return -2; }
+  if (src->cfg.dimx != dst->cfg.dimx || src->cfg.dimy != dst->cfg.dimy) {
+    ctx->err = "smx_copy_state: dst is " + std::to_string(dst->cfg.dimx) + "x" + std::to_string(dst->cfg.dimy) + ", src is " + std::to_string(src->cfg.dimx) + "x" +
+               std::to_string(src->cfg.dimy) + ": the dims must be equal";
+    return -2;
+  }
+  if (src->cfg.device != dst->cfg.device) { ctx->err = "smx_copy_state: dst and src live on different devices"; return -2; }
+  if (!src->stream || !dst->stream) { ctx->err = "smx_copy_state: a context without a device"; return -3; }
+  roctx_range rr("soilmx:copy_state");
+  HIPCHK(hipSetDevice(dst->cfg.device));
+  std::string why;
+  if (fork_reserve(dst->fork, src->ncells, 0, dst->stream, why)) { ctx->err = "smx_copy_state: " + why; return -1; }
+  if (fork_order(src, dst->stream, why)) { ctx->err = "smx_copy_state: " + why; return -1; }
+  ForkTotals tot;
+  if (int rc = fork_measure("smx_copy_state", src, dst->fork, dst->stream, dst->cfg.pool_capacity, tot, why)) { ctx->err = why; return rc; }
+  fork_write(src, dst->fork, dst->stream, tot, nullptr, 1, fork_dst(dst, false, 0));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(dst->stream));
+  fork_adopt(dst, src);
+  return 0;
+}
+
+int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_capacity, const uint32_t* seeds, smx_ctx** members) {
+  if (!e) return -2;
+  if (!src || !members) { e->err = "smx_ensemble_fork: null argument"; return -2; }
+  if (!e->stream) { e->err = "smx_ensemble_fork: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (n <= 0) { e->err = "smx_ensemble_fork: n = " + std::to_string(n) + ": at least one member"; return -2; }
+  if (e->members.size() + (size_t)n > (size_t)SMX_ENSEMBLE_MAX_MEMBERS) {
+    e->err = "smx_ensemble_fork: " + std::to_string(e->members.size()) + " members + " + std::to_string(n) + " would pass SMX_ENSEMBLE_MAX_MEMBERS (" + std::to_string((int)SMX_ENSEMBLE_MAX_MEMBERS) + ")";
+    return -2;
+  }
+  if (src->partial()) { e->err = "smx_ensemble_fork: the source is a strip context (smx_create_strip): it holds only a part of the map"; return -2; }
+  if (src->cfg.device != e->device || !src->stream) { e->err = "smx_ensemble_fork: the source lives on another device than the ensemble"; return -2; }
+  smx_config cfg = src->cfg;
+  cfg.scale = src->d.scale; cfg.engine = SMX_ENGINE_SERIAL; cfg.device = e->device; cfg.reserved = 0;
+  if (pool_capacity) cfg.pool_capacity = pool_capacity;
+  if (cfg.pool_capacity >= 0x7FFFFFFFull) { e->err = "smx_ensemble_fork: pool_capacity " + std::to_string(cfg.pool_capacity) + " is out of range"; return -2; }
+  roctx_range rr("soilmx:ensemble_fork");
+  EHIPCHK(hipSetDevice(e->device));
+  std::string why;
+  if (fork_reserve(e->fork, src->ncells, (uint32_t)n, e->stream, why)) { e->err = "smx_ensemble_fork: " + why; return -1; }
+  if (fork_order(src, e->stream, why)) { e->err = "smx_ensemble_fork: " + why; return -1; }
+  ForkTotals tot;
+  if (int rc = fork_measure("smx_ensemble_fork", src, e->fork, e->stream, cfg.pool_capacity, tot, why)) { e->err = why; return rc; }
+  if (int rc = ens_reserve(e, (uint32_t)e->members.size() + (uint32_t)n)) { e->err = "smx_ensemble_fork: " + e->err; return rc; }
+  std::vector<smx_ctx*> made;
+  std::vector<ForkDst> tab;
+  made.reserve((size_t)n); tab.reserve((size_t)n);
+  int rc = 0;
+  for (int32_t i = 0; i < n && rc == 0; i++) {
+    smx_ctx* ctx = nullptr;
+    rc = create_range(&cfg, 0, cfg.dimx, e->stream, &ctx, true);
+    if (rc != 0) {
+      e->err = "smx_ensemble_fork: member " + std::to_string(i) + " of " + std::to_string(n) + ": " + (ctx ? ctx->err : std::string("invalid configuration")) + " (the members made by this call were freed)";
+      if (ctx) smx_destroy(ctx);
+      break;
+    }
+    made.push_back(ctx);
+    tab.push_back(fork_dst(ctx, seeds != nullptr, seeds ? seeds[i] : 0u));
+  }
+  if (rc == 0) {
+    bool ok = hipMemcpyAsync(e->fork.tab, tab.data(), tab.size() * sizeof(ForkDst), hipMemcpyHostToDevice, e->stream) == hipSuccess;
+    if (ok) fork_write(src, e->fork, e->stream, tot, e->fork.tab, (uint32_t)n, ForkDst{});
+    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess;
+    if (!ok) { e->err = "smx_ensemble_fork: writing the members failed on the device (the members made by this call were freed)"; rc = -1; }
+  }
+  if (rc != 0) {
+    hipStreamSynchronize(e->stream);
+    for (smx_ctx* c : made) smx_destroy(c);   // (not yet members: frees what was allocated, leaves the ensemble's stream alone)
+    (void)hipGetLastError();                  // an out-of-memory failure must not surface in the next tick's launch check
+    return rc;
+  }
+  for (int32_t i = 0; i < n; i++) {
+    fork_adopt(made[(size_t)i], src);
+    made[(size_t)i]->ensemble = e;
+    e->members.push_back(made[(size_t)i]);
+    members[i] = made[(size_t)i];
+  }
   return 0;
 }
 

@@ -21,9 +21,9 @@ class EnsembleMember(Layermap):
     """A member of an ``Ensemble``: a ``Layermap`` whose context the ensemble created and frees."""
 
     def __init__(self, ens: "Ensemble", cfg: SoilConfig, dimx: int | None = None, dimy: int | None = None, *, seed: int = 0,
-                 pool: int | None = None):
+                 pool: int | None = None, initialize: bool = True):
         self._ens = ens
-        super().__init__(cfg, dimx, dimy, seed=seed, pool=pool, device=ens.device, engine=capi.ENGINE_SERIAL)
+        super().__init__(cfg, dimx, dimy, seed=seed, pool=pool, device=ens.device, engine=capi.ENGINE_SERIAL, initialize=initialize)
 
     def _open(self, c: capi.Config):
         h = C.c_void_p()
@@ -32,6 +32,19 @@ class EnsembleMember(Layermap):
             raise SoilmxError(f"smx_ensemble_add: {self._ens.last_error()} (rc={rc})")
         self._ens.members.append(self)              # the ensemble holds it from here on, whatever the set-up below does
         return h
+
+    @classmethod
+    def _wrap(cls, ens: "Ensemble", h, src: Layermap, pool: int) -> "EnsembleMember":
+        """A member around a handle the library has already made and filled (smx_ensemble_fork): none of Layermap.__init__'s set-up."""
+        m = cls.__new__(cls)
+        m._ens = ens
+        m.L = ens.L
+        m.cfg, m.dimx, m.dimy, m.seed = src.cfg, src.dimx, src.dimy, src.seed
+        m.pool = int(pool)
+        m.x_range = None
+        m._soils = src._soils
+        m.h = C.c_void_p(h)
+        return m
 
     def close(self):
         """Forget the handle; the context itself belongs to the ensemble (Ensemble.close frees it)."""
@@ -86,12 +99,13 @@ class Ensemble:
 
     # -- members --
     def add(self, cfg: SoilConfig, dimx: int | None = None, dimy: int | None = None, *, seed: int = 0,
-            pool: int | None = None) -> EnsembleMember:
+            pool: int | None = None, initialize: bool = True) -> EnsembleMember:
         """A new member: as ``Layermap(cfg, dimx, dimy, seed=seed, pool=pool)`` -- soils set, srand(seed), initialize(seed).
-        ``pool`` defaults to the reference's POOLSIZE like ``Layermap``; pass a smaller one for many members."""
+        ``pool`` defaults to the reference's POOLSIZE like ``Layermap``; pass a smaller one for many members. ``initialize`` off:
+        an empty map, for a caller that loads a state (``Layermap.load`` / ``restore``)."""
         n = len(self.members)
         try:
-            return EnsembleMember(self, cfg, dimx, dimy, seed=seed, pool=pool)
+            return EnsembleMember(self, cfg, dimx, dimy, seed=seed, pool=pool, initialize=initialize)
         except Exception:
             # set_soils / srand / initialize failed after smx_ensemble_add (e.g. smx_initialize's -4, a pool smaller than cells x
             # layers): take the half-made member out again, so that the ensemble holds exactly the members this object lists
@@ -101,6 +115,24 @@ class Ensemble:
                     self.L.smx_ensemble_remove(self.h, m.h)
                     m.h = None
             raise
+
+    def fork(self, src: Layermap, n: int = 1, *, seeds=None, pool: int | None = None) -> list:
+        """``n`` new members branched from ``src`` on the device (``smx_ensemble_fork``): each holds src's columns, frequency planes,
+        soil table and SCALE with every counter but the live sections at zero. ``src`` is a ``Layermap`` of any engine or an
+        ``EnsembleMember`` (of this ensemble or another) on this device and is only read. ``seeds`` None: every member continues
+        src's rand() stream exactly; a sequence of n seeds: member i is as after ``srand(seeds[i])``. ``pool``: sections per
+        member (None: src's own pool). If the call fails nothing is added."""
+        n = int(n)
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(list(seeds), np.uint32)
+            if sd.shape != (n,):
+                raise ValueError(f"seeds: {sd.size} seeds for {n} members")
+        out = (C.c_void_p * max(n, 1))()
+        self._chk(self.L.smx_ensemble_fork(self.h, src.h, n, int(pool or 0), capi.ptr(sd), out))
+        made = [EnsembleMember._wrap(self, out[i], src, int(pool or src.pool)) for i in range(n)]
+        self.members.extend(made)
+        return made
 
     def remove(self, member: EnsembleMember):
         """Take `member` out of the ensemble and free it (smx_ensemble_remove); the members after it move up one place."""

@@ -172,6 +172,16 @@ class Layermap:
             self._chk(rc)
         return rc == 0
 
+    def copy_from(self, src: "Layermap"):
+        """Take over `src`'s whole state on the device (smx_copy_state): columns, frequency planes, rand() generator, SCALE, soil
+        table, flag plane and live-section count -- what save() on `src` and restore() here would leave, without the host. Equal
+        dims, the same device; this map's pool size, engine and other counters stay."""
+        rc = self.L.smx_copy_state(self.h, src.h)
+        if rc != 0:
+            self._chk(rc)
+        self.cfg = src.cfg
+        self._soils = src._soils
+
     def digest(self) -> dict:
         """The Appendix-E state digest (sum of heights, section count, type hash) + rand() draws consumed."""
         sh, ns, th = C.c_double(), C.c_uint64(), C.c_uint64()

@@ -5,6 +5,13 @@ cell; 5 warm-up ticks, 20 timed. Prints one JSON line and writes profiles/r07_en
 
 usage: ensemble_bench.py [--batches 1,8,64,256,1024] [--warmup 5] [--ticks 20] [--tag bench] [--out profiles] [--no-record] [--no-ref]
        ensemble_bench.py --observe [--batches 1,8,64,256,1024] [--calls 10] [--tag observe]     (writes profiles/r09_ensemble_<tag>.json)
+       ensemble_bench.py --fork [--batches 8,64,256,1024] [--calls 5] [--tag fork] [--no-big]    (writes profiles/r10_ensemble_<tag>.json / .md)
+
+--fork: a spun-up map branched into B members (smx_ensemble_fork) against the path without it: one snapshot() of the source, then per
+member Ensemble.add(initialize off) + load + smx_set_rand_state. Source: the workload below after tick 25. Both paths run in this
+process, alternating, `calls` times each; both must give bit-identical members before a time is taken. Plus one line for a 4096^2
+rockgravelpebblessand source after 5 relaxed ticks, forked into 4 members. SMX_FORK_PROFILE_ONLY=B runs just the fork of B members,
+SMX_FORK_PROFILE_ONLY=1024x8 one fork of a 1024^2 rockgravelpebblessand source (deep columns) into 8 (each for a kernel trace); --scatter-stats FILE folds such a trace's k_fork_scatter time into the record.
 
 --observe: the ensemble OBSERVED in one call (smx_ensemble_figures / smx_ensemble_plane_stats) against the per-member path that
 yields the same numbers on the same state (B x smx_digest + the counter / generator getters; B x smx_read_heights + the numpy member
@@ -276,8 +283,236 @@ def write_observe_md(rec: dict, path: str):
         f.write(head + "\n".join(out) + "\n")
 
 
+# ---------------------------------------------------------------- --fork
+FORK_TICKS = 25
+BIG = {"soil": "rockgravelpebblessand.soil", "size": 4096, "nwater": 64000, "nwind": 16000, "ticks": 5, "members": 4}
+
+
+def _rand_state(m):
+    import ctypes as C
+    ring, idx, calls = (C.c_uint32 * 31)(), C.c_uint32(), C.c_uint64()
+    m._chk(m.L.smx_get_rand_state(m.h, ring, C.byref(idx), C.byref(calls)))
+    return ring, int(idx.value), int(calls.value)
+
+
+def fork_bytes(snap, cap: int, members: int) -> dict:
+    """The bytes the algorithm must move, from the section counts: the count pass reads every record once; per member the scatter
+    reads every record, the two count words and the flag byte per cell, and writes the records, the flag bytes and the free list; the
+    plane copy reads and writes three f32 planes."""
+    n, total = snap.ncells, snap.nsec
+    used = total - int((snap.count > 0).sum())
+    rec = 32 * (n + used)
+    count = rec + n + 9 * n
+    scatter = (rec + 9 * n) + (rec + n + 4 * (cap - used))
+    planes = 2 * 12 * n
+    return {"cells": n, "sections": total, "buried": used, "count_pass": count, "scatter_per_member": scatter, "planes_per_member": planes,
+            "total": count + members * (scatter + planes)}
+
+
+def _fork_once(src, b, pool):
+    ens = Ensemble(0)
+    t0 = time.perf_counter()
+    mem = ens.fork(src, b, pool=pool)
+    return ens, mem, 1e3 * (time.perf_counter() - t0)
+
+
+def _parent_once(src, b, pool):
+    ens = Ensemble(0)
+    t0 = time.perf_counter()
+    snap = src.snapshot()
+    ring, idx, calls = _rand_state(src)
+    mem = []
+    for _ in range(b):
+        m = ens.add(src.cfg, src.dimx, src.dimy, seed=0, pool=pool, initialize=False)
+        m.load(snap)
+        m._chk(m.L.smx_set_rand_state(m.h, ring, idx, calls))
+        mem.append(m)
+    return ens, mem, 1e3 * (time.perf_counter() - t0)
+
+
+def _check_identical(b, ea, ma, eb, mb):
+    from soilmachine_amd.snapshot import compare
+    key = lambda f: (float(f["sumh"]).hex(), f["nsec"], f["typehash"], f["rand_calls"], f["live_sections"], f["wet_cells"], float(f["water_volume"]).hex())
+    fa, fb = [key(f) for f in ea.figures()], [key(f) for f in eb.figures()]
+    if fa != fb or len(set(fa)) != 1:
+        raise SystemExit(f"B={b}: the forked members and the loaded members DISAGREE (figures)")
+    for i in sorted({0, b - 1}):
+        bad = compare(ma[i].snapshot(), mb[i].snapshot())
+        ra, rb = _rand_state(ma[i]), _rand_state(mb[i])
+        if bad or (tuple(ra[0]), ra[1:]) != (tuple(rb[0]), rb[1:]) or ma[i].counters() != mb[i].counters():
+            raise SystemExit(f"B={b}: forked member {i} and loaded member {i} DISAGREE: {bad}")
+
+
+def run_fork(src, snap, b: int, calls: int, pool: int) -> dict:
+    import statistics
+    ea, ma, _ = _fork_once(src, b, pool)
+    eb, mb, _ = _parent_once(src, b, pool)
+    _check_identical(b, ea, ma, eb, mb)
+    ea.close(); eb.close()
+    tf, tp = [], []
+    for _ in range(calls):                                     # alternating: fork, parent path, fork, ...
+        e, _, ms = _fork_once(src, b, pool); tf.append(ms); e.close()
+        e, _, ms = _parent_once(src, b, pool); tp.append(ms); e.close()
+    by = fork_bytes(snap, pool, b)
+    f_ms, p_ms = statistics.median(tf), statistics.median(tp)
+    return {"members": b, "calls": calls, "fork_ms": round(f_ms, 3), "fork_ms_min": round(min(tf), 3), "fork_ms_max": round(max(tf), 3),
+            "parent_path_ms": round(p_ms, 3), "parent_path_ms_min": round(min(tp), 3), "parent_path_ms_max": round(max(tp), 3),
+            "speedup": round(p_ms / f_ms, 2), "algorithmic_bytes": by, "fork_gb_per_s": round(by["total"] / 1e9 / (f_ms / 1e3), 2)}
+
+
+def run_fork_big(calls: int) -> dict:
+    from soilmachine_amd.snapshot import compare
+    import statistics
+    cfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", BIG["soil"]))
+    src = Layermap(cfg, BIG["size"], BIG["size"], seed=0, engine=capi.ENGINE_RELAXED)
+    for _ in range(BIG["ticks"]):
+        src._chk(src.L.smx_tick(src.h, BIG["nwater"], BIG["nwind"], 1, 1))
+    src.sync()
+    snap = src.snapshot()
+    ts = []
+    for k in range(calls + 1):
+        e, mem, ms = _fork_once(src, BIG["members"], None)
+        if k == 0:                                              # (warm-up call: checked against the source's exported state)
+            figs = e.figures()
+            d = snap.digest() if snap.ncells <= 1 << 16 else None
+            if len({(f["nsec"], f["typehash"], float(f["sumh"]).hex()) for f in figs}) != 1 or figs[0]["nsec"] != snap.nsec or (d and d["typehash"] != figs[0]["typehash"]):
+                raise SystemExit("4096^2: the forked members differ from the source")
+            bad = compare(mem[-1].snapshot(), snap)
+            if bad:
+                raise SystemExit(f"4096^2: the last forked member differs from the source: {bad}")
+        else:
+            ts.append(ms)
+        e.close()
+    by = fork_bytes(snap, src.pool, BIG["members"])
+    src.close()
+    ms = statistics.median(ts)
+    return {**BIG, "engine": "relaxed", "pool_sections": src.pool, "calls": calls, "fork_ms": round(ms, 3), "fork_ms_min": round(min(ts), 3), "fork_ms_max": round(max(ts), 3),
+            "parent_path_ms": "not measured", "algorithmic_bytes": by, "fork_gb_per_s": round(by["total"] / 1e9 / (ms / 1e3), 2)}
+
+
+def scatter_stats(path: str) -> dict:
+    """k_fork_scatter / k_fork_count / k_fork_planes out of a rocprofv3 --kernel-trace --stats CSV (*_kernel_stats.csv)."""
+    import csv
+    import glob
+    out = {}
+    if os.path.isdir(path):                                     # (rocprofv3 -d DIR: the file sits in a sub-directory named after the host)
+        found = sorted(glob.glob(os.path.join(path, "**", "*kernel_stats.csv"), recursive=True))
+        if not found:
+            return out
+        path = found[0]
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name", "")
+            for k in ("k_fork_scatter", "k_fork_count", "k_fork_planes"):
+                if k in name:
+                    out[k] = {"calls": int(row["Calls"]), "total_ns": int(float(row["TotalDurationNs"])), "average_ns": float(row["AverageNs"])}
+    return out
+
+
+def profile_deep(size: int, members: int):
+    """One fork of a size^2 rockgravelpebblessand source (deep columns) after 3 relaxed ticks with area-scaled particle counts: the run
+    a kernel trace is taken of, to see what the deepest columns cost a lane-per-cell scatter."""
+    cfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", BIG["soil"]))
+    k = (size / 256.0) ** 2
+    src = Layermap(cfg, size, size, seed=0, pool=32 * size * size, engine=capi.ENGINE_RELAXED)
+    for _ in range(3):
+        src._chk(src.L.smx_tick(src.h, int(250 * k), int(62.5 * k), 1, 1))
+    src.sync()
+    snap = src.snapshot()
+    pool = snap.nsec + 4 * size * size
+    e, _, ms = _fork_once(src, members, pool)
+    print(json.dumps({"profile_only": f"{size}x{members}", "soil": BIG["soil"], "fork_ms": round(ms, 3), "deepest_column": int(snap.count.max()),
+                      "mean_column": round(snap.nsec / snap.ncells, 2), "pool": pool, "algorithmic_bytes": fork_bytes(snap, pool, members)}), flush=True)
+    e.close(); src.close()
+
+
+def main_fork(a):
+    only = os.environ.get("SMX_FORK_PROFILE_ONLY")
+    if only and "x" in only:
+        return profile_deep(*(int(v) for v in only.split("x")))
+    cfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", SOIL))
+    pool = 8 * SIZE * SIZE
+    src = Layermap(cfg, SIZE, SIZE, seed=0, pool=pool, engine=capi.ENGINE_SERIAL)
+    for _ in range(FORK_TICKS):
+        src._chk(src.L.smx_tick(src.h, NWATER, NWIND, 1, 1))
+    src.sync()
+    snap = src.snapshot()
+    if only:                                                    # one fork, nothing else: the run a kernel trace is taken of
+        e, _, ms = _fork_once(src, int(only), pool)
+        print(json.dumps({"profile_only": int(only), "fork_ms": round(ms, 3), "algorithmic_bytes": fork_bytes(snap, pool, int(only))}), flush=True)
+        e.close(); src.close()
+        return
+    rec = {"workload": {"soil": SOIL, "size": SIZE, "nwater": NWATER, "nwind": NWIND, "seed": 0, "pool_sections_per_cell": 8, "state": f"after tick {FORK_TICKS}",
+                        "sections": snap.nsec, "deepest_column": int(snap.count.max()), "calls": a.calls,
+                        "clock": "wall clock around the blocking calls (member creation included, destruction not), the two paths alternating; median (min, max)",
+                        "parent_path": "one snapshot() of the source, then per member Ensemble.add(initialize off) + load + smx_set_rand_state",
+                        "checked": "before a time is taken: figures() of all members of both paths equal; snapshot, generator and counters of the first and the last member equal",
+                        "stream_rate_tb_s": STREAM_TBS},
+           "fork": []}
+    for b in (int(x) for x in a.batches.split(",") if x):
+        r = run_fork(src, snap, b, a.calls, pool)
+        rec["fork"].append(r)
+        print(f"[fork] B={b:5d}  fork {r['fork_ms']:10.3f} ms  parent path {r['parent_path_ms']:11.3f} ms  x{r['speedup']:.1f}", file=sys.stderr, flush=True)
+    src.close()
+    if not a.no_big:
+        rec["fork_4096"] = run_fork_big(max(3, a.calls))
+        print(f"[fork] 4096^2 x {BIG['members']}: {rec['fork_4096']['fork_ms']:.1f} ms", file=sys.stderr, flush=True)
+    rec["k_fork_scatter"] = "not measured"
+    if a.scatter_stats:
+        st = scatter_stats(a.scatter_stats)
+        b = a.scatter_members
+        by = fork_bytes(snap, pool, b)
+        if "k_fork_scatter" in st:
+            sec = st["k_fork_scatter"]["total_ns"] / 1e9
+            rec["k_fork_scatter"] = {"members": b, "kernels": st, "scatter_bytes": b * by["scatter_per_member"], "gb_per_s": round(b * by["scatter_per_member"] / 1e9 / sec, 1),
+                                     "share_of_stream_rate": round(b * by["scatter_per_member"] / 1e9 / sec / (1e3 * STREAM_TBS), 4),
+                                     "source": "a separate rocprofv3 --kernel-trace --stats run of SMX_FORK_PROFILE_ONLY=" + str(b)}
+    print(json.dumps(rec), flush=True)
+    if not a.no_record:
+        os.makedirs(a.out, exist_ok=True)
+        stem = os.path.join(a.out, f"r10_ensemble_{a.tag if a.tag != 'bench' else 'fork'}")
+        with open(stem + ".json", "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        write_fork_md(rec, stem + ".md")
+
+
+def write_fork_md(rec: dict, path: str):
+    head = ""
+    if os.path.exists(path):
+        head = open(path).read().split(MD_MARK)[0]
+    w = rec["workload"]
+    out = [MD_MARK + f" (`tools/ensemble_bench.py --fork`, {os.path.basename(path)[:-3]}.json)", "",
+           f"Source: {w['size']}² `{w['soil']}`, {w['nwater']} + {w['nwind']} particles, seed {w['seed']}, {w['pool_sections_per_cell']} pool sections per cell, {w['state']} "
+           f"({w['sections']} sections, deepest column {w['deepest_column']}). Parent path: {w['parent_path']}. Times: {w['clock']} of {w['calls']} calls. Checked {w['checked']}.", "",
+           "| B | `fork` ms (min, max) | parent path ms (min, max) | speed-up | bytes the fork must move | fork GB/s (whole call) |",
+           "|---:|---:|---:|---:|---:|---:|"]
+    for r in rec["fork"]:
+        out.append(f"| {r['members']} | {r['fork_ms']:.2f} ({r['fork_ms_min']:.2f}, {r['fork_ms_max']:.2f}) | {r['parent_path_ms']:.1f} ({r['parent_path_ms_min']:.1f}, {r['parent_path_ms_max']:.1f}) | "
+                   f"{r['speedup']:.1f} × | {r['algorithmic_bytes']['total'] / 1e6:.1f} MB | {r['fork_gb_per_s']:.1f} |")
+    g = rec.get("fork_4096")
+    if g:
+        out += ["", f"{g['size']}² `{g['soil']}` after {g['ticks']} relaxed ticks ({g['nwater']} + {g['nwind']} particles, pool {g['pool_sections']} sections, {g['algorithmic_bytes']['sections']} live), "
+                    f"forked into {g['members']} members with the source's pool size: {g['fork_ms']:.1f} ms ({g['fork_ms_min']:.1f}, {g['fork_ms_max']:.1f}) for {g['algorithmic_bytes']['total'] / 1e9:.2f} GB "
+                    f"= {g['fork_gb_per_s']:.0f} GB/s over the whole call; parent path: {g['parent_path_ms']}."]
+    k = rec.get("k_fork_scatter")
+    if isinstance(k, dict):
+        ks = k["kernels"]
+        out += ["", f"`k_fork_scatter` alone ({k['source']}): {ks['k_fork_scatter']['total_ns'] / 1e3:.1f} µs for {k['scatter_bytes'] / 1e6:.1f} MB = {k['gb_per_s']:.0f} GB/s, "
+                    f"{100 * k['share_of_stream_rate']:.1f} % of the {w['stream_rate_tb_s']} TB/s measured for `k_map_frequency`"
+                    + "".join(f"; `{n}` {v['total_ns'] / 1e3:.1f} µs" for n, v in ks.items() if n != "k_fork_scatter") + "."]
+    else:
+        out += ["", "`k_fork_scatter`'s own rate: not measured."]
+    with open(path, "w") as f:
+        f.write(head + "\n".join(out) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fork", action="store_true", help="time smx_ensemble_fork against snapshot + per-member add / load")
+    ap.add_argument("--no-big", action="store_true", help="--fork: leave the 4096^2 line out")
+    ap.add_argument("--scatter-stats", default=None, metavar="CSV", help="--fork: a rocprofv3 kernel-stats CSV of an SMX_FORK_PROFILE_ONLY run")
+    ap.add_argument("--scatter-members", type=int, default=256, help="--fork: the B of that run")
     ap.add_argument("--observe", action="store_true", help="time smx_ensemble_figures / _plane_stats against the per-member path")
     ap.add_argument("--calls", type=int, default=10, help="--observe: timed calls per figure (after 2 warm-up calls)")
     ap.add_argument("--batches", default="1,8,64,256,1024")
@@ -289,6 +524,12 @@ def main():
     ap.add_argument("--no-ref", action="store_true")
     ap.add_argument("--no-standalone", action="store_true")
     a = ap.parse_args()
+    if a.fork:
+        if a.batches == "1,8,64,256,1024":
+            a.batches = "8,64,256,1024"
+        if a.calls == 10:
+            a.calls = 5
+        return main_fork(a)
     if a.observe:
         return main_observe(a)
     cfg = loadsoil(os.path.join(ROOT, "soilmachine_amd", "soils", SOIL))
