@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include "soil_devmem.h"
 
 namespace smx {
 constexpr int LQ = 19;
@@ -197,6 +198,7 @@ struct smx_lbm {
   smx::LbmConsts k{};
   int device = 0;
   hipStream_t stream = nullptr;
+  DevMem mem;                                                 // owns the lattices and the staging of smx_lbm_write_f / smx_lbm_move
   float *f[2] = {nullptr, nullptr}, *B = nullptr, *rho = nullptr;
   float4* v = nullptr;
   int cur = 0;                                                // which lattice holds F

@@ -21,6 +21,7 @@ static_assert(sizeof(XBundle) == 32, "seam message header");
 struct StripTransport {
   int rank = 0, world = 1;
   uint64_t bytes_sent = 0, messages = 0;
+  DevMem mem;                                                 // owns the transport's staging buffers
   uint64_t host_syncs = 0, groups = 0;                        // stream synchronisations the transport itself asked for; ncclGroupStart/End pairs (smx_strips_sync_stats)
   virtual ~StripTransport() {}
   // ONE seam exchange of this rank: `out` goes to send_peer, `in` comes from recv_peer (-1: this rank has no such neighbour). Default -- blocking host
@@ -59,10 +60,10 @@ struct RcclApi {
   }
 };
 static RcclApi g_rccl;
-#define NCCLCHK(call)                                                                                \
+#define NCCLCHK(obj, call)                                                                           \
   do {                                                                                               \
     ncclResult_t r_ = (call);                                                                        \
-    if (r_ != ncclSuccess) { ctx->err = std::string(#call) + ": " + g_rccl.GetErrorString(r_); return -1; } \
+    if (r_ != ncclSuccess) { (obj)->err = std::string(#call) + ": " + g_rccl.GetErrorString(r_); return -1; } \
   } while (0)
 
 struct RcclTransport : StripTransport {
@@ -73,33 +74,33 @@ struct RcclTransport : StripTransport {
   XBundle* h_hdr = nullptr; uint32_t hdr_slot = 0;            // pinned ring of outgoing headers: the async copy reads its slot when the stream gets there,
   static constexpr uint32_t HDR_RING = 64;                    // long after send_bundle's caller has dropped its own (stack) header; every chunk synchronises
                                                               // the stream at least once (recv_bundle, the live-count all-reduce), so at most a few slots are in flight
-  ~RcclTransport() override { if (comm) g_rccl.CommDestroy(comm); hipFree(d_hdr); hipFree(d_coll); hipFree(d_gather); hipFree(d_mine); if (h_hdr) hipHostFree(h_hdr); }
+  ~RcclTransport() override { if (comm) g_rccl.CommDestroy(comm); }
   int send_bundle(smx_ctx* ctx, int peer, const XBundle& b) override {
     hipStream_t st = ctx->stream;
-    if (!h_hdr) HIPCHK(hipHostMalloc(&h_hdr, HDR_RING * sizeof(XBundle)));
+    if (!h_hdr) HIPCHK(ctx, mem.pinned(h_hdr, HDR_RING));
     XBundle* slot = &h_hdr[hdr_slot++ % HDR_RING];
     *slot = b;
-    HIPCHK(hipMemcpyAsync(&d_hdr[0], slot, sizeof(b), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(&d_hdr[0], slot, sizeof(b), hipMemcpyHostToDevice, st));
     // same shape on both sides: the header as an operation of its own (the receiver needs it before it can post the rest),
     // then ONE group with the payloads -- point-to-point operations between two ranks pair up in the order they were issued
-    NCCLCHK(g_rccl.Send(&d_hdr[0], sizeof(XBundle), ncclUint8, peer, comm, st));
-    NCCLCHK(g_rccl.GroupStart());
-    if (b.nrec) { NCCLCHK(g_rccl.Send(ctx->d_xoffs, 4ull * b.nrec, ncclUint8, peer, comm, st)); NCCLCHK(g_rccl.Send(ctx->d_xdata, b.nbytes, ncclUint8, peer, comm, st)); }
-    if (b.npart) NCCLCHK(g_rccl.Send(ctx->d_xpart, (size_t)b.npart * b.rs, ncclUint8, peer, comm, st));
-    NCCLCHK(g_rccl.GroupEnd());
+    NCCLCHK(ctx, g_rccl.Send(&d_hdr[0], sizeof(XBundle), ncclUint8, peer, comm, st));
+    NCCLCHK(ctx, g_rccl.GroupStart());
+    if (b.nrec) { NCCLCHK(ctx, g_rccl.Send(ctx->d_xoffs, 4ull * b.nrec, ncclUint8, peer, comm, st)); NCCLCHK(ctx, g_rccl.Send(ctx->d_xdata, b.nbytes, ncclUint8, peer, comm, st)); }
+    if (b.npart) NCCLCHK(ctx, g_rccl.Send(ctx->d_xpart, (size_t)b.npart * b.rs, ncclUint8, peer, comm, st));
+    NCCLCHK(ctx, g_rccl.GroupEnd());
     bytes_sent += sizeof(XBundle) + 4ull * b.nrec + b.nbytes + (uint64_t)b.npart * b.rs; messages++;
     return 0;
   }
   int recv_bundle(smx_ctx* ctx, int peer, XBundle& b) override {
     hipStream_t st = ctx->stream;
-    NCCLCHK(g_rccl.Recv(&d_hdr[1], sizeof(XBundle), ncclUint8, peer, comm, st));
-    HIPCHK(hipMemcpyAsync(&b, &d_hdr[1], sizeof(b), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st)); host_syncs++;           // the payload sizes decide the receives that follow
+    NCCLCHK(ctx, g_rccl.Recv(&d_hdr[1], sizeof(XBundle), ncclUint8, peer, comm, st));
+    HIPCHK(ctx, hipMemcpyAsync(&b, &d_hdr[1], sizeof(b), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st)); host_syncs++;           // the payload sizes decide the receives that follow
     if (b.nrec > ctx->xoffs_cap || b.nbytes > ctx->xdata_cap || (uint64_t)b.npart * b.rs > ctx->xpart_cap) { ctx->err = "strips: incoming seam message exceeds the exchange buffers"; return -2; }
-    NCCLCHK(g_rccl.GroupStart());
-    if (b.nrec) { NCCLCHK(g_rccl.Recv(ctx->d_roffs, 4ull * b.nrec, ncclUint8, peer, comm, st)); NCCLCHK(g_rccl.Recv(ctx->d_rdata, b.nbytes, ncclUint8, peer, comm, st)); }
-    if (b.npart) NCCLCHK(g_rccl.Recv(ctx->d_rpart, (size_t)b.npart * b.rs, ncclUint8, peer, comm, st));
-    NCCLCHK(g_rccl.GroupEnd());
+    NCCLCHK(ctx, g_rccl.GroupStart());
+    if (b.nrec) { NCCLCHK(ctx, g_rccl.Recv(ctx->d_roffs, 4ull * b.nrec, ncclUint8, peer, comm, st)); NCCLCHK(ctx, g_rccl.Recv(ctx->d_rdata, b.nbytes, ncclUint8, peer, comm, st)); }
+    if (b.npart) NCCLCHK(ctx, g_rccl.Recv(ctx->d_rpart, (size_t)b.npart * b.rs, ncclUint8, peer, comm, st));
+    NCCLCHK(ctx, g_rccl.GroupEnd());
     return 0;
   }
   // Both directions of a seam exchange in TWO grouped operations (round 6): {header out, header in}, one stream synchronisation
@@ -109,37 +110,37 @@ struct RcclTransport : StripTransport {
   int exchange(smx_ctx* ctx, int send_peer, const XBundle* out, int recv_peer, XBundle* in) override {
     hipStream_t st = ctx->stream;
     if (send_peer < 0 && recv_peer < 0) return 0;
-    if (!h_hdr) HIPCHK(hipHostMalloc(&h_hdr, HDR_RING * sizeof(XBundle)));
+    if (!h_hdr) HIPCHK(ctx, mem.pinned(h_hdr, HDR_RING));
     XBundle* hin = &h_hdr[hdr_slot++ % HDR_RING];
     if (send_peer >= 0) {
       XBundle* slot = &h_hdr[hdr_slot++ % HDR_RING];
       *slot = *out;
-      HIPCHK(hipMemcpyAsync(&d_hdr[0], slot, sizeof(XBundle), hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, hipMemcpyAsync(&d_hdr[0], slot, sizeof(XBundle), hipMemcpyHostToDevice, st));
     }
-    NCCLCHK(g_rccl.GroupStart());
-    if (send_peer >= 0) NCCLCHK(g_rccl.Send(&d_hdr[0], sizeof(XBundle), ncclUint8, send_peer, comm, st));
-    if (recv_peer >= 0) NCCLCHK(g_rccl.Recv(&d_hdr[1], sizeof(XBundle), ncclUint8, recv_peer, comm, st));
-    NCCLCHK(g_rccl.GroupEnd());
+    NCCLCHK(ctx, g_rccl.GroupStart());
+    if (send_peer >= 0) NCCLCHK(ctx, g_rccl.Send(&d_hdr[0], sizeof(XBundle), ncclUint8, send_peer, comm, st));
+    if (recv_peer >= 0) NCCLCHK(ctx, g_rccl.Recv(&d_hdr[1], sizeof(XBundle), ncclUint8, recv_peer, comm, st));
+    NCCLCHK(ctx, g_rccl.GroupEnd());
     groups++;
     XBundle bi;
     if (recv_peer >= 0) {
-      HIPCHK(hipMemcpyAsync(hin, &d_hdr[1], sizeof(XBundle), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st)); host_syncs++;        // the payload sizes decide the receives that follow
+      HIPCHK(ctx, hipMemcpyAsync(hin, &d_hdr[1], sizeof(XBundle), hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st)); host_syncs++;        // the payload sizes decide the receives that follow
       bi = *hin; *in = bi;
       if (bi.nrec > ctx->xoffs_cap || bi.nbytes > ctx->xdata_cap || (uint64_t)bi.npart * bi.rs > ctx->xpart_cap) { ctx->err = "strips: incoming seam message exceeds the exchange buffers"; return -2; }
     }
     const bool so = send_peer >= 0 && (out->nrec || out->npart), si = recv_peer >= 0 && (bi.nrec || bi.npart);
     if (so || si) {
-      NCCLCHK(g_rccl.GroupStart());
+      NCCLCHK(ctx, g_rccl.GroupStart());
       if (so) {
-        if (out->nrec) { NCCLCHK(g_rccl.Send(ctx->d_xoffs, 4ull * out->nrec, ncclUint8, send_peer, comm, st)); NCCLCHK(g_rccl.Send(ctx->d_xdata, out->nbytes, ncclUint8, send_peer, comm, st)); }
-        if (out->npart) NCCLCHK(g_rccl.Send(ctx->d_xpart, (size_t)out->npart * out->rs, ncclUint8, send_peer, comm, st));
+        if (out->nrec) { NCCLCHK(ctx, g_rccl.Send(ctx->d_xoffs, 4ull * out->nrec, ncclUint8, send_peer, comm, st)); NCCLCHK(ctx, g_rccl.Send(ctx->d_xdata, out->nbytes, ncclUint8, send_peer, comm, st)); }
+        if (out->npart) NCCLCHK(ctx, g_rccl.Send(ctx->d_xpart, (size_t)out->npart * out->rs, ncclUint8, send_peer, comm, st));
       }
       if (si) {
-        if (bi.nrec) { NCCLCHK(g_rccl.Recv(ctx->d_roffs, 4ull * bi.nrec, ncclUint8, recv_peer, comm, st)); NCCLCHK(g_rccl.Recv(ctx->d_rdata, bi.nbytes, ncclUint8, recv_peer, comm, st)); }
-        if (bi.npart) NCCLCHK(g_rccl.Recv(ctx->d_rpart, (size_t)bi.npart * bi.rs, ncclUint8, recv_peer, comm, st));
+        if (bi.nrec) { NCCLCHK(ctx, g_rccl.Recv(ctx->d_roffs, 4ull * bi.nrec, ncclUint8, recv_peer, comm, st)); NCCLCHK(ctx, g_rccl.Recv(ctx->d_rdata, bi.nbytes, ncclUint8, recv_peer, comm, st)); }
+        if (bi.npart) NCCLCHK(ctx, g_rccl.Recv(ctx->d_rpart, (size_t)bi.npart * bi.rs, ncclUint8, recv_peer, comm, st));
       }
-      NCCLCHK(g_rccl.GroupEnd());
+      NCCLCHK(ctx, g_rccl.GroupEnd());
       groups++;
     }
     if (send_peer >= 0) { bytes_sent += sizeof(XBundle) + 4ull * out->nrec + out->nbytes + (uint64_t)out->npart * out->rs; messages++; }
@@ -148,48 +149,43 @@ struct RcclTransport : StripTransport {
   int allreduce_sum(smx_ctx* ctx, uint64_t& v) override {
     hipStream_t st = ctx->stream;
     unsigned long long h = v;
-    HIPCHK(hipMemcpyAsync(d_coll, &h, 8, hipMemcpyHostToDevice, st));
-    NCCLCHK(g_rccl.AllReduce(d_coll, d_coll + 1, 1, ncclUint64, ncclSum, comm, st));
-    HIPCHK(hipMemcpyAsync(&h, d_coll + 1, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st)); host_syncs++;
+    HIPCHK(ctx, hipMemcpyAsync(d_coll, &h, 8, hipMemcpyHostToDevice, st));
+    NCCLCHK(ctx, g_rccl.AllReduce(d_coll, d_coll + 1, 1, ncclUint64, ncclSum, comm, st));
+    HIPCHK(ctx, hipMemcpyAsync(&h, d_coll + 1, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st)); host_syncs++;
     v = h;
     return 0;
   }
-  int ensure(smx_ctx* ctx, void*& p, size_t& cap, size_t need) {
-    if (cap >= need) return 0;
-    hipFree(p); p = nullptr; cap = 0;
-    HIPCHK(hipMalloc(&p, need)); cap = need;
-    return 0;
-  }
+  int ensure(smx_ctx* ctx, void*& p, size_t& cap, size_t need) { HIPCHK(ctx, mem.grow(p, cap, need, need)); return 0; }
   int allreduce_min_u32(smx_ctx* ctx, uint32_t* a, size_t n) override {
     if (n == 0) return 0;
     hipStream_t st = ctx->stream;
     if (ensure(ctx, d_mine, mine_cap, n * 4)) return -1;
-    HIPCHK(hipMemcpyAsync(d_mine, a, n * 4, hipMemcpyHostToDevice, st));
-    NCCLCHK(g_rccl.AllReduce(d_mine, d_mine, n, ncclUint32, ncclMin, comm, st));
-    HIPCHK(hipMemcpyAsync(a, d_mine, n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(d_mine, a, n * 4, hipMemcpyHostToDevice, st));
+    NCCLCHK(ctx, g_rccl.AllReduce(d_mine, d_mine, n, ncclUint32, ncclMin, comm, st));
+    HIPCHK(ctx, hipMemcpyAsync(a, d_mine, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
   }
   int allgather_children(smx_ctx* ctx, const BChild* mine, uint32_t n, std::vector<BChild>& all) override {
     hipStream_t st = ctx->stream;
     std::vector<unsigned long long> cnt((size_t)world, 0ull);
     unsigned long long h = n;
-    HIPCHK(hipMemcpyAsync(d_coll, &h, 8, hipMemcpyHostToDevice, st));
-    NCCLCHK(g_rccl.AllGather(d_coll, d_coll + 8, 1, ncclUint64, comm, st));
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_coll + 8, 8ull * world, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(d_coll, &h, 8, hipMemcpyHostToDevice, st));
+    NCCLCHK(ctx, g_rccl.AllGather(d_coll, d_coll + 8, 1, ncclUint64, comm, st));
+    HIPCHK(ctx, hipMemcpyAsync(cnt.data(), d_coll + 8, 8ull * world, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     unsigned long long mx = 0, tot = 0;
     for (unsigned long long c : cnt) { mx = std::max(mx, c); tot += c; }
     all.clear();
     if (tot == 0) return 0;
     const size_t each = (size_t)mx * sizeof(BChild);          // every rank contributes a block padded to the longest list
     if (ensure(ctx, d_mine, mine_cap, each) || ensure(ctx, d_gather, gather_cap, each * world)) return -1;
-    if (n) HIPCHK(hipMemcpyAsync(d_mine, mine, (size_t)n * sizeof(BChild), hipMemcpyHostToDevice, st));
-    NCCLCHK(g_rccl.AllGather(d_mine, d_gather, each, ncclUint8, comm, st));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(d_mine, mine, (size_t)n * sizeof(BChild), hipMemcpyHostToDevice, st));
+    NCCLCHK(ctx, g_rccl.AllGather(d_mine, d_gather, each, ncclUint8, comm, st));
     std::vector<BChild> buf((size_t)mx * world);
-    HIPCHK(hipMemcpyAsync(buf.data(), d_gather, each * world, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(buf.data(), d_gather, each * world, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     all.reserve(tot);
     for (int r = 0; r < world; r++) all.insert(all.end(), buf.begin() + (size_t)r * mx, buf.begin() + (size_t)r * mx + cnt[r]);
     return 0;
@@ -200,24 +196,17 @@ struct RcclTransport : StripTransport {
 struct HostTransport : StripTransport {
   smx_transport t{};
   uint8_t* h_buf = nullptr; uint64_t h_cap = 0;               // pinned staging of one message
-  ~HostTransport() override { if (h_buf) hipHostFree(h_buf); }
-  int stage(smx_ctx* ctx, uint64_t need) {
-    if (h_cap >= need) return 0;
-    if (h_buf) hipHostFree(h_buf);
-    h_buf = nullptr; h_cap = 0;
-    HIPCHK(hipHostMalloc(&h_buf, need)); h_cap = need;
-    return 0;
-  }
+  int stage(smx_ctx* ctx, uint64_t need) { HIPCHK(ctx, mem.grow(h_buf, h_cap, need, need, true)); return 0; }
   int send_bundle(smx_ctx* ctx, int peer, const XBundle& b) override {
     hipStream_t st = ctx->stream;
     const uint64_t total = sizeof(XBundle) + 4ull * b.nrec + b.nbytes + (uint64_t)b.npart * b.rs;
     if (stage(ctx, total)) return -1;
     memcpy(h_buf, &b, sizeof(b));
     uint64_t o = sizeof(XBundle);
-    if (b.nrec) { HIPCHK(hipMemcpyAsync(h_buf + o, ctx->d_xoffs, 4ull * b.nrec, hipMemcpyDeviceToHost, st)); o += 4ull * b.nrec;
-                  HIPCHK(hipMemcpyAsync(h_buf + o, ctx->d_xdata, b.nbytes, hipMemcpyDeviceToHost, st)); o += b.nbytes; }
-    if (b.npart) HIPCHK(hipMemcpyAsync(h_buf + o, ctx->d_xpart, (size_t)b.npart * b.rs, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (b.nrec) { HIPCHK(ctx, hipMemcpyAsync(h_buf + o, ctx->d_xoffs, 4ull * b.nrec, hipMemcpyDeviceToHost, st)); o += 4ull * b.nrec;
+                  HIPCHK(ctx, hipMemcpyAsync(h_buf + o, ctx->d_xdata, b.nbytes, hipMemcpyDeviceToHost, st)); o += b.nbytes; }
+    if (b.npart) HIPCHK(ctx, hipMemcpyAsync(h_buf + o, ctx->d_xpart, (size_t)b.npart * b.rs, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     if (t.send(t.user, peer, h_buf, total) != 0) { ctx->err = "strips: transport send failed"; return -1; }
     bytes_sent += total; messages++;
     return 0;
@@ -237,10 +226,10 @@ struct HostTransport : StripTransport {
     const uint64_t total = sizeof(XBundle) + 4ull * b.nrec + b.nbytes + (uint64_t)b.npart * b.rs;
     if (total != got || b.nrec > ctx->xoffs_cap || b.nbytes > ctx->xdata_cap || (uint64_t)b.npart * b.rs > ctx->xpart_cap) { ctx->err = "strips: malformed seam message"; return -2; }
     uint64_t o = sizeof(XBundle);
-    if (b.nrec) { HIPCHK(hipMemcpyAsync(ctx->d_roffs, h_buf + o, 4ull * b.nrec, hipMemcpyHostToDevice, st)); o += 4ull * b.nrec;
-                  HIPCHK(hipMemcpyAsync(ctx->d_rdata, h_buf + o, b.nbytes, hipMemcpyHostToDevice, st)); o += b.nbytes; }
-    if (b.npart) HIPCHK(hipMemcpyAsync(ctx->d_rpart, h_buf + o, (size_t)b.npart * b.rs, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));                         // (the staging buffer is reused by the next message)
+    if (b.nrec) { HIPCHK(ctx, hipMemcpyAsync(ctx->d_roffs, h_buf + o, 4ull * b.nrec, hipMemcpyHostToDevice, st)); o += 4ull * b.nrec;
+                  HIPCHK(ctx, hipMemcpyAsync(ctx->d_rdata, h_buf + o, b.nbytes, hipMemcpyHostToDevice, st)); o += b.nbytes; }
+    if (b.npart) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rpart, h_buf + o, (size_t)b.npart * b.rs, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));                         // (the staging buffer is reused by the next message)
     return 0;
   }
   int allreduce_sum(smx_ctx* ctx, uint64_t& v) override { if (t.allreduce_sum_u64(t.user, &v) != 0) { ctx->err = "strips: transport allreduce failed"; return -1; } return 0; }
@@ -272,12 +261,12 @@ struct StripState {
 static int xbuf_alloc_strips(smx_ctx* ctx) {                  // exchange buffers of both directions + the particle regions
   if (xbuf_alloc(ctx)) return -1;
   if (!ctx->d_rdata) {
-    HIPCHK(hipMalloc(&ctx->d_rdata, ctx->xdata_cap)); HIPCHK(hipMalloc(&ctx->d_roffs, (size_t)ctx->xoffs_cap * 4));
+    HIPCHK(ctx, ctx->mem.dev(ctx->d_rdata, ctx->xdata_cap)); HIPCHK(ctx, ctx->mem.dev(ctx->d_roffs, ctx->xoffs_cap));
   }
   const uint64_t need = (uint64_t)std::max<uint32_t>(ctx->batch_cap, 4096u) * (4 + std::max(sizeof(BWater), sizeof(BWind)));
   if (ctx->xpart_cap < need) {
-    hipFree(ctx->d_xpart); hipFree(ctx->d_rpart); ctx->d_xpart = ctx->d_rpart = nullptr; ctx->xpart_cap = 0;
-    HIPCHK(hipMalloc(&ctx->d_xpart, need)); HIPCHK(hipMalloc(&ctx->d_rpart, need)); ctx->xpart_cap = need;
+    ctx->mem.drop(ctx->d_xpart); ctx->mem.drop(ctx->d_rpart); ctx->xpart_cap = 0;
+    HIPCHK(ctx, ctx->mem.dev(ctx->d_xpart, need)); HIPCHK(ctx, ctx->mem.dev(ctx->d_rpart, need)); ctx->xpart_cap = need;
   }
   return 0;
 }
@@ -291,15 +280,15 @@ static int st_pack_band(smx_ctx* ctx, StripState& S, int cx0, int cx1, int px0, 
   const int gx0 = cx0 >> 2, gx1 = (cx1 + 3) >> 2, gty = (ctx->cfg.dimy + 3) >> 2;
   const long long nt = (long long)(gx1 - gx0) * gty;
   XCursor c[2] = {};
-  HIPCHK(hipMemsetAsync(ctx->d_xcur, 0, 2 * sizeof(XCursor), st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_xcur, 0, 2 * sizeof(XCursor), st));
   if (nt > 0) hipLaunchKernelGGL(k_strip_pack_columns, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, st, ctx->d, ctx->bs, gx0, gx1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xoffs, ctx->xoffs_cap, ctx->d_xcur);
   const bool parts = particles && ctx->d_nslots;
   if (parts) {
     const uint32_t nslots = ctx->d_nslots;
     LAUNCH_WIND_WATER(ctx->d_wind, k_strip_pack_particles, dim3((nslots + 255u) / 256u), dim3(256), st, ctx->bs, nslots, px0, px1, ctx->d_xpart, ctx->xpart_cap, ctx->d_xcur + 1);
   }
-  HIPCHK(hipMemcpyAsync(c, ctx->d_xcur, 2 * sizeof(XCursor), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st)); S.T->host_syncs++;
+  HIPCHK(ctx, hipMemcpyAsync(c, ctx->d_xcur, 2 * sizeof(XCursor), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st)); S.T->host_syncs++;
   if (c[0].lost) { ctx->err = "strips: exchange buffer too small for the halo columns"; return -2; }
   if (c[1].lost) { ctx->err = "strips: exchange buffer too small for the migrating particles"; return -2; }
   b.nrec = c[0].nrec; b.nbytes = (uint32_t)c[0].bytes;
@@ -318,7 +307,7 @@ static int st_unpack_band(smx_ctx* ctx, const XBundle& b) {
     if (b.rs != 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater))) { ctx->err = "strips: particle records of the wrong phase"; return -2; }
     LAUNCH_WIND_WATER(ctx->d_wind, k_strip_unpack_particles, dim3((b.npart + 255u) / 256u), dim3(256), st, ctx->bs, ctx->d_rpart, b.npart);
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 // one seam exchange: what this rank packs goes to `send_peer`, what `recv_peer` packed comes in and is unpacked (StripTransport::exchange)
@@ -426,11 +415,11 @@ int smx_strips_rccl_unique_id(void* out128) {
 int smx_strips_attach_rccl(smx_ctx* ctx, const void* unique_id128, int32_t rank, int32_t world, int32_t inset, int32_t seam_halfwidth) {
   if (!unique_id128 || rank < 0 || rank >= world || world < 1 || world > 8) { ctx->err = "smx_strips_attach_rccl: 1..8 ranks"; return -2; }
   if (!g_rccl.load(ctx->err)) return -3;
-  HIPCHK(hipSetDevice(ctx->cfg.device));
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
   RcclTransport* T = new RcclTransport();
   ncclUniqueId id; memcpy(&id, unique_id128, 128);
   { ncclResult_t r_ = g_rccl.CommInitRank(&T->comm, world, id, rank); if (r_ != ncclSuccess) { ctx->err = std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r_); delete T; return -1; } }
-  if (hipMalloc(&T->d_hdr, 2 * sizeof(XBundle)) != hipSuccess || hipMalloc(&T->d_coll, 64 * 8) != hipSuccess) { ctx->err = "smx_strips_attach_rccl: out of device memory"; delete T; return -1; }
+  if (T->mem.dev(T->d_hdr, 2) != hipSuccess || T->mem.dev(T->d_coll, 64) != hipSuccess) { ctx->err = "smx_strips_attach_rccl: out of device memory"; delete T; return -1; }
   return strips_attach_common(ctx, T, rank, world, inset, seam_halfwidth);
 }
 int smx_strips_attach(smx_ctx* ctx, const smx_transport* t, int32_t rank, int32_t world, int32_t inset, int32_t seam_halfwidth) {
@@ -492,18 +481,18 @@ int smx_strips_selfcheck(smx_ctx* ctx, uint32_t nrec, uint32_t nbytes, uint32_t 
   uint32_t x = 0x9e3779b9u ^ (nrec * 31u + nbytes * 7u + npart);
   auto nxt = [&x]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
   for (auto& v : offs) v = nxt(); for (auto& v : data) v = (uint8_t)nxt(); for (auto& v : part) v = (uint8_t)nxt();
-  if (nrec) HIPCHK(hipMemcpyAsync(ctx->d_xoffs, offs.data(), 4ull * nrec, hipMemcpyHostToDevice, st));
-  if (nbytes) HIPCHK(hipMemcpyAsync(ctx->d_xdata, data.data(), nbytes, hipMemcpyHostToDevice, st));
-  if (npart) HIPCHK(hipMemcpyAsync(ctx->d_xpart, part.data(), part.size(), hipMemcpyHostToDevice, st));
-  if (nrec) HIPCHK(hipMemsetAsync(ctx->d_roffs, 0, 4ull * nrec, st)); if (nbytes) HIPCHK(hipMemsetAsync(ctx->d_rdata, 0, nbytes, st)); if (npart) HIPCHK(hipMemsetAsync(ctx->d_rpart, 0, part.size(), st));
+  if (nrec) HIPCHK(ctx, hipMemcpyAsync(ctx->d_xoffs, offs.data(), 4ull * nrec, hipMemcpyHostToDevice, st));
+  if (nbytes) HIPCHK(ctx, hipMemcpyAsync(ctx->d_xdata, data.data(), nbytes, hipMemcpyHostToDevice, st));
+  if (npart) HIPCHK(ctx, hipMemcpyAsync(ctx->d_xpart, part.data(), part.size(), hipMemcpyHostToDevice, st));
+  if (nrec) HIPCHK(ctx, hipMemsetAsync(ctx->d_roffs, 0, 4ull * nrec, st)); if (nbytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_rdata, 0, nbytes, st)); if (npart) HIPCHK(ctx, hipMemsetAsync(ctx->d_rpart, 0, part.size(), st));
   XBundle out, in; out.nrec = nrec; out.nbytes = nbytes; out.npart = npart; out.rs = rs; out.pad[0] = 0x5e1fc4ecu;
   if (T->exchange(ctx, T->rank, &out, T->rank, &in)) return -1;
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   if (memcmp(&in, &out, sizeof(XBundle)) != 0) { ctx->err = "smx_strips_selfcheck: the header came back changed"; return -4; }
   std::vector<uint32_t> roffs(nrec); std::vector<uint8_t> rdata(nbytes), rpart(part.size());
-  if (nrec) HIPCHK(hipMemcpy(roffs.data(), ctx->d_roffs, 4ull * nrec, hipMemcpyDeviceToHost));
-  if (nbytes) HIPCHK(hipMemcpy(rdata.data(), ctx->d_rdata, nbytes, hipMemcpyDeviceToHost));
-  if (npart) HIPCHK(hipMemcpy(rpart.data(), ctx->d_rpart, part.size(), hipMemcpyDeviceToHost));
+  if (nrec) HIPCHK(ctx, hipMemcpy(roffs.data(), ctx->d_roffs, 4ull * nrec, hipMemcpyDeviceToHost));
+  if (nbytes) HIPCHK(ctx, hipMemcpy(rdata.data(), ctx->d_rdata, nbytes, hipMemcpyDeviceToHost));
+  if (npart) HIPCHK(ctx, hipMemcpy(rpart.data(), ctx->d_rpart, part.size(), hipMemcpyDeviceToHost));
   if (roffs != offs || rdata != data || rpart != part) { ctx->err = "smx_strips_selfcheck: a payload came back changed"; return -4; }
   return 0;
 }

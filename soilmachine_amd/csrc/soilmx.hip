@@ -40,6 +40,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_noise.h"
 #include "soil_batch.h"
 #include "soil_relax.h"
+#include "soil_devmem.h"
 #include "soil_lbm.h"
 #include "soil_observe.h"
 #include "soil_fork.h"
@@ -1437,6 +1438,7 @@ struct ForkScratch {
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
+  DevMem mem;                         // owns every device and pinned buffer below, the views' included (soil_devmem.h); smx_destroy lists none of them
   bool own_stream = true;             // false: the stream is an ensemble's (smx_ensemble_add), which destroys it
   smx_ensemble* ensemble = nullptr;   // the ensemble that owns this context (smx_destroy refuses it), or null
   std::string err;
@@ -1492,11 +1494,12 @@ struct smx_ctx : EventTimer {
   ForkScratch fork;                   // smx_copy_state into this context
 };
 
-#define HIPCHK(call)                                                                                  \
+// a failed HIP call: its text and the runtime's message go to the `err` of `obj` (a context, an ensemble, a lattice), the function returns -1
+#define HIPCHK(obj, call)                                                                             \
   do {                                                                                                \
     hipError_t e_ = (call);                                                                           \
     if (e_ != hipSuccess) {                                                                           \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                                   \
+      (obj)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                 \
       return -1;                                                                                      \
     }                                                                                                 \
   } while (0)
@@ -1546,10 +1549,10 @@ static int reset_pool(smx_ctx* ctx) {
   const uint64_t cap = ctx->cfg.pool_capacity;
   std::vector<uint32_t> fl(cap);
   for (uint64_t i = 0; i < cap; i++) fl[i] = (uint32_t)(cap - 1 - i);
-  HIPCHK(hipMemcpyAsync(ctx->d.freelist, fl.data(), cap * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.freelist, fl.data(), cap * 4, hipMemcpyHostToDevice, ctx->stream));
   uint32_t fc = (uint32_t)cap;
-  HIPCHK(hipMemcpyAsync(ctx->d.free_count, &fc, 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.free_count, &fc, 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
@@ -1567,9 +1570,9 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t s
   *out = ctx;   // handed out even on failure so the caller can read smx_last_error(); smx_destroy() is safe
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { ctx->err = "no HIP device visible (the soilmx product path has no CPU fallback)"; return -3; }
-  HIPCHK(hipSetDevice(cfg->device));
+  HIPCHK(ctx, hipSetDevice(cfg->device));
   if (stream) { ctx->stream = stream; ctx->own_stream = false; }
-  else HIPCHK(hipStreamCreate(&ctx->stream));
+  else HIPCHK(ctx, hipStreamCreate(&ctx->stream));
   hipDeviceSetLimit(hipLimitStackSize, 16384);   // recursion depth of cascade<->nested particles is bounded by spill (water.h:34)
   const size_t n = (size_t)cfg->dimx * cfg->dimy;
   ctx->ncells = n;
@@ -1580,29 +1583,26 @@ static int create_range(const smx_config* cfg, int x_lo, int x_hi, hipStream_t s
   d.x_lo = x_lo; d.x_hi = x_hi;
   ctx->c_lo = (size_t)x_lo * cfg->dimy; ctx->c_hi = (size_t)x_hi * cfg->dimy; ctx->lcells = ctx->c_hi - ctx->c_lo;
   const size_t ln = ctx->lcells;
-  HIPCHK(hipMalloc(&ctx->cells_alloc, ln * sizeof(Sec)));
+  DevMem& m = ctx->mem;
+  HIPCHK(ctx, m.dev(ctx->cells_alloc, ln));
   d.cells = ctx->cells_alloc - ctx->c_lo;                     // global cell index, held range only (DevState::x_lo)
-  HIPCHK(hipMalloc(&d.pool, cfg->pool_capacity * sizeof(Sec)));
-  HIPCHK(hipMalloc(&d.freelist, cfg->pool_capacity * 4));
-  HIPCHK(hipMalloc(&d.free_count, 64));
-  HIPCHK(hipMalloc(&ctx->flags_alloc, ln + 8));   // (whole 32-bit words: SerialPolicy::set_flag; c_lo is a multiple of 4 or the context holds everything)
+  HIPCHK(ctx, m.dev(d.pool, cfg->pool_capacity)); HIPCHK(ctx, m.dev(d.freelist, cfg->pool_capacity)); HIPCHK(ctx, m.dev(d.free_count, 16));
+  HIPCHK(ctx, m.dev(ctx->flags_alloc, ln + 8));   // (whole 32-bit words: SerialPolicy::set_flag; c_lo is a multiple of 4 or the context holds everything)
   d.flags = ctx->flags_alloc - ctx->c_lo;
-  HIPCHK(hipMalloc(&d.wfreq, n * 4)); HIPCHK(hipMalloc(&d.wtrack, n * 4)); HIPCHK(hipMalloc(&d.windfreq, n * 4));
-  HIPCHK(hipMalloc(&d.rnd, sizeof(RandState)));
-  HIPCHK(hipMalloc(&d.ctr, C_COUNT * 8));
-  HIPCHK(hipMalloc(&d.active, (ctx->nw0 + 64) * 8)); HIPCHK(hipMalloc(&d.active1, (ctx->nw1 + 64) * 8)); HIPCHK(hipMalloc(&d.active2, (ctx->nw2 + 64) * 8));
-  HIPCHK(hipMalloc(&ctx->d_scratch, 64));
-  HIPCHK(hipMalloc(&ctx->d_soils, 256 * sizeof(SoilP)));
+  HIPCHK(ctx, m.dev(d.wfreq, n)); HIPCHK(ctx, m.dev(d.wtrack, n)); HIPCHK(ctx, m.dev(d.windfreq, n));
+  HIPCHK(ctx, m.dev(d.rnd, 1)); HIPCHK(ctx, m.dev(d.ctr, C_COUNT));
+  HIPCHK(ctx, m.dev(d.active, ctx->nw0 + 64)); HIPCHK(ctx, m.dev(d.active1, ctx->nw1 + 64)); HIPCHK(ctx, m.dev(d.active2, ctx->nw2 + 64));
+  HIPCHK(ctx, m.dev(ctx->d_scratch, 8)); HIPCHK(ctx, m.dev(ctx->d_soils, 256));
   d.soils = ctx->d_soils;
-  HIPCHK(hipMemsetAsync(d.wfreq, 0, n * 4, ctx->stream)); HIPCHK(hipMemsetAsync(d.wtrack, 0, n * 4, ctx->stream));
-  HIPCHK(hipMemsetAsync(d.windfreq, 0, n * 4, ctx->stream));
-  HIPCHK(hipMemsetAsync(ctx->flags_alloc, 0, ln + 8, ctx->stream));
-  HIPCHK(hipMemsetAsync(d.ctr, 0, C_COUNT * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(d.wfreq, 0, n * 4, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(d.wtrack, 0, n * 4, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(d.windfreq, 0, n * 4, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->flags_alloc, 0, ln + 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(d.ctr, 0, C_COUNT * 8, ctx->stream));
   if (!bare) {   // all columns empty
     std::vector<Sec> empty(ln);
     for (size_t i = 0; i < ln; i++) { empty[i].size = 0; empty[i].floor = 0; empty[i].sat = 0; empty[i].type = EMPTY; empty[i].prev = NIL; }
-    HIPCHK(hipMemcpyAsync(ctx->cells_alloc, empty.data(), ln * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->cells_alloc, empty.data(), ln * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (!bare) {
     if (reset_pool(ctx)) return -1;
@@ -1642,7 +1642,6 @@ int smx_create_strip(const smx_config* cfg, int32_t x_lo, int32_t x_hi, smx_ctx*
   if (ctx->partial()) { ctx->err = what ": not available on a strip context (smx_create_strip): it holds only a part of the map"; return -2; }
 
 static void strips_free(smx_ctx* ctx);
-static void fork_free(ForkScratch& f);
 void smx_destroy(smx_ctx* ctx) {
   if (!ctx) return;
   if (ctx->ensemble) { ctx->err = "smx_destroy: this context is a member of an ensemble; smx_ensemble_destroy frees it (nothing was freed)"; return; }
@@ -1683,26 +1682,7 @@ void smx_destroy(smx_ctx* ctx) {
   }
   drain_events(ctx);
   for (hipEvent_t e : ctx->evpool) hipEventDestroy(e);
-  DevState& d = ctx->d;
-  hipFree(ctx->cells_alloc); hipFree(d.pool); hipFree(d.freelist); hipFree(d.free_count); hipFree(ctx->flags_alloc);
-  hipFree(d.wfreq); hipFree(d.wtrack); hipFree(d.windfreq); hipFree(d.rnd); hipFree(d.ctr);
-  hipFree(d.active); hipFree(d.active1); hipFree(d.active2); hipFree(ctx->d_scratch); hipFree(ctx->d_soils);
-  hipFree(ctx->d_vtx); hipFree(ctx->d_vcol); hipFree(ctx->d_plane);
-  fork_free(ctx->fork);
-  if (ctx->sh.stamp) {
-    SpecShared& sh = ctx->sh;
-    hipFree(sh.stamp); hipFree(sh.claim); hipFree(sh.ctrl); hipFree(sh.reclaim); hipHostFree(ctx->h_ctrl);
-    // (hipFree(nullptr) is a no-op: after a failed spec_alloc some of these are null)
-    hipFree(sh.part); hipFree(sh.chunk_tab); hipFree(sh.arena); hipFree(sh.alloc_log); hipFree(sh.free_log);
-    hipFree(sh.pending); hipFree(sh.draws); hipFree(sh.scout_cells); hipFree(sh.scout_len); hipFree(sh.ckpt);
-  }
-  {
-    BatchShared& bs = ctx->bs;
-    hipFree(bs.claim[0]); hipFree(bs.claim[1]); hipFree(bs.water); hipFree(bs.wind); hipFree(bs.live); hipFree(bs.children);
-    hipFree(bs.freed); hipFree(bs.ctrl); hipFree(bs.dirty); hipFree(bs.req); hipFree(bs.rnext); hipFree(bs.rcount); hipFree(ctx->rhead_alloc); hipFree(ctx->cflag_alloc); hipFree(ctx->cstate_alloc); hipFree(bs.flist[0]); hipFree(bs.flist[1]); hipFree(bs.clist[0]); hipFree(bs.clist[1]); hipFree(bs.flagl[0]); hipFree(bs.flagl[1]); hipFree(ctx->d_rdata); hipFree(ctx->d_roffs); hipFree(ctx->d_xpart); hipFree(ctx->d_rpart); hipFree(ctx->d_contains); hipFree(ctx->d_xdata); hipFree(ctx->d_xoffs); hipFree(ctx->d_xcur); hipFree(ctx->d_draws); hipFree(ctx->d_kids); hipFree(ctx->d_skeys[0]); hipFree(ctx->d_skeys[1]); hipFree(ctx->d_sidx[0]); hipFree(ctx->d_sidx[1]); hipFree(ctx->d_stemp); hipFree(ctx->d_vtx1); hipFree(ctx->d_tsort); hipFree(ctx->d_tdone); hipFree(ctx->d_tpend[0]); hipFree(ctx->d_tpend[1]); hipFree(ctx->d_tcount); hipFree(ctx->d_gbar); if (ctx->h_tcount) hipHostFree(ctx->h_tcount);
-    if (ctx->h_draws) hipHostFree(ctx->h_draws);
-    if (ctx->h_bctrl) hipHostFree(ctx->h_bctrl);
-  }
+  ctx->mem.clear();
   if (ctx->stream && ctx->own_stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -1713,8 +1693,8 @@ int smx_set_soils(smx_ctx* ctx, const smx_soil* soils, int32_t n) {
     if (soils[i].transports >= (uint32_t)n || soils[i].erodes >= (uint32_t)n || soils[i].cascades >= (uint32_t)n || soils[i].abrades >= (uint32_t)n) {
       ctx->err = "smx_set_soils: soil index out of range"; return -2;
     }
-  HIPCHK(hipMemcpyAsync(ctx->d_soils, soils, n * sizeof(SoilP), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_soils, soils, n * sizeof(SoilP), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->nsoils = n; ctx->d.nsoils = n;
   return 0;
 }
@@ -1789,41 +1769,41 @@ void* smx_stream(smx_ctx* ctx) { return (void*)ctx->stream; }
 int smx_srand(smx_ctx* ctx, uint32_t seed) {   // glibc srandom_r, TYPE_3 (stdlib/random_r.c)
   RandState r;
   rand_seed(r, seed);
-  HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 int smx_rand(smx_ctx* ctx, int32_t* out) {
   PointOp o{}; o.op = 5;
   hipLaunchKernelGGL(k_point_op, dim3(1), dim3(64), 0, ctx->stream, ctx->d, o, ctx->d_scratch);
   double v = 0;
-  HIPCHK(hipMemcpyAsync(&v, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&v, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *out = (int32_t)v;
   return 0;
 }
 
 int smx_get_rand_state(smx_ctx* ctx, uint32_t ring31[31], uint32_t* idx, uint64_t* calls) {
   RandState r;
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(ring31, r.ring, sizeof(r.ring)); if (idx) *idx = r.idx; if (calls) *calls = r.calls;
   return 0;
 }
 int smx_set_rand_state(smx_ctx* ctx, const uint32_t ring31[31], uint32_t idx, uint64_t calls) {
   RandState r; memcpy(r.ring, ring31, sizeof(r.ring)); r.idx = idx; r.calls = calls;
-  HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 int smx_rand_advance(smx_ctx* ctx, uint64_t ndraws) {
   RandState r;
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   rand_skip(r, ndraws);
   r.calls += ndraws;
-  HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
@@ -1837,7 +1817,7 @@ int smx_initialize(smx_ctx* ctx, int32_t seed, const smx_layer* layers, int32_t 
     return -4;
   }
   if (reset_pool(ctx)) return -1;
-  HIPCHK(hipMemsetAsync(ctx->d.ctr + C_LIVE_SECTIONS, 0, 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.ctr + C_LIVE_SECTIONS, 0, 8, ctx->stream));
   LayersDev L; L.n = nlayers;
   const int MAXSEED = 10000;
   for (int l = 0; l < nlayers; l++) {
@@ -1855,8 +1835,8 @@ int smx_initialize(smx_ctx* ctx, int32_t seed, const smx_layer* layers, int32_t 
   }
   const unsigned nb = (unsigned)((ctx->lcells + 255) / 256);
   hipLaunchKernelGGL(k_init_terrain, dim3(nb), dim3(256), 0, ctx->stream, ctx->d, L);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
@@ -1892,29 +1872,29 @@ int smx_import_columns(smx_ctx* ctx, const uint32_t* count, const uint32_t* type
   for (uint64_t i = cap; i-- > used;) fl[nf++] = (uint32_t)i;
   uint32_t fc = (uint32_t)nf;
   unsigned long long live = total;
-  HIPCHK(hipMemcpyAsync(ctx->cells_alloc, cells.data(), ln * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
-  if (used) HIPCHK(hipMemcpyAsync(ctx->d.pool, pool.data(), used * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d.freelist, fl.data(), cap * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d.free_count, &fc, 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->flags_alloc, flags.data(), ln, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d.ctr + C_LIVE_SECTIONS, &live, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cells_alloc, cells.data(), ln * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
+  if (used) HIPCHK(ctx, hipMemcpyAsync(ctx->d.pool, pool.data(), used * sizeof(Sec), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.freelist, fl.data(), cap * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.free_count, &fc, 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->flags_alloc, flags.data(), ln, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.ctr + C_LIVE_SECTIONS, &live, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int smx_import_frequency(smx_ctx* ctx, const float* wfreq, const float* wtrack, const float* windfreq) {
   const size_t n = ctx->ncells;
-  if (wfreq) HIPCHK(hipMemcpyAsync(ctx->d.wfreq, wfreq, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (wtrack) HIPCHK(hipMemcpyAsync(ctx->d.wtrack, wtrack, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (windfreq) HIPCHK(hipMemcpyAsync(ctx->d.windfreq, windfreq, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (wfreq) HIPCHK(ctx, hipMemcpyAsync(ctx->d.wfreq, wfreq, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (wtrack) HIPCHK(ctx, hipMemcpyAsync(ctx->d.wtrack, wtrack, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (windfreq) HIPCHK(ctx, hipMemcpyAsync(ctx->d.windfreq, windfreq, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int smx_num_sections(smx_ctx* ctx, uint64_t* out) {
   unsigned long long live = 0;
-  HIPCHK(hipMemcpyAsync(&live, ctx->d.ctr + C_LIVE_SECTIONS, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&live, ctx->d.ctr + C_LIVE_SECTIONS, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *out = live;
   return 0;
 }
@@ -1923,9 +1903,9 @@ int smx_export_columns(smx_ctx* ctx, uint32_t* count, uint32_t* type, double* si
   const size_t n = ctx->ncells, lo = ctx->c_lo, hi = ctx->c_hi, ln = ctx->lcells;   // (a strip context reports empty columns outside its range)
   const uint64_t cap = ctx->cfg.pool_capacity;
   std::vector<Sec> cells(ln), pool(cap);
-  HIPCHK(hipMemcpyAsync(cells.data(), ctx->cells_alloc, ln * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(pool.data(), ctx->d.pool, cap * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cells.data(), ctx->cells_alloc, ln * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(pool.data(), ctx->d.pool, cap * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   size_t off = 0;
   std::vector<const Sec*> col;
   for (size_t c = 0; c < n; c++) {
@@ -1964,11 +1944,11 @@ int smx_save(smx_ctx* ctx, const char* path) {
   // the per-column flag plane (bit1 = "this column has held a saturation", sticky): context state the column records do not
   // carry; the throughput engines fix the active set of their grid pass from it, so a resume without it can differ
   std::vector<uint8_t> fl(n);
-  HIPCHK(hipMemcpyAsync(fl.data(), ctx->d.flags, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(fl.data(), ctx->d.flags, n, hipMemcpyDeviceToHost, ctx->stream));
   RandTrailer tr; memcpy(tr.magic, "SMXRAND1", 8);
   RandState r;
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(tr.ring, r.ring, sizeof(tr.ring)); tr.idx = r.idx; tr.calls = r.calls;
   SnapHdr h; memset(&h, 0, sizeof(h)); memcpy(h.magic, "SMXSNAP1", 8);
   h.dimx = ctx->cfg.dimx; h.dimy = ctx->cfg.dimy; h.scale = ctx->d.scale; h.nsoils = ctx->nsoils; h.ncells = n; h.nsec = ns;
@@ -2021,16 +2001,16 @@ int smx_load(smx_ctx* ctx, const char* path) {
   if (smx_import_frequency(ctx, wf.data(), wt.data(), wi.data())) return -1;
   if (!fl.empty()) {                                         // the sticky bit on top of what the import derived from the columns
     std::vector<uint8_t> cur(n);
-    HIPCHK(hipMemcpyAsync(cur.data(), ctx->d.flags, n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cur.data(), ctx->d.flags, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t c = 0; c < n; c++) cur[c] |= (uint8_t)(fl[c] & F_SAT);
-    HIPCHK(hipMemcpyAsync(ctx->d.flags, cur.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d.flags, cur.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (have_rand) {
     RandState r; memcpy(r.ring, tr.ring, sizeof(r.ring)); r.idx = tr.idx; r.calls = tr.calls;
-    HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   ctx->d.scale = h.scale; ctx->cfg.scale = h.scale;
   return have_rand ? 0 : 1;   /* 1: state restored, but the file carries no generator state (a bare snapshot): re-seed it yourself */
@@ -2038,16 +2018,16 @@ int smx_load(smx_ctx* ctx, const char* path) {
 
 int smx_read_frequency(smx_ctx* ctx, float* wfreq, float* wtrack, float* windfreq) {
   const size_t n = ctx->ncells;
-  if (wfreq) HIPCHK(hipMemcpyAsync(wfreq, ctx->d.wfreq, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (wtrack) HIPCHK(hipMemcpyAsync(wtrack, ctx->d.wtrack, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (windfreq) HIPCHK(hipMemcpyAsync(windfreq, ctx->d.windfreq, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (wfreq) HIPCHK(ctx, hipMemcpyAsync(wfreq, ctx->d.wfreq, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (wtrack) HIPCHK(ctx, hipMemcpyAsync(wtrack, ctx->d.wtrack, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (windfreq) HIPCHK(ctx, hipMemcpyAsync(windfreq, ctx->d.windfreq, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 static int read_plane(smx_ctx* ctx, void* host, size_t bytes, int which) {   // (a strip context fills its range; the rest of `host` reads 0)
   if (which == 2) { FULLMAP("smx_normals") }
-  if (ctx->plane_cap < bytes) { hipFree(ctx->d_plane); ctx->d_plane = nullptr; ctx->plane_cap = 0; HIPCHK(hipMalloc(&ctx->d_plane, bytes)); ctx->plane_cap = bytes; }
+  HIPCHK(ctx, ctx->mem.grow(ctx->d_plane, ctx->plane_cap, bytes, bytes));
   void* tmp = ctx->d_plane;
   const unsigned nb = (unsigned)((ctx->lcells + 255) / 256);
   const size_t el = which == 0 ? 8 : (which == 1 ? 4 : 12);
@@ -2068,28 +2048,28 @@ static int fill_vertices(smx_ctx* ctx, const float* colors4, int32_t ncolors, vo
   FULLMAP("smx_fill_vertices")
   if (!colors4 || ncolors <= 0 || !out_vertices44) { ctx->err = "smx_fill_vertices: colors4/out must be given"; return -2; }
   const size_t bytes = ctx->ncells * 44;
-  if (!ctx->d_vcol) { HIPCHK(hipMalloc(&ctx->d_vcol, 256 * 16)); ctx->vcol_n = -1; }
+  if (!ctx->d_vcol) { HIPCHK(ctx, ctx->mem.dev(ctx->d_vcol, 256 * 4)); ctx->vcol_n = -1; }
   if (ncolors > 256) ncolors = 256;
   if (ctx->vcol_n != ncolors || memcmp(ctx->vcol_host, colors4, (size_t)ncolors * 16) != 0) {   // (the colour table rarely changes: one upload, not one per call)
-    HIPCHK(hipMemcpyAsync(ctx->d_vcol, colors4, (size_t)ncolors * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_vcol, colors4, (size_t)ncolors * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(ctx->vcol_host, colors4, (size_t)ncolors * 16); ctx->vcol_n = ncolors;
   }
   if (one_cell >= 0) {                                        // one column (Layermap::update(ivec2, ...)): the 256-cell block that holds it, into a block-sized scratch
-    if (!ctx->d_vtx1) HIPCHK(hipMalloc(&ctx->d_vtx1, 256 * 44));
+    if (!ctx->d_vtx1) HIPCHK(ctx, ctx->mem.dev(ctx->d_vtx1, 256 * 11));
     cut.block0 = (unsigned)((size_t)one_cell / 256); cut.rel = 1u;
     hipLaunchKernelGGL(k_fill_vertices, dim3(1), dim3(256), 0, ctx->stream, ctx->d, ctx->d_vcol, (uint32_t)ncolors, ctx->d_vtx1, cut);
-    HIPCHK(hipMemcpyAsync(out_vertices44, reinterpret_cast<const char*>(ctx->d_vtx1) + ((size_t)one_cell % 256) * 44, 44, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out_vertices44, reinterpret_cast<const char*>(ctx->d_vtx1) + ((size_t)one_cell % 256) * 44, 44, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
   }
   if (!ctx->d_vtx) {                                        // whole-map scratch kept for the context's lifetime (738 MB at 4096^2)
-    if (hipMalloc(&ctx->d_vtx, bytes) != hipSuccess) { ctx->d_vtx = nullptr; ctx->err = "smx_fill_vertices: out of device memory"; return -1; }
+    if (ctx->mem.dev(ctx->d_vtx, ctx->ncells * 11) != hipSuccess) { ctx->err = "smx_fill_vertices: out of device memory"; return -1; }
   }
   hipLaunchKernelGGL(k_fill_vertices, dim3((unsigned)((ctx->ncells + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d, ctx->d_vcol,
                      (uint32_t)ncolors, ctx->d_vtx, cut);
-  HIPCHK(hipMemcpyAsync(out_vertices44, ctx->d_vtx, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out_vertices44, ctx->d_vtx, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 int smx_fill_vertices(smx_ctx* ctx, const float* colors4, int32_t ncolors, void* out_vertices44) {
@@ -2114,12 +2094,12 @@ int smx_fill_vertex_cut(smx_ctx* ctx, const float* colors4, int32_t ncolors, int
 int smx_heights_bilinear(smx_ctx* ctx, const float* pos2, int32_t n, double* out) {
   FULLMAP("smx_heights_bilinear")
   float* dpos = nullptr; double* dout = nullptr;
-  HIPCHK(hipMalloc(&dpos, (size_t)n * 8)); HIPCHK(hipMalloc(&dout, (size_t)n * 8));
-  HIPCHK(hipMemcpyAsync(dpos, pos2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, ctx->mem.dev(dpos, (size_t)n * 2)); HIPCHK(ctx, ctx->mem.dev(dout, (size_t)n));
+  HIPCHK(ctx, hipMemcpyAsync(dpos, pos2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_bilinear, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d, dpos, n, dout);
   hipError_t e = hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(dpos); hipFree(dout);
+  ctx->mem.drop(dpos); ctx->mem.drop(dout);
   if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return -1; }
   return 0;
 }
@@ -2130,17 +2110,16 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
   if (ctx->spec_cap >= n && !ctx->spec_realloc) return 0;
   ctx->spec_realloc = false;
   SpecShared& sh = ctx->sh;
-  if (ctx->spec_cap) {
-    hipFree(sh.part); hipFree(sh.chunk_tab); hipFree(sh.arena); hipFree(sh.alloc_log); hipFree(sh.free_log);
-    hipFree(sh.pending); hipFree(sh.draws); hipFree(sh.scout_cells); hipFree(sh.scout_len); hipFree(sh.ckpt);
-    sh.part = nullptr; sh.chunk_tab = nullptr; sh.arena = nullptr; sh.alloc_log = nullptr; sh.free_log = nullptr;
-    sh.pending = nullptr; sh.draws = nullptr; sh.scout_cells = nullptr; sh.scout_len = nullptr; sh.ckpt = nullptr;
-    ctx->spec_cap = 0;                                        // a failed hipMalloc below must not leave dangling pointers
+  DevMem& m = ctx->mem;
+  if (ctx->spec_cap) {                                        // the per-slot buffers go before the larger ones are asked for
+    m.drop(sh.part); m.drop(sh.chunk_tab); m.drop(sh.arena); m.drop(sh.alloc_log); m.drop(sh.free_log);
+    m.drop(sh.pending); m.drop(sh.draws); m.drop(sh.scout_cells); m.drop(sh.scout_len); m.drop(sh.ckpt);
+    ctx->spec_cap = 0;
   } else {
-    HIPCHK(hipMalloc(&sh.stamp, ctx->ncells * 4)); HIPCHK(hipMalloc(&sh.claim, ctx->ncells * 4));
-    HIPCHK(hipMalloc(&sh.ctrl, SC_COUNT * 4));
-    sh.reclaim_cap = 1u << 22; HIPCHK(hipMalloc(&sh.reclaim, (size_t)sh.reclaim_cap * 4));
-    HIPCHK(hipHostMalloc(&ctx->h_ctrl, SC_COUNT * 4));
+    HIPCHK(ctx, m.dev(sh.stamp, ctx->ncells)); HIPCHK(ctx, m.dev(sh.claim, ctx->ncells));
+    HIPCHK(ctx, m.dev(sh.ctrl, SC_COUNT));
+    sh.reclaim_cap = 1u << 22; HIPCHK(ctx, m.dev(sh.reclaim, sh.reclaim_cap));
+    HIPCHK(ctx, m.pinned(ctx->h_ctrl, SC_COUNT));
   }
   const uint32_t cap = n < 1024 ? 1024 : n;                 // particles
   // nested-particle slots of a sub-phase: 8192 on the device (21 KB of per-slot records each: 170 MB). With the 1 024 of round 3 a
@@ -2149,17 +2128,15 @@ static int spec_alloc(smx_ctx* ctx, uint32_t n) {          // n = particles of a
   static const uint32_t maxnest = (uint32_t)std::min(60000ll, std::max(128ll, env_int("SMX_SPEC_MAXNEST")));
   sh.maxnest = ctx->spec_maxnest ? ctx->spec_maxnest : maxnest;
   const uint32_t slots = cap + sh.maxnest;                  // per-slot records (soil_spec.h "rand() SLOTS")
-  HIPCHK(hipMalloc(&sh.part, (size_t)slots * sizeof(SpecPart)));
-  HIPCHK(hipMalloc(&sh.chunk_tab, (size_t)slots * MAX_CHUNKS * 4));
+  HIPCHK(ctx, m.dev(sh.part, slots)); HIPCHK(ctx, m.dev(sh.chunk_tab, (size_t)slots * MAX_CHUNKS));
   sh.arena_chunks = cap * 32u < 16384u ? 16384u : cap * 32u;
-  HIPCHK(hipMalloc(&sh.arena, (size_t)sh.arena_chunks * LOG_CHUNK * sizeof(SpecLog)));
-  HIPCHK(hipMalloc(&sh.alloc_log, (size_t)slots * MAX_NODELOG * 4)); HIPCHK(hipMalloc(&sh.free_log, (size_t)slots * MAX_NODELOG * 4));
-  HIPCHK(hipMalloc(&sh.pending, (size_t)slots * 4));
-  sh.ndraws = 2 * slots; HIPCHK(hipMalloc(&sh.draws, (size_t)sh.ndraws * 4));
+  HIPCHK(ctx, m.dev(sh.arena, (size_t)sh.arena_chunks * LOG_CHUNK));
+  HIPCHK(ctx, m.dev(sh.alloc_log, (size_t)slots * MAX_NODELOG)); HIPCHK(ctx, m.dev(sh.free_log, (size_t)slots * MAX_NODELOG));
+  HIPCHK(ctx, m.dev(sh.pending, slots)); sh.ndraws = 2 * slots; HIPCHK(ctx, m.dev(sh.draws, sh.ndraws));
   // scouted footprints (the first n + SPEC_SCOUT_MARGIN slots only): water paths are a few thousand cells, wind paths up to ~10^5
   sh.scout_cap = cap <= 2048 ? 131072u : 16384u;
-  HIPCHK(hipMalloc(&sh.scout_cells, (size_t)(cap + SPEC_SCOUT_MARGIN) * sh.scout_cap * 4)); HIPCHK(hipMalloc(&sh.scout_len, (size_t)slots * 4));
-  HIPCHK(hipMalloc(&sh.ckpt, (size_t)slots * sizeof(SpecCkpt)));
+  HIPCHK(ctx, m.dev(sh.scout_cells, (size_t)(cap + SPEC_SCOUT_MARGIN) * sh.scout_cap)); HIPCHK(ctx, m.dev(sh.scout_len, slots));
+  HIPCHK(ctx, m.dev(sh.ckpt, slots));
   sh.mode = 3u;
   ctx->spec_cap = cap;
   return 0;
@@ -2179,7 +2156,7 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
   ctx->sh.mode = wind ? mode_wind : mode_water;
   const SpecShared& sh = ctx->sh;
   hipStream_t st = ctx->stream;
-  HIPCHK(hipMemsetAsync(sh.stamp, 0, ctx->ncells * 4, st));
+  HIPCHK(ctx, hipMemsetAsync(sh.stamp, 0, ctx->ncells * 4, st));
   hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, st, ctx->d, sh, (uint32_t)n);
   const uint32_t L = (uint32_t)spec_lanes();
   static const bool wind_scout = env_flag("SMX_WIND_SCOUT");
@@ -2192,10 +2169,10 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
   *outcome = 0;
   static const bool trace_rounds = env_flag("SMX_TRACE_ROUNDS");
   uint32_t prev_exec = 0, prev_sum = 0;
-  if (trace_rounds) HIPCHK(hipStreamSynchronize(st));
+  if (trace_rounds) HIPCHK(ctx, hipStreamSynchronize(st));
   auto t_round = std::chrono::steady_clock::now();
   for (int round = 0;; round++) {
-    HIPCHK(hipMemsetAsync(sh.claim, 0xFF, ctx->ncells * 4, st));
+    HIPCHK(ctx, hipMemsetAsync(sh.claim, 0xFF, ctx->ncells * 4, st));
     hipLaunchKernelGGL(k_spec_claim, dim3(np), dim3(64), 0, st, sh);
     if (sh.mode & 1u) hipLaunchKernelGGL(k_spec_select, dim3(np), dim3(64), 0, st, sh);
     {
@@ -2204,8 +2181,8 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
       else LAUNCH_WIND_WATER(wind, k_spec_exec, dim3((np + L - 1) / L), dim3(64), st, ctx->d, sh, L);
     }
     hipLaunchKernelGGL(k_spec_boundary, dim3(1), dim3(1024), 0, st, ctx->d, sh);
-    HIPCHK(hipMemcpyAsync(ctx->h_ctrl, sh.ctrl, SC_COUNT * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_ctrl, sh.ctrl, SC_COUNT * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     const uint32_t* c = ctx->h_ctrl;
     if (trace_rounds) {                                                   // SMX_TRACE_ROUNDS=1: one line per round on stderr
       const auto now = std::chrono::steady_clock::now();
@@ -2232,11 +2209,11 @@ static int spec_subphase(smx_ctx* ctx, int32_t n, bool wind, uint32_t* committed
   } else {
     hipLaunchKernelGGL(k_spec_end, dim3(1), dim3(256), 0, st, ctx->d, sh, 1u);
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   {
     uint32_t crossed = 0;
-    HIPCHK(hipMemcpyAsync(&crossed, sh.ctrl + SC_POOL_CROSSED, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(&crossed, sh.ctrl + SC_POOL_CROSSED, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     if (crossed) { ctx->err = "speculative phase ran past pool_capacity (pool.get() would have failed inside it): raise pool_capacity"; return -6; }
   }
   if (c[SC_RECLAIM_LOST] != 0) { ctx->err = "speculative phase: reclaim list overflow (pool nodes leaked)"; return -6; }
@@ -2268,7 +2245,7 @@ static int spec_phase(smx_ctx* ctx, int32_t n, bool wind) {
     if (outcome == 2) { ctx->spec_fallbacks++; serial(remaining); remaining = 0; }
     else if (committed == 0) { ctx->spec_serial_particles++; serial(1u); remaining -= 1u; }   // one particle with more nested particles than a sub-phase has slots
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 
@@ -2277,53 +2254,52 @@ static void launch_classify(smx_ctx* ctx);
 // ---------------- batched engine: host driver (tests/hostsim/hostsim.cpp batch_generations drives the same headers on host threads) ----------------
 static int batch_alloc(smx_ctx* ctx, uint32_t nslots, bool wind) {
   BatchShared& bs = ctx->bs;
+  DevMem& m = ctx->mem;
   if (!bs.ctrl) {
     bs.tshift = -1; bs.ntx = ctx->cfg.dimx; bs.nty = ctx->cfg.dimy; bs.txb = 0; bs.txe = ctx->cfg.dimx;
     const size_t nt = ctx->lcells + 2 * (size_t)ctx->cfg.dimy;   // one claim word per held cell (+ a row of slack for tiles cut by the range's edges): enough for every granularity
-    HIPCHK(hipMalloc(&bs.claim[0], nt * 8)); HIPCHK(hipMalloc(&bs.claim[1], nt * 8));
-    HIPCHK(hipMalloc(&bs.ctrl, BC_COUNT * 4)); HIPCHK(hipMemsetAsync(bs.ctrl, 0, BC_COUNT * 4, ctx->stream));
+    HIPCHK(ctx, m.dev(bs.claim[0], nt)); HIPCHK(ctx, m.dev(bs.claim[1], nt));
+    HIPCHK(ctx, m.dev(bs.ctrl, BC_COUNT)); HIPCHK(ctx, hipMemsetAsync(bs.ctrl, 0, BC_COUNT * 4, ctx->stream));
     // nested particles of one generation / pool nodes released in one chunk: sized by the map (a grid pass over a map full
     // of lakes emits children for a sizeable part of its cells); running out is counted (children_lost) / an error (freed)
-    bs.child_cap = (uint32_t)std::max<size_t>((size_t)1 << 20, ctx->lcells / 2); HIPCHK(hipMalloc(&bs.children, (size_t)bs.child_cap * sizeof(BChild)));
-    bs.freed_cap = (uint32_t)std::max<size_t>((size_t)1 << 22, ctx->lcells / 2); HIPCHK(hipMalloc(&bs.freed, (size_t)bs.freed_cap * 4));
+    bs.child_cap = (uint32_t)std::max<size_t>((size_t)1 << 20, ctx->lcells / 2); HIPCHK(ctx, m.dev(bs.children, bs.child_cap));
+    bs.freed_cap = (uint32_t)std::max<size_t>((size_t)1 << 22, ctx->lcells / 2); HIPCHK(ctx, m.dev(bs.freed, bs.freed_cap));
     {
       const size_t ngt = (size_t)((ctx->cfg.dimx + 3) >> 2) * ((ctx->cfg.dimy + 3) >> 2);
-      HIPCHK(hipMalloc(&bs.dirty, ngt)); HIPCHK(hipMemsetAsync(bs.dirty, 0, ngt, ctx->stream));
+      HIPCHK(ctx, m.dev(bs.dirty, ngt)); HIPCHK(ctx, hipMemsetAsync(bs.dirty, 0, ngt, ctx->stream));
     }
-    HIPCHK(hipHostMalloc(&ctx->h_bctrl, BC_COUNT * 4));
+    HIPCHK(ctx, m.pinned(ctx->h_bctrl, BC_COUNT));
   }
   if (ctx->batch_cap < nslots) {
-    hipFree(bs.water); hipFree(bs.wind); hipFree(bs.live); bs.water = nullptr; bs.wind = nullptr; bs.live = nullptr; ctx->batch_cap = 0;
+    m.drop(bs.water); m.drop(bs.wind); m.drop(bs.live); ctx->batch_cap = 0;
     const uint32_t cap = nslots < 4096u ? 4096u : nslots;
-    HIPCHK(hipMalloc(&bs.water, (size_t)cap * sizeof(BWater))); HIPCHK(hipMalloc(&bs.wind, (size_t)cap * sizeof(BWind)));
-    HIPCHK(hipMalloc(&bs.live, (size_t)cap * 4));
+    HIPCHK(ctx, m.dev(bs.water, cap)); HIPCHK(ctx, m.dev(bs.wind, cap)); HIPCHK(ctx, m.dev(bs.live, cap));
     ctx->batch_cap = cap;
   }
   if (ctx->cfg.engine == SMX_ENGINE_RELAXED && ctx->relax_cap < ctx->batch_cap) {   // request entries (2 per step), per-epoch flood and cascade lists
-    hipFree(bs.req); hipFree(bs.rnext); hipFree(bs.rcount); hipFree(bs.flist[0]); hipFree(bs.flist[1]); hipFree(bs.clist[0]); hipFree(bs.clist[1]);
-    hipFree(bs.flagl[0]); hipFree(bs.flagl[1]); bs.flagl[0] = bs.flagl[1] = nullptr;
-    bs.req = nullptr; bs.rnext = nullptr; bs.rcount = nullptr; bs.flist[0] = bs.flist[1] = bs.clist[0] = bs.clist[1] = nullptr; ctx->relax_cap = 0;
+    m.drop(bs.req); m.drop(bs.rnext); m.drop(bs.rcount); ctx->relax_cap = 0;
+    for (int k = 0; k < 2; k++) { m.drop(bs.flist[k]); m.drop(bs.flagl[k]); m.drop(bs.clist[k]); }
     const uint32_t cap = ctx->batch_cap;
     const size_t ent = (size_t)cap * 2 * R_MAXSTEPS;
-    HIPCHK(hipMalloc(&bs.req, ent * sizeof(RReq))); HIPCHK(hipMalloc(&bs.rnext, ent * 4)); HIPCHK(hipMalloc(&bs.rcount, (size_t)cap * 4));
-    HIPCHK(hipMemsetAsync(bs.rcount, 0, (size_t)cap * 4, ctx->stream));
+    HIPCHK(ctx, m.dev(bs.req, ent)); HIPCHK(ctx, m.dev(bs.rnext, ent)); HIPCHK(ctx, m.dev(bs.rcount, cap));
+    HIPCHK(ctx, hipMemsetAsync(bs.rcount, 0, (size_t)cap * 4, ctx->stream));
     bs.list_cap = cap; bs.flag_cap = (uint32_t)ent; bs.clist_cap = (uint32_t)std::max<size_t>(4096, ent / 2);
     for (int k = 0; k < 2; k++) {
-      HIPCHK(hipMalloc(&bs.flist[k], (size_t)bs.list_cap * 4)); HIPCHK(hipMalloc(&bs.flagl[k], (size_t)bs.flag_cap * 4));
-      HIPCHK(hipMalloc(&bs.clist[k], (size_t)9 * bs.clist_cap * 4));
+      HIPCHK(ctx, m.dev(bs.flist[k], bs.list_cap)); HIPCHK(ctx, m.dev(bs.flagl[k], bs.flag_cap));
+      HIPCHK(ctx, m.dev(bs.clist[k], (size_t)9 * bs.clist_cap));
     }
     ctx->relax_cap = cap;
   }
   if (ctx->cfg.engine == SMX_ENGINE_RELAXED && !bs.rhead) {   // per-cell request lists and cascade flags (8 B / cell), empty between epochs
-    HIPCHK(hipMalloc(&ctx->rhead_alloc, ctx->lcells * 4)); HIPCHK(hipMalloc(&ctx->cflag_alloc, ctx->lcells * 4));
-    HIPCHK(hipMemsetAsync(ctx->rhead_alloc, 0xFF, ctx->lcells * 4, ctx->stream)); HIPCHK(hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, ctx->stream));
-    HIPCHK(hipMalloc(&ctx->cstate_alloc, ctx->lcells * 4)); HIPCHK(hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, ctx->stream));
+    HIPCHK(ctx, m.dev(ctx->rhead_alloc, ctx->lcells)); HIPCHK(ctx, m.dev(ctx->cflag_alloc, ctx->lcells));
+    HIPCHK(ctx, hipMemsetAsync(ctx->rhead_alloc, 0xFF, ctx->lcells * 4, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, ctx->stream));
+    HIPCHK(ctx, m.dev(ctx->cstate_alloc, ctx->lcells)); HIPCHK(ctx, hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, ctx->stream));
     bs.rhead = ctx->rhead_alloc - ctx->c_lo; bs.cflag = ctx->cflag_alloc - ctx->c_lo; bs.cstate = ctx->cstate_alloc - ctx->c_lo;   // (global cell index, held range only)
   }
   if (ctx->draws_cap < 2u * nslots) {
-    hipFree(ctx->d_draws); if (ctx->h_draws) hipHostFree(ctx->h_draws); ctx->d_draws = nullptr; ctx->h_draws = nullptr; ctx->draws_cap = 0;
+    m.drop(ctx->d_draws); m.drop(ctx->h_draws); ctx->draws_cap = 0;
     const uint32_t cap = 2u * (nslots < 4096u ? 4096u : nslots);
-    HIPCHK(hipMalloc(&ctx->d_draws, (size_t)cap * 4)); HIPCHK(hipHostMalloc(&ctx->h_draws, (size_t)cap * 4));
+    HIPCHK(ctx, m.dev(ctx->d_draws, cap)); HIPCHK(ctx, m.pinned(ctx->h_draws, cap));
     ctx->draws_cap = cap;
   }
   bs.draws = ctx->d_draws; bs.dilate = ctx->batch_dilate; bs.maxsteps = 1;
@@ -2357,20 +2333,21 @@ __global__ void __launch_bounds__(256) k_child_gather(const BChild* __restrict__
 static int sort_children(smx_ctx* ctx, uint32_t nc) {       // bs.children[0, nc) -> ctx->d_kids[0, nc), ascending key; asynchronous on the context's stream
   hipStream_t st = ctx->stream;
   if (nc == 0) return 0;
-  if (ctx->kids_cap < nc) { hipFree(ctx->d_kids); ctx->d_kids = nullptr; ctx->kids_cap = 0; const uint32_t cap = nc + nc / 2; HIPCHK(hipMalloc(&ctx->d_kids, (size_t)cap * sizeof(BChild))); ctx->kids_cap = cap; }
+  DevMem& m = ctx->mem;
+  HIPCHK(ctx, m.grow(ctx->d_kids, ctx->kids_cap, nc, nc + nc / 2));
   if (ctx->sort_cap < nc) {
-    for (int k = 0; k < 2; k++) { hipFree(ctx->d_skeys[k]); hipFree(ctx->d_sidx[k]); ctx->d_skeys[k] = nullptr; ctx->d_sidx[k] = nullptr; }
-    hipFree(ctx->d_stemp); ctx->d_stemp = nullptr; ctx->stemp_bytes = 0; ctx->sort_cap = 0;
+    for (int k = 0; k < 2; k++) { m.drop(ctx->d_skeys[k]); m.drop(ctx->d_sidx[k]); }
+    m.drop(ctx->d_stemp); ctx->stemp_bytes = 0; ctx->sort_cap = 0;
     const uint32_t cap = nc + nc / 2;
-    for (int k = 0; k < 2; k++) { HIPCHK(hipMalloc(&ctx->d_skeys[k], (size_t)cap * 8)); HIPCHK(hipMalloc(&ctx->d_sidx[k], (size_t)cap * 4)); }
+    for (int k = 0; k < 2; k++) { HIPCHK(ctx, m.dev(ctx->d_skeys[k], cap)); HIPCHK(ctx, m.dev(ctx->d_sidx[k], cap)); }
     size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, ctx->d_skeys[0], ctx->d_skeys[1], ctx->d_sidx[0], ctx->d_sidx[1], (size_t)cap, 0u, 64u, st));
-    HIPCHK(hipMalloc(&ctx->d_stemp, tb)); ctx->stemp_bytes = tb; ctx->sort_cap = cap;
+    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, ctx->d_skeys[0], ctx->d_skeys[1], ctx->d_sidx[0], ctx->d_sidx[1], (size_t)cap, 0u, 64u, st));
+    HIPCHK(ctx, m.dev(ctx->d_stemp, tb)); ctx->stemp_bytes = tb; ctx->sort_cap = cap;
   }
   const unsigned nb = (nc + 255u) / 256u;
   hipLaunchKernelGGL(k_child_keys, dim3(nb), dim3(256), 0, st, ctx->bs.children, nc, ctx->d_skeys[0], ctx->d_sidx[0]);
   size_t tb = ctx->stemp_bytes;
-  HIPCHK(rocprim::radix_sort_pairs(ctx->d_stemp, tb, ctx->d_skeys[0], ctx->d_skeys[1], ctx->d_sidx[0], ctx->d_sidx[1], (size_t)nc, 0u, 64u, st));
+  HIPCHK(ctx, rocprim::radix_sort_pairs(ctx->d_stemp, tb, ctx->d_skeys[0], ctx->d_skeys[1], ctx->d_sidx[0], ctx->d_sidx[1], (size_t)nc, 0u, 64u, st));
   hipLaunchKernelGGL(k_child_gather, dim3(nb), dim3(256), 0, st, ctx->bs.children, ctx->d_sidx[1], nc, ctx->d_kids);
   return 0;
 }
@@ -2389,7 +2366,7 @@ static int batch_check_ctrl(smx_ctx* ctx, uint32_t& nc) {
 static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uint32_t nepochs) {
   hipStream_t st = ctx->stream;
   if (!ctx->d_gbar) {
-    if (hipMalloc(&ctx->d_gbar, sizeof(GridBar)) != hipSuccess) { ctx->mega_off = true; return 1; }
+    if (ctx->mem.dev(ctx->d_gbar, 1) != hipSuccess) { ctx->mega_off = true; return 1; }
     hipMemsetAsync(ctx->d_gbar, 0, sizeof(GridBar), st);
   }
   if (!ctx->mega_blocks) {
@@ -2451,7 +2428,7 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
   const bool regrain = plan.regrain;
   if (regrain) {                                           // (the planes hold the tile columns of the context's range)
     const size_t nt = (size_t)(((ctx->d.x_hi - 1) >> bs.tshift) - (ctx->d.x_lo >> bs.tshift) + 1) * bs.nty;
-    HIPCHK(hipMemsetAsync(bs.claim[0], 0, nt * 8, st)); HIPCHK(hipMemsetAsync(bs.claim[1], 0, nt * 8, st));
+    HIPCHK(ctx, hipMemsetAsync(bs.claim[0], 0, nt * 8, st)); HIPCHK(ctx, hipMemsetAsync(bs.claim[1], 0, nt * 8, st));
   }
   if ((regrain || strips) && nlive)                        // under strips every chunk starts with fresh reservations
     LAUNCH_WIND_WATER(wind, k_batch_reclaim, dim3((nlive + 63u) / 64u), dim3(64), st, ctx->d, bs, nlive, epoch);
@@ -2469,8 +2446,8 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
     static const int mega_chunk = (int)std::max(0ll, env_int("SMX_RELAX_MEGA_CHUNK"));   // (0: the chunk lengths of the per-phase launches)
     const bool mega = !wind && !tail && use_mega && !ctx->mega_off && bs.cstate != nullptr;
     chunk_epochs = strips ? plan.chunk_epochs : (tail ? 64 : (mega && mega_chunk ? mega_chunk : (first ? CHUNK : RCHUNK_KIDS)));
-    if (ctx->relax_tag > 0x7FFF0000u) { ctx->relax_tag = 0; HIPCHK(hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, st)); HIPCHK(hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, st)); }   // (tags never repeat; 2 * tag + 1 fits 32 bits)
-    if (strips) HIPCHK(hipMemsetAsync(bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // (the epoch skipped between two chunks breaks the lists' parity hand-over)
+    if (ctx->relax_tag > 0x7FFF0000u) { ctx->relax_tag = 0; HIPCHK(ctx, hipMemsetAsync(ctx->cflag_alloc, 0, ctx->lcells * 4, st)); HIPCHK(ctx, hipMemsetAsync(ctx->cstate_alloc, 0, ctx->lcells * 4, st)); }   // (tags never repeat; 2 * tag + 1 fits 32 bits)
+    if (strips) HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // (the epoch skipped between two chunks breaks the lists' parity hand-over)
     if (strips && !wind) {                                   // who waits for a flood on this device right now?
       if (nslots) hipLaunchKernelGGL(k_relax_rebuild_floods, dim3((nslots + 255u) / 256u), dim3(256), 0, st, bs, nslots, epoch & 1u);
     }
@@ -2542,8 +2519,8 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
   RandState r;                                              // the host draws for the device: glibc rand() is a serial recurrence
   const bool draws = first;                                 // (suspended nested particles carry their state: no draws, no round trip)
   if (draws) {
-    HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
   }
   while (nslots > 0) {
     if (batch_alloc(ctx, nslots, wind)) return -1;
@@ -2553,12 +2530,12 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
         ctx->h_draws[i] = rand_step(r) >> 1;
         r.calls++;
       }
-      HIPCHK(hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)2u * nslots * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(ctx, hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)2u * nslots * 4, hipMemcpyHostToDevice, st));
     }
     ctx->bs.tshift = -1;                                      // (the first chunk clears the planes and issues the first reservations)
     const bool relax_gen = ctx->cfg.engine == SMX_ENGINE_RELAXED;
     ctx->bs.relaxed = relax_gen ? 1 : 0;
-    if (relax_gen) HIPCHK(hipMemsetAsync(ctx->bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // flood, flag and cascade lists start empty
+    if (relax_gen) HIPCHK(ctx, hipMemsetAsync(ctx->bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // flood, flag and cascade lists start empty
     const BChild* dk = first ? nullptr : ctx->d_kids;        // (sorted there by sort_children)
     const unsigned nb = (nslots + 63u) / 64u;
     LAUNCH_WIND_WATER(wind, k_batch_spawn, dim3(nb), dim3(64), st, ctx->d, bs, nslots, dk, (const uint32_t*)nullptr);
@@ -2570,10 +2547,10 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
       const uint32_t live_in = nlive;
       int chunk_epochs = 0;
       if (run_chunk(ctx, wind, nlive, nlive, nslots, first, relax_gen, epoch, chunk, &chunk_epochs)) return -1;
-      HIPCHK(hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
+      HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
       LAUNCH_WIND_WATER(wind, k_batch_compact, dim3((nslots + 255u) / 256u), dim3(256), st, bs, nslots);
-      HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(ctx, hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipStreamSynchronize(st));
       nlive = ctx->h_bctrl[BC_NLIVE];
       ctx->batch_epochs += chunk_epochs;
       if (trace) fprintf(stderr, "[soilmx] batched %s gen-slots %u epochs %u..%u live %u -> %u grain %d dilate %d maxsteps %d  %.3f ms\n", wind ? "wind " : "water", nslots,
@@ -2586,15 +2563,15 @@ static int batch_generations(smx_ctx* ctx, bool wind, uint32_t n, uint32_t nkids
     if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
     if (wind) nc = 0;
     if (nc && sort_children(ctx, nc)) return -1;             // -> ctx->d_kids, on the device
-    HIPCHK(hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));   // NCHILD, CHILD_LOST
+    HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));   // NCHILD, CHILD_LOST
     first = false;
     nslots = nc;
   }
   if (draws) {
-    HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
   }
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 // One sweep of the grid pass over the tile columns [tx_lo, tx_hi): the tiles with work, in (colour, tile) order, through the dataflow
@@ -2608,8 +2585,8 @@ static int grid_sweep(smx_ctx* ctx, int phase, int tx_lo, int tx_hi) {
   if (tx_hi <= tx_lo) return 0;
   if (!ctx->d_tdone) {
     const size_t nt = (size_t)(txe - txb) * gty;
-    HIPCHK(hipMalloc(&ctx->d_tdone, nt * 4)); HIPCHK(hipMalloc(&ctx->d_tpend[0], nt * 4)); HIPCHK(hipMalloc(&ctx->d_tpend[1], nt * 4));
-    HIPCHK(hipMalloc(&ctx->d_tcount, 8)); HIPCHK(hipHostMalloc(&ctx->h_tcount, 8));
+    HIPCHK(ctx, ctx->mem.dev(ctx->d_tdone, nt)); HIPCHK(ctx, ctx->mem.dev(ctx->d_tpend[0], nt)); HIPCHK(ctx, ctx->mem.dev(ctx->d_tpend[1], nt));
+    HIPCHK(ctx, ctx->mem.dev(ctx->d_tcount, 2)); HIPCHK(ctx, ctx->mem.pinned(ctx->h_tcount, 2));
   }
   ctx->bs.tshift = GRID_SHIFT; ctx->bs.sphase = phase;
   const BatchShared& bs = ctx->bs;
@@ -2617,35 +2594,35 @@ static int grid_sweep(smx_ctx* ctx, int phase, int tx_lo, int tx_hi) {
   g.tdone = ctx->d_tdone; g.pend[0] = ctx->d_tpend[0]; g.pend[1] = ctx->d_tpend[1]; g.count = ctx->d_tcount;
   g.gtx = gtx; g.gty = gty; g.txb = txb; g.txe = txe; g.tx_lo = tx_lo; g.tx_hi = tx_hi;
   g.keybase = (unsigned long long)phase * 9ull * (unsigned long long)gtx * (unsigned long long)gty;   // key prefix = (phase * 9 + colour) * tiles + tile
-  HIPCHK(hipMemsetAsync(ctx->d_tcount, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_tcount, 0, 8, st));
   const uint32_t ntl = (uint32_t)(tx_hi - tx_lo) * (uint32_t)gty;
   hipLaunchKernelGGL(k_grid_tiles_init, dim3((ntl + 255u) / 256u), dim3(256), 0, st, ctx->d, bs, g);
-  HIPCHK(hipMemcpyAsync(ctx->h_tcount, ctx->d_tcount, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_tcount, ctx->d_tcount, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   const uint32_t n = ctx->h_tcount[0];
   const bool trace = trace_batch();
   const auto t_sweep = std::chrono::steady_clock::now();
   if (n > 0) {
     // the tiles with work in (colour, tile) order (the init kernel appended them as its wavefronts came); entries are unique
     if (ctx->tsort_cap < n) {
-      hipFree(ctx->d_tsort); ctx->d_tsort = nullptr; ctx->tsort_cap = 0; ctx->tsort_bytes = 0;
+      ctx->mem.drop(ctx->d_tsort); ctx->tsort_cap = 0; ctx->tsort_bytes = 0;
       const uint32_t cap = (uint32_t)((size_t)(txe - txb) * gty);
       size_t tb = 0;
-      HIPCHK(rocprim::radix_sort_keys(nullptr, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)cap, 0u, 32u, st));
-      HIPCHK(hipMalloc(&ctx->d_tsort, tb)); ctx->tsort_bytes = tb; ctx->tsort_cap = cap;
+      HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)cap, 0u, 32u, st));
+      HIPCHK(ctx, ctx->mem.dev(ctx->d_tsort, tb)); ctx->tsort_bytes = tb; ctx->tsort_cap = cap;
     }
     size_t tb = ctx->tsort_bytes;
-    HIPCHK(rocprim::radix_sort_keys(ctx->d_tsort, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)n, 0u, 32u, st));
-    HIPCHK(hipMemsetAsync(ctx->d_tcount + 1, 0, 4, st));     // the cursor of the dataflow kernel
+    HIPCHK(ctx, rocprim::radix_sort_keys(ctx->d_tsort, tb, ctx->d_tpend[0], ctx->d_tpend[1], (size_t)n, 0u, 32u, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_tcount + 1, 0, 4, st));     // the cursor of the dataflow kernel
     static const unsigned flow_waves = (unsigned)std::max(1ll, env_int("SMX_GRID_FLOW_WAVES"));
     static const uint32_t poll_naps = (uint32_t)env_int("SMX_GRID_POLL_NAPS");   // (x 3.4 us between two polls of a waiting tile)
     { PhaseTimer tk(ctx, PH_K_GRIDTILES); hipLaunchKernelGGL(k_grid_tiles_flow, dim3(std::min<unsigned>(n, flow_waves)), dim3(64), 0, st, ctx->d, bs, g, ctx->d_tpend[1], n, poll_naps | (flood_prof() ? 0x80000000u : 0u), spin_budget(1u << 22)); }
     hipLaunchKernelGGL(k_batch_merge_freed, dim3(1), dim3(256), 0, st, ctx->d, bs);
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     ctx->grid_passes++;
   }
   if (trace) fprintf(stderr, "[soilmx] grid sweep (kind %d): %u tiles with work  %.3f ms\n", phase, n, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sweep).count());
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 static int batch_grid(smx_ctx* ctx) {
@@ -2653,20 +2630,20 @@ static int batch_grid(smx_ctx* ctx) {
   if (batch_alloc(ctx, 1, false)) return -1;
   const BatchShared& bs = ctx->bs;
   unsigned long long v0 = 0;
-  HIPCHK(hipMemcpyAsync(&v0, ctx->d.ctr + C_GRID_ACTIVE, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, st));
-  HIPCHK(hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, st));
+  HIPCHK(ctx, hipMemcpyAsync(&v0, ctx->d.ctr + C_GRID_ACTIVE, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, st));
   launch_classify(ctx);
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   const int gtx = (ctx->cfg.dimx + (1 << GRID_SHIFT) - 1) >> GRID_SHIFT;
   for (int ph = 0; ph < (bs.strips.n > 1 ? 2 : 1); ph++) { const int rc = grid_sweep(ctx, ph, 0, gtx); if (rc) return rc; }
   hipLaunchKernelGGL(k_batch_grid_finish, dim3(1), dim3(1), 0, st, ctx->d, v0);
-  HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   uint32_t nc = 0;
   if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
   if (nc && sort_children(ctx, nc)) return -1;
-  HIPCHK(hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));
   if (nc) { PhaseTimer tk(ctx, PH_K_GRID_CHILDREN); return batch_generations(ctx, false, 0, nc); }   // the nested particles that left their tile's region
   return 0;
 }
@@ -2686,7 +2663,7 @@ static void launch_classify(smx_ctx* ctx) {                  // which cells can 
 static int xbuf_alloc(smx_ctx* ctx) {
   if (ctx->d_xdata) return 0;
   ctx->xdata_cap = 256ull << 20; ctx->xoffs_cap = 8u << 20;
-  HIPCHK(hipMalloc(&ctx->d_xdata, ctx->xdata_cap)); HIPCHK(hipMalloc(&ctx->d_xoffs, (size_t)ctx->xoffs_cap * 4)); HIPCHK(hipMalloc(&ctx->d_xcur, 2 * sizeof(XCursor)));   // [0] columns, [1] particles (st_pack_band)
+  HIPCHK(ctx, ctx->mem.dev(ctx->d_xdata, ctx->xdata_cap)); HIPCHK(ctx, ctx->mem.dev(ctx->d_xoffs, ctx->xoffs_cap)); HIPCHK(ctx, ctx->mem.dev(ctx->d_xcur, 2));   // [0] columns, [1] particles (st_pack_band)
   return 0;
 }
 extern "C" {
@@ -2698,37 +2675,37 @@ int smx_d_gen_begin(smx_ctx* ctx, int32_t wind, uint32_t nslots, const void* kid
     ctx->stagger_phase_n = (!wind && !kids_host && ctx->cfg.engine == SMX_ENGINE_RELAXED && ctx->water_stagger > 0 && ctx->water_generations > 1) ? nslots : 0u;
   if (batch_alloc(ctx, nslots ? nslots : 1, ctx->d_wind)) return -1;
   RandState r;                                              // every rank holds the same generator state and draws the same values
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   const uint32_t ndraw = kids_host ? 0u : 2u * nslots;          // (suspended nested particles carry their state: no draws)
   for (uint32_t i = 0; i < ndraw; i++) {
     ctx->h_draws[i] = rand_step(r) >> 1;
     r.calls++;
   }
-  HIPCHK(hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, st));
-  if (ndraw) HIPCHK(hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)ndraw * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d.rnd, &r, sizeof(r), hipMemcpyHostToDevice, st));
+  if (ndraw) HIPCHK(ctx, hipMemcpyAsync(ctx->d_draws, ctx->h_draws, (size_t)ndraw * 4, hipMemcpyHostToDevice, st));
   ctx->bs.tshift = -1;
-  HIPCHK(hipMemsetAsync(ctx->bs.ctrl + BC_NCHILD, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->bs.ctrl + BC_NCHILD, 0, 8, st));
   ctx->bs.relaxed = ctx->cfg.engine == SMX_ENGINE_RELAXED ? 1 : 0;
-  if (ctx->bs.relaxed) HIPCHK(hipMemsetAsync(ctx->bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // flood, flag and cascade lists start empty
+  if (ctx->bs.relaxed) HIPCHK(ctx, hipMemsetAsync(ctx->bs.ctrl + BC_NFLOOD, 0, (BC_LISTS_END - BC_NFLOOD) * 4, st));   // flood, flag and cascade lists start empty
   if (kids_host) {
-    if (ctx->kids_cap < nslots) { hipFree(ctx->d_kids); ctx->d_kids = nullptr; ctx->kids_cap = 0; HIPCHK(hipMalloc(&ctx->d_kids, (size_t)nslots * sizeof(BChild))); ctx->kids_cap = nslots; }
-    if (ctx->contains_cap < nslots) { hipFree(ctx->d_contains); ctx->d_contains = nullptr; ctx->contains_cap = 0; HIPCHK(hipMalloc(&ctx->d_contains, (size_t)nslots * 4)); ctx->contains_cap = nslots; }
-    HIPCHK(hipMemcpyAsync(ctx->d_kids, kids_host, (size_t)nslots * sizeof(BChild), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, ctx->mem.grow(ctx->d_kids, ctx->kids_cap, nslots, nslots));
+    HIPCHK(ctx, ctx->mem.grow(ctx->d_contains, ctx->contains_cap, nslots, nslots));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_kids, kids_host, (size_t)nslots * sizeof(BChild), hipMemcpyHostToDevice, st));
     if (contains_out) {
       hipLaunchKernelGGL(k_batch_child_contains, dim3((nslots + 63u) / 64u), dim3(64), 0, st, ctx->d_kids, nslots, ctx->d_contains);
-      HIPCHK(hipMemcpyAsync(contains_out, ctx->d_contains, (size_t)nslots * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(contains_out, ctx->d_contains, (size_t)nslots * 4, hipMemcpyDeviceToHost, st));
     }
   }
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   return 0;
 }
 static int d_compact(smx_ctx* ctx, uint32_t* nlive) {
   hipStream_t st = ctx->stream; const BatchShared& bs = ctx->bs; const uint32_t nslots = ctx->d_nslots;
-  HIPCHK(hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
+  HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NLIVE, 0, 4, st));
   if (nslots) LAUNCH_WIND_WATER(ctx->d_wind, k_batch_compact, dim3((nslots + 255u) / 256u), dim3(256), st, bs, nslots);
-  HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   *nlive = ctx->h_bctrl[BC_NLIVE];
   return 0;
 }
@@ -2736,7 +2713,7 @@ int smx_d_gen_spawn(smx_ctx* ctx, const uint32_t* contains_host, uint32_t* nlive
   hipStream_t st = ctx->stream; const uint32_t nslots = ctx->d_nslots;
   if (nslots == 0) { *nlive_local = 0; return 0; }
   const BChild* dk = ctx->d_first ? nullptr : ctx->d_kids;
-  if (dk && contains_host) HIPCHK(hipMemcpyAsync(ctx->d_contains, contains_host, (size_t)nslots * 4, hipMemcpyHostToDevice, st));
+  if (dk && contains_host) HIPCHK(ctx, hipMemcpyAsync(ctx->d_contains, contains_host, (size_t)nslots * 4, hipMemcpyHostToDevice, st));
   const unsigned nb = (nslots + 63u) / 64u;
   if (ctx->d_wind) hipLaunchKernelGGL(k_batch_spawn<true>, dim3(nb), dim3(64), 0, st, ctx->d, ctx->bs, nslots, dk, (const uint32_t*)nullptr);
   else hipLaunchKernelGGL(k_batch_spawn<false>, dim3(nb), dim3(64), 0, st, ctx->d, ctx->bs, nslots, dk, (const uint32_t*)(dk && contains_host ? ctx->d_contains : nullptr));
@@ -2757,15 +2734,15 @@ static int d_gen_end_impl(smx_ctx* ctx, void* children_out, uint32_t cap, uint32
     LAUNCH_WIND_WATER(ctx->d_wind, k_batch_counters, dim3(64), dim3(256), st, ctx->d, bs, nslots);
     ctx->d_nslots = 0;                                       // (the slots' counters are committed once, whatever happens below)
   }
-  HIPCHK(hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->h_bctrl, bs.ctrl, BC_COUNT * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   uint32_t nc = 0;
   if (const int rc = batch_check_ctrl(ctx, nc)) return rc;
   if (vec) { vec->resize(nc); children_out = vec->data(); cap = nc; }
   if (nc > cap) { ctx->err = "smx_d_gen_end: children buffer too small (call again with room for *n records)"; *n = nc; return -2; }
-  if (nc) HIPCHK(hipMemcpyAsync(children_out, bs.children, (size_t)nc * sizeof(BChild), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (nc) HIPCHK(ctx, hipMemcpyAsync(children_out, bs.children, (size_t)nc * sizeof(BChild), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemsetAsync(bs.ctrl + BC_NCHILD, 0, 8, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   *n = nc;
   ctx->batch_generations++;
   return 0;
@@ -2777,21 +2754,21 @@ int smx_d_pack_columns(smx_ctx* ctx, int32_t x0, int32_t x1, void* host_buf, uin
   if (batch_alloc(ctx, 1, false) || xbuf_alloc(ctx)) return -1;
   if (x0 < 0) x0 = 0; if (x1 > ctx->cfg.dimx) x1 = ctx->cfg.dimx;
   const int gx0 = x0 >> 2, gx1 = (x1 + 3) >> 2, gty = (ctx->cfg.dimy + 3) >> 2;
-  HIPCHK(hipMemsetAsync(ctx->d_xcur, 0, sizeof(XCursor), st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_xcur, 0, sizeof(XCursor), st));
   const long long nt = (long long)(gx1 - gx0) * gty;
   if (nt > 0) hipLaunchKernelGGL(k_strip_pack_columns, dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, st, ctx->d, ctx->bs, gx0, gx1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xoffs, ctx->xoffs_cap, ctx->d_xcur);
   XCursor c;
-  HIPCHK(hipMemcpyAsync(&c, ctx->d_xcur, sizeof(c), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(&c, ctx->d_xcur, sizeof(c), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   if (c.lost) { ctx->err = "smx_d_pack_columns: exchange buffer too small"; return -2; }
   const uint64_t total = 8 + 4ull * c.nrec + c.bytes;
   if (total > cap) { ctx->err = "smx_d_pack_columns: host buffer too small"; return -2; }
   uint8_t* hb = (uint8_t*)host_buf;
   const uint32_t nb = (uint32_t)c.bytes;
   memcpy(hb, &c.nrec, 4); memcpy(hb + 4, &nb, 4);
-  if (c.nrec) HIPCHK(hipMemcpyAsync(hb + 8, ctx->d_xoffs, 4ull * c.nrec, hipMemcpyDeviceToHost, st));
-  if (c.bytes) HIPCHK(hipMemcpyAsync(hb + 8 + 4ull * c.nrec, ctx->d_xdata, c.bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (c.nrec) HIPCHK(ctx, hipMemcpyAsync(hb + 8, ctx->d_xoffs, 4ull * c.nrec, hipMemcpyDeviceToHost, st));
+  if (c.bytes) HIPCHK(ctx, hipMemcpyAsync(hb + 8 + 4ull * c.nrec, ctx->d_xdata, c.bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   *bytes = total;
   return 0;
 }
@@ -2809,12 +2786,12 @@ int smx_d_unpack_columns(smx_ctx* ctx, const void* host_buf, uint64_t bytes) {
     memcpy(hd, hb + 8 + 4ull * nrec + o, 8);                  // {cell, section count}
     if (hd[0] >= ctx->ncells || (uint64_t)o + 24 + 32ull * hd[1] > nb) { ctx->err = "smx_d_unpack_columns: bad record"; return -2; }
   }
-  HIPCHK(hipMemcpyAsync(ctx->d_xoffs, hb + 8, 4ull * nrec, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(ctx->d_xdata, hb + 8 + 4ull * nrec, nb, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_xoffs, hb + 8, 4ull * nrec, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_xdata, hb + 8 + 4ull * nrec, nb, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_strip_unpack_columns, dim3((nrec + 63u) / 64u), dim3(64), 0, st, ctx->d, ctx->bs, ctx->d_xdata, ctx->d_xoffs, nrec, nb);
   hipLaunchKernelGGL(k_batch_merge_freed, dim3(1), dim3(256), 0, st, ctx->d, ctx->bs);
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 int smx_d_pack_particles(smx_ctx* ctx, int32_t x0, int32_t x1, void* host_buf, uint64_t cap, uint64_t* bytes) {
@@ -2822,16 +2799,16 @@ int smx_d_pack_particles(smx_ctx* ctx, int32_t x0, int32_t x1, void* host_buf, u
   if (xbuf_alloc(ctx)) return -1;
   const uint32_t nslots = ctx->d_nslots;
   const uint64_t rs = 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater));
-  HIPCHK(hipMemsetAsync(ctx->d_xcur, 0, sizeof(XCursor), st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_xcur, 0, sizeof(XCursor), st));
   if (nslots) LAUNCH_WIND_WATER(ctx->d_wind, k_strip_pack_particles, dim3((nslots + 255u) / 256u), dim3(256), st, ctx->bs, nslots, x0, x1, ctx->d_xdata, ctx->xdata_cap, ctx->d_xcur);
   XCursor c;
-  HIPCHK(hipMemcpyAsync(&c, ctx->d_xcur, sizeof(c), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipMemcpyAsync(&c, ctx->d_xcur, sizeof(c), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   if (c.lost || 4 + c.nrec * rs > cap) { ctx->err = "smx_d_pack_particles: buffer too small"; return -2; }
   uint8_t* hb = (uint8_t*)host_buf;
   memcpy(hb, &c.nrec, 4);
-  if (c.nrec) HIPCHK(hipMemcpyAsync(hb + 4, ctx->d_xdata, c.nrec * rs, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (c.nrec) HIPCHK(ctx, hipMemcpyAsync(hb + 4, ctx->d_xdata, c.nrec * rs, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   *bytes = 4 + c.nrec * rs;
   return 0;
 }
@@ -2844,25 +2821,25 @@ int smx_d_unpack_particles(smx_ctx* ctx, const void* host_buf, uint64_t bytes) {
   if (n == 0) return 0;
   const uint64_t rs = 4 + (ctx->d_wind ? sizeof(BWind) : sizeof(BWater));
   if (4 + n * rs > bytes || n * rs > ctx->xdata_cap) { ctx->err = "smx_d_unpack_particles: bad buffer"; return -2; }
-  HIPCHK(hipMemcpyAsync(ctx->d_xdata, hb + 4, n * rs, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_xdata, hb + 4, n * rs, hipMemcpyHostToDevice, st));
   LAUNCH_WIND_WATER(ctx->d_wind, k_strip_unpack_particles, dim3((n + 255u) / 256u), dim3(256), st, ctx->bs, ctx->d_xdata, n);
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
   return 0;
 }
 int smx_d_grid_begin(smx_ctx* ctx) {
   hipStream_t st = ctx->stream;
   if (batch_alloc(ctx, 1, false)) return -1;
   ctx->d_wind = false; ctx->d_nslots = 0; ctx->d_first = true;
-  HIPCHK(hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, st));
-  HIPCHK(hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, st));
-  HIPCHK(hipMemsetAsync(ctx->bs.ctrl + BC_NCHILD, 0, 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, st));
+  HIPCHK(ctx, hipMemsetAsync(ctx->bs.ctrl + BC_NCHILD, 0, 8, st));
   launch_classify(ctx);
   return 0;
 }
 int smx_d_grid_sweep_cols(smx_ctx* ctx, int32_t phase, int32_t x_lo, int32_t x_hi) {   // the tiles of the COLUMNS [x_lo, x_hi) (multiples of the tile size)
   const int rc = grid_sweep(ctx, phase, x_lo >> GRID_SHIFT, (x_hi + (1 << GRID_SHIFT) - 1) >> GRID_SHIFT);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 }  // extern "C"
@@ -2898,7 +2875,7 @@ int smx_tick_water(smx_ctx* ctx, int32_t nwater) {
   if (ctx->cfg.engine == SMX_ENGINE_SPECULATIVE) return spec_phase(ctx, nwater, false);
   PhaseTimer tk(ctx, PH_K_WATER);
   hipLaunchKernelGGL(k_water_serial, dim3(1), dim3(64), 0, ctx->stream, ctx->d, nwater);
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 int smx_grid_pass(smx_ctx* ctx) {
@@ -2906,11 +2883,11 @@ int smx_grid_pass(smx_ctx* ctx) {
   roctx_range rr("soilmx:grid");
   PhaseTimer t(ctx, PH_GRID);
   if (is_batched(ctx)) return batch_grid(ctx);
-  HIPCHK(hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, ctx->stream));
-  HIPCHK(hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active1, 0, (ctx->nw1 + 64) * 8, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.active2, 0, (ctx->nw2 + 64) * 8, ctx->stream));
   launch_classify(ctx);
   hipLaunchKernelGGL(k_grid_serial, dim3(1), dim3(64), 0, ctx->stream, ctx->d);
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 int smx_tick_wind(smx_ctx* ctx, int32_t nwind) {
@@ -2921,7 +2898,7 @@ int smx_tick_wind(smx_ctx* ctx, int32_t nwind) {
   if (ctx->cfg.engine == SMX_ENGINE_SPECULATIVE) return spec_phase(ctx, nwind, true);
   PhaseTimer tk(ctx, PH_K_WIND);
   hipLaunchKernelGGL(k_wind_serial, dim3(1), dim3(64), 0, ctx->stream, ctx->d, nwind);
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 int smx_map_frequency(smx_ctx* ctx) {
@@ -2932,12 +2909,12 @@ int smx_map_frequency(smx_ctx* ctx) {
   if (nb > 2048) nb = 2048;
   if (nb == 0) nb = 1;
   { PhaseTimer tk(ctx, PH_K_MAPFREQ); hipLaunchKernelGGL(k_map_frequency, dim3(nb), dim3(256), 0, ctx->stream, ctx->d.wfreq, ctx->d.wtrack, n4, n); }
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 int smx_reset_frequency(smx_ctx* ctx) {
   PhaseTimer t(ctx, PH_FREQ);
-  HIPCHK(hipMemsetAsync(ctx->d.wtrack, 0, ctx->ncells * 4, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d.wtrack, 0, ctx->ncells * 4, ctx->stream));
   return 0;
 }
 int smx_tick(smx_ctx* ctx, int32_t nwater, int32_t nwind, int32_t dowater, int32_t dowind) {   // SoilMachine.cpp:283-329
@@ -2948,8 +2925,8 @@ int smx_tick(smx_ctx* ctx, int32_t nwater, int32_t nwind, int32_t dowater, int32
   return 0;
 }
 int smx_sync(smx_ctx* ctx) {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 }  // extern "C"
@@ -2963,6 +2940,7 @@ constexpr int ENS_RING = 4;
 struct smx_ensemble : EventTimer {
   int device = 0;
   std::string err;
+  DevMem mem;                             // owns the tables, the observation scratch and the fork scratch
   std::vector<smx_ctx*> members;          // in order of addition
   uint32_t cap = 0;                       // members the tables are sized for
   EnsEntry* d_tab = nullptr;              // the table the kernels read
@@ -2976,36 +2954,21 @@ struct smx_ensemble : EventTimer {
   ForkScratch fork;                       // smx_ensemble_fork
 };
 
-#define EHIPCHK(call)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (call);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      e->err = std::string(#call) + ": " + hipGetErrorString(e_);                                     \
-      return -1;                                                                                      \
-    }                                                                                                 \
-  } while (0)
-
-static void ens_free_tables(smx_ensemble* e) {
-  hipFree(e->d_tab); e->d_tab = nullptr;
-  if (e->h_tab) hipHostFree(e->h_tab);
-  e->h_tab = nullptr; e->cap = 0;
-  for (int k = 0; k < ENS_RING; k++) e->h_used[k] = false;
-}
 static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
   if (n <= e->cap) return 0;
   uint32_t cap = e->cap ? e->cap : 64u;
   while (cap < n) cap *= 2u;
   if (cap > (uint32_t)SMX_ENSEMBLE_MAX_MEMBERS) cap = (uint32_t)SMX_ENSEMBLE_MAX_MEMBERS;
-  EHIPCHK(hipStreamSynchronize(e->stream));
-  EnsEntry* d = nullptr; EnsEntry* h = nullptr;
-  if (hipMalloc(&d, (size_t)cap * sizeof(EnsEntry)) != hipSuccess ||
-      hipHostMalloc(&h, (size_t)ENS_RING * cap * sizeof(EnsEntry), hipHostMallocDefault) != hipSuccess) {
-    hipFree(d);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  EnsEntry* d = nullptr; EnsEntry* h = nullptr;   // the new pair first: the old tables stay if either allocation fails
+  if (e->mem.dev(d, cap) != hipSuccess || e->mem.pinned(h, (size_t)ENS_RING * cap) != hipSuccess) {
+    e->mem.drop(d);
     (void)hipGetLastError();
     e->err = "smx_ensemble_add: out of memory for the member table";
     return -1;
   }
-  ens_free_tables(e);
+  e->mem.drop(e->d_tab); e->mem.drop(e->h_tab);
+  for (int k = 0; k < ENS_RING; k++) e->h_used[k] = false;
   e->d_tab = d; e->h_tab = h; e->cap = cap;
   return 0;
 }
@@ -3018,9 +2981,9 @@ int smx_ensemble_create(int32_t device, smx_ensemble** out) {
   *out = e;   // handed out even on failure so the caller can read smx_ensemble_last_error(); smx_ensemble_destroy() is safe
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { e->err = "no HIP device visible (the soilmx product path has no CPU fallback)"; return -3; }
-  EHIPCHK(hipSetDevice(device));
-  EHIPCHK(hipStreamCreate(&e->stream));
-  for (int k = 0; k < ENS_RING; k++) EHIPCHK(hipEventCreateWithFlags(&e->h_free[k], hipEventDisableTiming));
+  HIPCHK(e, hipSetDevice(device));
+  HIPCHK(e, hipStreamCreate(&e->stream));
+  for (int k = 0; k < ENS_RING; k++) HIPCHK(e, hipEventCreateWithFlags(&e->h_free[k], hipEventDisableTiming));
   return 0;
 }
 void smx_ensemble_destroy(smx_ensemble* e) {
@@ -3031,10 +2994,7 @@ void smx_ensemble_destroy(smx_ensemble* e) {
   drain_events(e);
   for (hipEvent_t ev : e->evpool) hipEventDestroy(ev);
   for (int k = 0; k < ENS_RING; k++) if (e->h_free[k]) hipEventDestroy(e->h_free[k]);
-  ens_free_tables(e);
-  hipFree(e->d_obs);
-  if (e->h_obs) hipHostFree(e->h_obs);
-  fork_free(e->fork);
+  e->mem.clear();
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3066,7 +3026,7 @@ int smx_ensemble_remove(smx_ensemble* e, smx_ctx* member) {
   if (!e) return -2;
   auto it = std::find(e->members.begin(), e->members.end(), member);
   if (!member || it == e->members.end()) { e->err = "smx_ensemble_remove: not a member of this ensemble"; return -2; }
-  EHIPCHK(hipStreamSynchronize(e->stream));   // (no queued tick still reads the member's state)
+  HIPCHK(e, hipStreamSynchronize(e->stream));   // (no queued tick still reads the member's state)
   e->members.erase(it);
   member->ensemble = nullptr;
   smx_destroy(member);
@@ -3089,7 +3049,7 @@ int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwi
   roctx_range rr("soilmx:ensemble");
   const int k = e->slot;
   e->slot = (e->slot + 1) % ENS_RING;
-  if (e->h_used[k]) EHIPCHK(hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
+  if (e->h_used[k]) HIPCHK(e, hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
   EnsEntry* h = e->h_tab + (size_t)k * e->cap;
   size_t cls_blocks = 1, freq_blocks = 1;
   for (uint32_t i = 0; i < nm; i++) {
@@ -3104,8 +3064,8 @@ int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwi
     cls_blocks = std::max(cls_blocks, t.classify8 ? (c->lcells / 8 + 255) / 256 : (c->lcells + 255) / 256);
     freq_blocks = std::max(freq_blocks, std::min<size_t>(2048, (c->ncells / 4 + 255) / 256));
   }
-  EHIPCHK(hipMemcpyAsync(e->d_tab, h, (size_t)nm * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
-  EHIPCHK(hipEventRecord(e->h_free[k], e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->d_tab, h, (size_t)nm * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipEventRecord(e->h_free[k], e->stream));
   e->h_used[k] = true;
   hipStream_t st = e->stream;
   const EnsEntry* tab = e->d_tab;
@@ -3132,25 +3092,25 @@ int smx_ensemble_tick(smx_ensemble* e, const int32_t* nwater, const int32_t* nwi
     PhaseTimer tk(e, PH_K_MAPFREQ);
     hipLaunchKernelGGL(k_ens_frequency, dim3((unsigned)freq_blocks, nm), dim3(256), 0, st, tab);
   }
-  EHIPCHK(hipGetLastError());
+  HIPCHK(e, hipGetLastError());
   return 0;
 }
 int smx_ensemble_sync(smx_ensemble* e) {
   if (!e || !e->stream) return -2;
-  EHIPCHK(hipStreamSynchronize(e->stream));
-  EHIPCHK(hipGetLastError());
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
   return 0;
 }
 int smx_ensemble_get_timing(smx_ensemble* e, smx_timing* out, uint64_t struct_size) {
   if (!e || !out || !e->stream) return -2;
-  EHIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   drain_events(e);
   memcpy(out, &e->timing, struct_size < sizeof(e->timing) ? (size_t)struct_size : sizeof(e->timing));
   return 0;
 }
 int smx_ensemble_timing_reset(smx_ensemble* e) {
   if (!e || !e->stream) return -2;
-  EHIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   drain_events(e);
   memset(&e->timing, 0, sizeof(e->timing));
   return 0;
@@ -3167,15 +3127,15 @@ static_assert(SMX_PLANE_HEIGHT == OBS_PLANE_HEIGHT && SMX_PLANE_WATER == OBS_PLA
 static int ens_upload_selection(smx_ensemble* e, const uint32_t* sel, uint32_t n) {
   const int k = e->slot;
   e->slot = (e->slot + 1) % ENS_RING;
-  if (e->h_used[k]) EHIPCHK(hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
+  if (e->h_used[k]) HIPCHK(e, hipEventSynchronize(e->h_free[k]));   // the copy out of this slot has run
   EnsEntry* h = e->h_tab + (size_t)k * e->cap;
   for (uint32_t i = 0; i < n; i++) {
     EnsEntry& t = h[i];
     t.s = e->members[sel ? sel[i] : i]->d;
     t.nwater = 0; t.nwind = 0; t.on = 0; t.classify8 = 0;
   }
-  EHIPCHK(hipMemcpyAsync(e->d_tab, h, (size_t)n * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
-  EHIPCHK(hipEventRecord(e->h_free[k], e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->d_tab, h, (size_t)n * sizeof(EnsEntry), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipEventRecord(e->h_free[k], e->stream));
   e->h_used[k] = true;
   return 0;
 }
@@ -3183,16 +3143,15 @@ static int ens_obs_reserve(smx_ensemble* e, size_t bytes) {
   if (bytes <= e->d_obs_cap && bytes <= e->h_obs_cap) return 0;
   size_t cap = e->d_obs_cap ? e->d_obs_cap : 4096;
   while (cap < bytes) cap *= 2;
-  EHIPCHK(hipStreamSynchronize(e->stream));
-  void* d = nullptr; void* h = nullptr;
-  if (hipMalloc(&d, cap) != hipSuccess || hipHostMalloc(&h, cap, hipHostMallocDefault) != hipSuccess) {
-    hipFree(d);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  void* d = nullptr; void* h = nullptr;   // (as ens_reserve: the old pair stays if either allocation fails)
+  if (e->mem.dev(d, cap) != hipSuccess || e->mem.pinned(h, cap) != hipSuccess) {
+    e->mem.drop(d);
     (void)hipGetLastError();
     e->err = "out of memory for the observation scratch (" + std::to_string(cap) + " bytes)";
     return -1;
   }
-  hipFree(e->d_obs);
-  if (e->h_obs) hipHostFree(e->h_obs);
+  e->mem.drop(e->d_obs); e->mem.drop(e->h_obs);
   e->d_obs = d; e->h_obs = h; e->d_obs_cap = cap; e->h_obs_cap = cap;
   return 0;
 }
@@ -3207,9 +3166,9 @@ int smx_ensemble_figures(smx_ensemble* e, smx_member_figures* out, uint64_t stru
   if (int rc = ens_obs_reserve(e, (size_t)nm * sizeof(ObsFigures))) { e->err = "smx_ensemble_figures: " + e->err; return rc; }
   if (int rc = ens_upload_selection(e, nullptr, nm)) return rc;
   hipLaunchKernelGGL(k_ens_figures, dim3(nm), dim3(FIG_LANES), 0, e->stream, e->d_tab, (ObsFigures*)e->d_obs);
-  EHIPCHK(hipGetLastError());
-  EHIPCHK(hipMemcpyAsync(e->h_obs, e->d_obs, (size_t)nm * sizeof(ObsFigures), hipMemcpyDeviceToHost, e->stream));
-  EHIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync(e->h_obs, e->d_obs, (size_t)nm * sizeof(ObsFigures), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   const ObsFigures* r = (const ObsFigures*)e->h_obs;
   for (uint32_t i = 0; i < nm; i++)
     if (r[i].corrupt) { e->err = "smx_ensemble_figures: corrupt section chain in member " + std::to_string(i); return -5; }
@@ -3267,9 +3226,9 @@ int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* whic
     case SMX_PLANE_WFREQ: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_WFREQ>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
     default: hipLaunchKernelGGL(k_ens_plane_stats<OBS_PLANE_WINDFREQ>, grid, block, 0, e->stream, e->d_tab, (uint32_t)n, cells, dp[0], dp[1], dp[2], dp[3], dnz); break;
   }
-  EHIPCHK(hipGetLastError());
-  EHIPCHK(hipMemcpyAsync(e->h_obs, e->d_obs, bytes, hipMemcpyDeviceToHost, e->stream));
-  EHIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync(e->h_obs, e->d_obs, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   const char* h = (const char*)e->h_obs;
   for (int k = 0; k < 4; k++) if (*want[k]) memcpy(*want[k], h + off[k], cells * sizeof(double));
   if (nonzero) memcpy(nonzero, h + off[4], cells * sizeof(uint32_t));
@@ -3279,30 +3238,23 @@ int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* whic
 // ---------------- forking a map on the device (smx_copy_state / smx_ensemble_fork; kernels: soil_fork.h) ----------------
 // Both calls: k_fork_count, rocPRIM's exclusive scan and one 24-byte copy back decide -4 / -5 before anything is written or allocated;
 // then k_fork_scatter and k_fork_planes write every destination (blockIdx.y) -- the same launches whatever the member count.
-static void fork_free(ForkScratch& f) {
-  hipFree(f.buried); hipFree(f.base); hipFree(f.flag); hipFree(f.tot); hipFree(f.temp); hipFree(f.tab);
-  f = ForkScratch();
-}
-static int fork_reserve(ForkScratch& f, size_t ncells, uint32_t ntab, hipStream_t st, std::string& err) {
+// (`m`: the owner the scratch lives in -- the destination context's or the ensemble's)
+static int fork_reserve(ForkScratch& f, DevMem& m, size_t ncells, uint32_t ntab, hipStream_t st, std::string& err) {
   bool ok = true;
   if (ncells > f.cells || !f.tot) {
     if (hipStreamSynchronize(st) != hipSuccess) ok = false;
-    hipFree(f.buried); hipFree(f.base); hipFree(f.flag); hipFree(f.temp); hipFree(f.tot);
-    f.buried = f.base = nullptr; f.flag = nullptr; f.temp = nullptr; f.tot = nullptr; f.cells = 0; f.temp_bytes = 0;
+    m.drop(f.buried); m.drop(f.base); m.drop(f.flag); m.drop(f.temp); m.drop(f.tot); f.cells = 0; f.temp_bytes = 0;
     size_t tb = 0;
     ok = ok && rocprim::exclusive_scan(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    ok = ok && hipMalloc(&f.buried, ncells * 4) == hipSuccess && hipMalloc(&f.base, ncells * 4) == hipSuccess && hipMalloc(&f.flag, ncells) == hipSuccess &&
-         hipMalloc(&f.tot, sizeof(ForkTotals)) == hipSuccess && hipMalloc(&f.temp, tb ? tb : 8) == hipSuccess;
+    ok = ok && m.dev(f.buried, ncells) == hipSuccess && m.dev(f.base, ncells) == hipSuccess && m.dev(f.flag, ncells) == hipSuccess &&
+         m.dev(f.tot, 1) == hipSuccess && m.dev(f.temp, tb ? tb : 8) == hipSuccess;
     if (ok) { f.cells = ncells; f.temp_bytes = tb; }
   }
-  if (ok && ntab > f.tab_cap) {
-    if (hipStreamSynchronize(st) != hipSuccess) ok = false;
-    hipFree(f.tab); f.tab = nullptr; f.tab_cap = 0;
-    ok = ok && hipMalloc(&f.tab, (size_t)ntab * sizeof(ForkDst)) == hipSuccess;
-    if (ok) f.tab_cap = ntab;
-  }
-  if (!ok) { (void)hipGetLastError(); fork_free(f); err = "out of device memory for the fork scratch"; return -1; }
-  return 0;
+  if (ok && ntab > f.tab_cap) ok = hipStreamSynchronize(st) == hipSuccess && m.grow(f.tab, f.tab_cap, ntab, ntab) == hipSuccess;
+  if (ok) return 0;
+  (void)hipGetLastError();   // nothing half-sized stays behind
+  m.drop(f.buried); m.drop(f.base); m.drop(f.flag); m.drop(f.tot); m.drop(f.temp); m.drop(f.tab);
+  f = ForkScratch(); err = "out of device memory for the fork scratch"; return -1;
 }
 static ForkSrc fork_src(const smx_ctx* src) {
   ForkSrc s;
@@ -3331,7 +3283,7 @@ static int fork_order(smx_ctx* src, hipStream_t st, std::string& err) {
   return 0;
 }
 // count + scan on `st`, the totals back, the verdict for a destination pool of dst_cap sections (the text goes to err)
-static int fork_measure(const char* who, smx_ctx* src, ForkScratch& f, hipStream_t st, uint64_t dst_cap, ForkTotals& tot, std::string& err) {
+static int fork_measure(const char* who, smx_ctx* src, ForkScratch& f, DevMem& m, hipStream_t st, uint64_t dst_cap, ForkTotals& tot, std::string& err) {
   const ForkSrc s = fork_src(src);
   const ForkTotals zero = {0ull, 0ull, FORK_NONE};
   const unsigned nb = (unsigned)((s.ncells + FORK_LANES - 1) / FORK_LANES);
@@ -3340,10 +3292,7 @@ static int fork_measure(const char* who, smx_ctx* src, ForkScratch& f, hipStream
   size_t tb = 0;   // (what THIS size needs: the scratch was sized for the largest map so far)
   ok = ok && rocprim::exclusive_scan(nullptr, tb, f.buried, f.base, 0u, (size_t)s.ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
   if (ok && tb > f.temp_bytes) {
-    ok = hipStreamSynchronize(st) == hipSuccess;
-    hipFree(f.temp); f.temp = nullptr; f.temp_bytes = 0;
-    ok = ok && hipMalloc(&f.temp, tb) == hipSuccess;
-    if (ok) f.temp_bytes = tb;
+    ok = hipStreamSynchronize(st) == hipSuccess && m.grow(f.temp, f.temp_bytes, tb, tb) == hipSuccess;
   }
   ok = ok && rocprim::exclusive_scan(f.temp, tb, f.buried, f.base, 0u, (size_t)s.ncells, rocprim::plus<uint32_t>(), st) == hipSuccess;
   ok = ok && hipMemcpyAsync(&tot, f.tot, sizeof(tot), hipMemcpyDeviceToHost, st) == hipSuccess;
@@ -3386,15 +3335,15 @@ int smx_copy_state(smx_ctx* dst, smx_ctx* src) {
   if (src->cfg.device != dst->cfg.device) { ctx->err = "smx_copy_state: dst and src live on different devices"; return -2; }
   if (!src->stream || !dst->stream) { ctx->err = "smx_copy_state: a context without a device"; return -3; }
   roctx_range rr("soilmx:copy_state");
-  HIPCHK(hipSetDevice(dst->cfg.device));
+  HIPCHK(ctx, hipSetDevice(dst->cfg.device));
   std::string why;
-  if (fork_reserve(dst->fork, src->ncells, 0, dst->stream, why)) { ctx->err = "smx_copy_state: " + why; return -1; }
+  if (fork_reserve(dst->fork, dst->mem, src->ncells, 0, dst->stream, why)) { ctx->err = "smx_copy_state: " + why; return -1; }
   if (fork_order(src, dst->stream, why)) { ctx->err = "smx_copy_state: " + why; return -1; }
   ForkTotals tot;
-  if (int rc = fork_measure("smx_copy_state", src, dst->fork, dst->stream, dst->cfg.pool_capacity, tot, why)) { ctx->err = why; return rc; }
+  if (int rc = fork_measure("smx_copy_state", src, dst->fork, dst->mem, dst->stream, dst->cfg.pool_capacity, tot, why)) { ctx->err = why; return rc; }
   fork_write(src, dst->fork, dst->stream, tot, nullptr, 1, fork_dst(dst, false, 0));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(dst->stream));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(dst->stream));
   fork_adopt(dst, src);
   return 0;
 }
@@ -3415,12 +3364,12 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
   if (pool_capacity) cfg.pool_capacity = pool_capacity;
   if (cfg.pool_capacity >= 0x7FFFFFFFull) { e->err = "smx_ensemble_fork: pool_capacity " + std::to_string(cfg.pool_capacity) + " is out of range"; return -2; }
   roctx_range rr("soilmx:ensemble_fork");
-  EHIPCHK(hipSetDevice(e->device));
+  HIPCHK(e, hipSetDevice(e->device));
   std::string why;
-  if (fork_reserve(e->fork, src->ncells, (uint32_t)n, e->stream, why)) { e->err = "smx_ensemble_fork: " + why; return -1; }
+  if (fork_reserve(e->fork, e->mem, src->ncells, (uint32_t)n, e->stream, why)) { e->err = "smx_ensemble_fork: " + why; return -1; }
   if (fork_order(src, e->stream, why)) { e->err = "smx_ensemble_fork: " + why; return -1; }
   ForkTotals tot;
-  if (int rc = fork_measure("smx_ensemble_fork", src, e->fork, e->stream, cfg.pool_capacity, tot, why)) { e->err = why; return rc; }
+  if (int rc = fork_measure("smx_ensemble_fork", src, e->fork, e->mem, e->stream, cfg.pool_capacity, tot, why)) { e->err = why; return rc; }
   if (int rc = ens_reserve(e, (uint32_t)e->members.size() + (uint32_t)n)) { e->err = "smx_ensemble_fork: " + e->err; return rc; }
   std::vector<smx_ctx*> made;
   std::vector<ForkDst> tab;
@@ -3461,8 +3410,8 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 // ---------------- point operations ----------------
 static int point_op(smx_ctx* ctx, const PointOp& o, double* out) {
   hipLaunchKernelGGL(k_point_op, dim3(1), dim3(64), 0, ctx->stream, ctx->d, o, ctx->d_scratch);
-  if (out) HIPCHK(hipMemcpyAsync(out, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (out) HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
 static bool inb(smx_ctx* ctx, int x, int y) {
@@ -3495,8 +3444,8 @@ int smx_seep(smx_ctx* ctx, int32_t x, int32_t y) {
 int smx_top(smx_ctx* ctx, int32_t x, int32_t y, uint32_t* type, double* size, double* floor, double* sat, int32_t* empty) {
   if (!inb(ctx, x, y)) return -2;
   Sec r;
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.cells + ((size_t)x * ctx->cfg.dimy + y), sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.cells + ((size_t)x * ctx->cfg.dimy + y), sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   const bool e = r.type == EMPTY;
   if (empty) *empty = e ? 1 : 0;
   if (type) *type = e ? 0u : r.type;
@@ -3511,11 +3460,11 @@ int smx_digest(smx_ctx* ctx, double* sumh, uint64_t* nsec, uint64_t* typehash) {
   const size_t n = ctx->lcells;
   const uint64_t cap = ctx->cfg.pool_capacity;
   std::vector<Sec> cells(n);
-  HIPCHK(hipMemcpyAsync(cells.data(), ctx->cells_alloc, n * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cells.data(), ctx->cells_alloc, n * sizeof(Sec), hipMemcpyDeviceToHost, ctx->stream));
   // {type, prev} = the last 8 bytes of every 32-byte pool record: one strided 2D copy instead of the whole pool
   std::vector<uint64_t> tp(cap);
-  HIPCHK(hipMemcpy2DAsync(tp.data(), 8, reinterpret_cast<const char*>(ctx->d.pool) + 24, sizeof(Sec), 8, cap, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy2DAsync(tp.data(), 8, reinterpret_cast<const char*>(ctx->d.pool) + 24, sizeof(Sec), 8, cap, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   double sh = 0.0; uint64_t ns = 0, h = 1469598103934665603ull;
   for (size_t c = 0; c < n; c++) {
     const Sec& t = cells[c];
@@ -3542,9 +3491,9 @@ int smx_digest(smx_ctx* ctx, double* sumh, uint64_t* nsec, uint64_t* typehash) {
 int smx_get_counters_sized(smx_ctx* ctx, smx_counters* out, uint64_t struct_size) {
   unsigned long long c[C_COUNT];
   RandState r;
-  HIPCHK(hipMemcpyAsync(c, ctx->d.ctr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(c, ctx->d.ctr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&r, ctx->d.rnd, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   smx_counters t;
   memset(&t, 0, sizeof(t));
   t.steps_water_top = c[C_STEPS_WATER_TOP]; t.steps_water_all = c[C_STEPS_WATER_ALL]; t.steps_wind = c[C_STEPS_WIND];
@@ -3561,14 +3510,14 @@ int smx_get_counters_sized(smx_ctx* ctx, smx_counters* out, uint64_t struct_size
 }
 int smx_get_counters(smx_ctx* ctx, smx_counters* out) { return smx_get_counters_sized(ctx, out, 16 * sizeof(uint64_t)); }   // the layout of rounds 1-3
 int smx_get_timing_sized(smx_ctx* ctx, smx_timing* out, uint64_t struct_size) {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   drain_events(ctx);
   memcpy(out, &ctx->timing, struct_size < sizeof(ctx->timing) ? (size_t)struct_size : sizeof(ctx->timing));
   return 0;
 }
 int smx_get_timing(smx_ctx* ctx, smx_timing* out) { return smx_get_timing_sized(ctx, out, 144); }   // the layout of rounds 2-4
 int smx_timing_reset(smx_ctx* ctx) {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   drain_events(ctx);
   memset(&ctx->timing, 0, sizeof(ctx->timing));
   return 0;
@@ -3579,17 +3528,12 @@ int smx_timing_reset(smx_ctx* ctx) {
 #include "soil_strips_host.h"
 
 // ---------------- LBM wind: lbmwind.h:75-197 + shader/LBM/*.cs, shader/move.cs -> soil_lbm.h ----------------
-#define LBMCHK(call)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (call);                                                                           \
-    if (e_ != hipSuccess) { l->err = std::string(#call) + ": " + hipGetErrorString(e_); return -1; }  \
-  } while (0)
 extern "C" {
 void smx_lbm_destroy(smx_lbm* l) {
   if (!l) return;
   hipSetDevice(l->device);
   if (l->stream) hipStreamSynchronize(l->stream);
-  hipFree(l->f[0]); hipFree(l->f[1]); hipFree(l->B); hipFree(l->rho); hipFree(l->v);
+  l->mem.clear();
   if (l->ev0) hipEventDestroy(l->ev0); if (l->ev1) hipEventDestroy(l->ev1);
   if (l->stream) hipStreamDestroy(l->stream);
   delete l;
@@ -3604,22 +3548,22 @@ int smx_lbm_create(int32_t nx, int32_t ny, int32_t nz, int32_t device, smx_lbm**
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { l->err = "no HIP device visible (soilmx has no CPU fallback)"; return -3; }
   l->device = device; l->d.nx = nx; l->d.ny = ny; l->d.nz = nz; l->d.n = (unsigned long long)nx * ny * nz;
   l->k = make_lbm_consts();
-  LBMCHK(hipSetDevice(device));
-  LBMCHK(hipStreamCreate(&l->stream));
-  LBMCHK(hipEventCreate(&l->ev0)); LBMCHK(hipEventCreate(&l->ev1));
+  HIPCHK(l, hipSetDevice(device));
+  HIPCHK(l, hipStreamCreate(&l->stream));
+  HIPCHK(l, hipEventCreate(&l->ev0)); HIPCHK(l, hipEventCreate(&l->ev1));
   const size_t n = (size_t)l->d.n;
-  LBMCHK(hipMalloc(&l->f[0], n * LQ * 4)); LBMCHK(hipMalloc(&l->f[1], n * LQ * 4));
-  LBMCHK(hipMalloc(&l->B, n * 4)); LBMCHK(hipMalloc(&l->rho, n * 4)); LBMCHK(hipMalloc(&l->v, n * 16));
-  LBMCHK(hipMemsetAsync(l->f[0], 0, n * LQ * 4, l->stream)); LBMCHK(hipMemsetAsync(l->f[1], 0, n * LQ * 4, l->stream));
-  LBMCHK(hipMemsetAsync(l->B, 0, n * 4, l->stream)); LBMCHK(hipMemsetAsync(l->rho, 0, n * 4, l->stream)); LBMCHK(hipMemsetAsync(l->v, 0, n * 16, l->stream));
-  LBMCHK(hipStreamSynchronize(l->stream));
+  HIPCHK(l, l->mem.dev(l->f[0], n * LQ)); HIPCHK(l, l->mem.dev(l->f[1], n * LQ));
+  HIPCHK(l, l->mem.dev(l->B, n)); HIPCHK(l, l->mem.dev(l->rho, n)); HIPCHK(l, l->mem.dev(l->v, n));
+  HIPCHK(l, hipMemsetAsync(l->f[0], 0, n * LQ * 4, l->stream)); HIPCHK(l, hipMemsetAsync(l->f[1], 0, n * LQ * 4, l->stream));
+  HIPCHK(l, hipMemsetAsync(l->B, 0, n * 4, l->stream)); HIPCHK(l, hipMemsetAsync(l->rho, 0, n * 4, l->stream)); HIPCHK(l, hipMemsetAsync(l->v, 0, n * 16, l->stream));
+  HIPCHK(l, hipStreamSynchronize(l->stream));
   return 0;
 }
 static unsigned lbm_grid(const smx_lbm* l) { const unsigned long long nb = (l->d.n + 255ull) / 256ull; return (unsigned)((nb + 7ull) / 8ull * 8ull); }
 int smx_lbm_set_boundary(smx_lbm* l, const float* b) {
-  LBMCHK(hipSetDevice(l->device));
-  LBMCHK(hipMemcpyAsync(l->B, b, (size_t)l->d.n * 4, hipMemcpyHostToDevice, l->stream));
-  LBMCHK(hipStreamSynchronize(l->stream));
+  HIPCHK(l, hipSetDevice(l->device));
+  HIPCHK(l, hipMemcpyAsync(l->B, b, (size_t)l->d.n * 4, hipMemcpyHostToDevice, l->stream));
+  HIPCHK(l, hipStreamSynchronize(l->stream));
   return 0;
 }
 int smx_lbm_boundary_from_map(smx_lbm* l, smx_ctx* ctx, float sx, float sy, float sz) {
@@ -3629,25 +3573,25 @@ int smx_lbm_boundary_from_map(smx_lbm* l, smx_ctx* ctx, float sx, float sy, floa
   if ((int)(sx * (float)(l->d.nx - 1)) >= ctx->cfg.dimx || (int)(sz * (float)(l->d.nz - 1)) >= ctx->cfg.dimy || sx < 0.f || sz < 0.f) {
     l->err = "smx_lbm_boundary_from_map: the scaled lattice does not fit the map"; return -2;
   }
-  if (ctx->plane_cap < ctx->ncells * 8) { hipFree(ctx->d_plane); ctx->d_plane = nullptr; ctx->plane_cap = 0; HIPCHK(hipMalloc(&ctx->d_plane, ctx->ncells * 8)); ctx->plane_cap = ctx->ncells * 8; }
+  HIPCHK(l, ctx->mem.grow(ctx->d_plane, ctx->plane_cap, ctx->ncells * 8, ctx->ncells * 8));   // (failures are the lattice's: the caller reads smx_lbm_last_error)
   hipLaunchKernelGGL(k_heights, dim3((unsigned)((ctx->ncells + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d, (double*)ctx->d_plane);
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(l, hipStreamSynchronize(ctx->stream));
   hipLaunchKernelGGL(k_lbm_boundary_from_heights, dim3((unsigned)((l->d.n + 255ull) / 256ull)), dim3(256), 0, l->stream, l->d, (const double*)ctx->d_plane,
                      ctx->cfg.dimy, sx, sy, sz, ctx->cfg.scale, l->B);
-  LBMCHK(hipStreamSynchronize(l->stream));
+  HIPCHK(l, hipStreamSynchronize(l->stream));
   return 0;
 }
 int smx_lbm_initialize(smx_lbm* l) {
-  LBMCHK(hipSetDevice(l->device));
+  HIPCHK(l, hipSetDevice(l->device));
   l->cur = 0;
   hipLaunchKernelGGL(k_lbm_init, dim3(lbm_grid(l)), dim3(256), 0, l->stream, l->d, l->k, l->B, l->f[0], l->rho, l->v);
-  LBMCHK(hipGetLastError());
+  HIPCHK(l, hipGetLastError());
   return 0;
 }
 int smx_lbm_step(smx_lbm* l, int32_t n) {
-  LBMCHK(hipSetDevice(l->device));
+  HIPCHK(l, hipSetDevice(l->device));
   if (n <= 0) return 0;
-  LBMCHK(hipEventRecord(l->ev0, l->stream));
+  HIPCHK(l, hipEventRecord(l->ev0, l->stream));
   static const int variant = (env_flag("SMX_LBM_NT") ? 1 : 0) | (env_flag("SMX_LBM_XCD") ? 2 : 0);   // measured switches (profiles/r02_lbm_bench.log); results do not depend on them
   for (int s = 0; s < n; s++) {
     const dim3 g(lbm_grid(l)), t(256);
@@ -3660,9 +3604,9 @@ int smx_lbm_step(smx_lbm* l, int32_t n) {
     }
     l->cur ^= 1;
   }
-  LBMCHK(hipEventRecord(l->ev1, l->stream));
-  LBMCHK(hipGetLastError());
-  LBMCHK(hipEventSynchronize(l->ev1));
+  HIPCHK(l, hipEventRecord(l->ev1, l->stream));
+  HIPCHK(l, hipGetLastError());
+  HIPCHK(l, hipEventSynchronize(l->ev1));
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, l->ev0, l->ev1) == hipSuccess) { l->ms_steps += ms; l->steps += (unsigned long long)n; }
   return 0;
@@ -3674,40 +3618,40 @@ int smx_lbm_get_timing(smx_lbm* l, double* ms_steps, uint64_t* steps, int32_t re
   return 0;
 }
 int smx_lbm_read(smx_lbm* l, float* rho, float* v4, float* f_aos) {
-  LBMCHK(hipSetDevice(l->device));
+  HIPCHK(l, hipSetDevice(l->device));
   const size_t n = (size_t)l->d.n;
-  if (rho) LBMCHK(hipMemcpyAsync(rho, l->rho, n * 4, hipMemcpyDeviceToHost, l->stream));
-  if (v4) LBMCHK(hipMemcpyAsync(v4, l->v, n * 16, hipMemcpyDeviceToHost, l->stream));
+  if (rho) HIPCHK(l, hipMemcpyAsync(rho, l->rho, n * 4, hipMemcpyDeviceToHost, l->stream));
+  if (v4) HIPCHK(l, hipMemcpyAsync(v4, l->v, n * 16, hipMemcpyDeviceToHost, l->stream));
   if (f_aos) {                                                // the spare lattice is scratch between steps (a step writes every slot of it)
     float* tmp = l->f[l->cur ^ 1];
     hipLaunchKernelGGL(k_lbm_to_aos, dim3((unsigned)((n * LQ + 255) / 256)), dim3(256), 0, l->stream, l->d, l->f[l->cur], tmp);
-    LBMCHK(hipMemcpyAsync(f_aos, tmp, n * LQ * 4, hipMemcpyDeviceToHost, l->stream));
+    HIPCHK(l, hipMemcpyAsync(f_aos, tmp, n * LQ * 4, hipMemcpyDeviceToHost, l->stream));
   }
-  LBMCHK(hipStreamSynchronize(l->stream));
+  HIPCHK(l, hipStreamSynchronize(l->stream));
   return 0;
 }
 int smx_lbm_write_f(smx_lbm* l, const float* f_aos) {
-  LBMCHK(hipSetDevice(l->device));
+  HIPCHK(l, hipSetDevice(l->device));
   const size_t n = (size_t)l->d.n;
   float* stage = nullptr;
-  LBMCHK(hipMalloc(&stage, n * LQ * 4));
+  HIPCHK(l, l->mem.dev(stage, n * LQ));
   hipError_t e = hipMemcpyAsync(stage, f_aos, n * LQ * 4, hipMemcpyHostToDevice, l->stream);
   hipLaunchKernelGGL(k_lbm_from_aos, dim3((unsigned)((n * LQ + 255) / 256)), dim3(256), 0, l->stream, l->d, stage, l->f[l->cur]);
   if (e == hipSuccess) e = hipStreamSynchronize(l->stream);
-  hipFree(stage);
+  l->mem.drop(stage);
   if (e != hipSuccess) { l->err = hipGetErrorString(e); return -1; }
   return 0;
 }
 int smx_lbm_move(smx_lbm* l, float* pos4, int32_t n) {
-  LBMCHK(hipSetDevice(l->device));
+  HIPCHK(l, hipSetDevice(l->device));
   if (n <= 0) return 0;
   float4* d = nullptr;
-  LBMCHK(hipMalloc(&d, (size_t)n * 16));
+  HIPCHK(l, l->mem.dev(d, (size_t)n));
   hipError_t e = hipMemcpyAsync(d, pos4, (size_t)n * 16, hipMemcpyHostToDevice, l->stream);
   hipLaunchKernelGGL(k_lbm_move, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, l->stream, l->d, l->v, d, n);
   if (e == hipSuccess) e = hipMemcpyAsync(pos4, d, (size_t)n * 16, hipMemcpyDeviceToHost, l->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(l->stream);
-  hipFree(d);
+  l->mem.drop(d);
   if (e != hipSuccess) { l->err = hipGetErrorString(e); return -1; }
   return 0;
 }
