@@ -257,6 +257,42 @@ int smx_ensemble_plane_stats(smx_ensemble* e, int32_t plane, const int32_t* whic
  * fork that runs out of device memory returns < 0 and frees every member it had made. */
 int smx_copy_state(smx_ctx* dst, smx_ctx* src);
 int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_capacity, const uint32_t* seeds, smx_ctx** members /* n handles out */);
+/* ---- the lake census: which lakes are there, how big, how deep, how level -- connected wet cells labelled on the device ----
+ * A WET CELL is a non-empty column whose top section is Air (type 0), the rule of smx_member_figures.wet_cells: empty columns and
+ * buried water are dry. A LAKE is a maximal set of wet cells connected through the EIGHT neighbours, the neighbourhood
+ * WaterParticle::cascade levels water over (source/particle/water.h:155-164); cells do not connect across the map border. A lake's
+ * IDENTITY is its smallest cell index x*dimy+y, first_cell; lakes are listed in ascending first_cell, and lake k of that order has
+ * RANK k. Every field of a record is an integer or an order-free extreme: nothing depends on a summation order, and a host
+ * restatement reproduces each bit.
+ *   volume_q40   sum over the lake's cells of floor(size * 2^40), size = the top Air section's size: an exact integer (the scaling
+ *                and the floor are exact in f64). volume_q40 * 2^-40 lies below the exact sum of the sizes by less than cells * 2^-40.
+ *   level_min / level_max   extremes of Layermap::height (floor + size) over the lake: equal on a levelled lake, their spread says
+ *                how far the lake is from settled.     depth_max   the largest top-section size.     For all three, -0 < +0.
+ *   x0, y0, x1, y1   the inclusive bounding box.
+ *   flags        bit 0: a cell of the lake lies on the map border. bit 1: the volume is unreliable -- a size was not finite, was
+ *                negative or was >= 2^24 (such a cell contributes 0), or the 64-bit sum wrapped.
+ * A caller passes sizeof(ITS struct) and gets that prefix of each record, as with smx_member_figures. */
+typedef struct smx_lake {                /* 64 bytes */
+  uint32_t first_cell, cells;
+  uint64_t volume_q40;
+  double   level_min, level_max;
+  double   depth_max;
+  uint16_t x0, y0, x1, y1;
+  uint32_t flags;
+  uint32_t reserved[3];                  /* written as 0 */
+} smx_lake;
+/* *nlakes = the number of lakes, whatever cap is; the first min(cap, *nlakes) records are written in rank order, record k at byte
+ * k * struct_size; out may be NULL when cap is 0 (counting only). labels (NULL = skip): dimx*dimy words in cell order, the rank of
+ * the cell's lake or 0xFFFFFFFF for a dry cell. In the ensemble call member i's records start at out + i * cap_per_member records
+ * and nlakes holds one count per member in member order; an empty ensemble: 0, nothing written.
+ * Both calls run on the context's / the ensemble's stream (they see every tick queued before them), launch the same kernels
+ * whatever the map holds and however many members there are (one table upload; k_lake_tiles, k_lake_merge, k_lake_flatten, a
+ * prefix sum, k_lake_stats; the RESULTS copied back), synchronise once and change neither a map nor a counter. Only the 32-byte
+ * top records are read, so a context of any engine serves; a strip context, a null context and struct_size == 0 return -2. The
+ * scratch -- two u32 planes per cell and the records asked for -- is allocated by the first census and kept; an allocation that
+ * fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels);
+int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nlakes);
 
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */

@@ -80,6 +80,21 @@ class MemberFigures(C.Structure):
         return d
 
 
+class Lake(C.Structure):
+    """smx_lake: one lake of smx_lakes / smx_ensemble_lakes (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("volume_q40", C.c_uint64), ("level_min", C.c_double),
+                ("level_max", C.c_double), ("depth_max", C.c_double), ("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16),
+                ("y1", C.c_uint16), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        d["volume"] = int(self.volume_q40) * 2.0 ** -40      # below the exact sum of the sizes by less than cells * 2^-40
+        return d
+
+
+LAKE_DRY = 0xFFFFFFFF                  # a dry cell of the label plane
+LAKE_BORDER, LAKE_VOLUME_UNRELIABLE = 1, 2                             # smx_lake.flags
+
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
 
@@ -99,6 +114,7 @@ SYMBOLS = [
     "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
     "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
+    "smx_lakes", "smx_ensemble_lakes",
     "smx_switches",
 ]
 
@@ -219,6 +235,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_plane_stats.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.smx_copy_state.argtypes = [vp, vp]
     L.smx_ensemble_fork.argtypes = [vp, vp, i32, u64, vp, C.POINTER(vp)]
+    L.smx_lakes.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp]
+    L.smx_ensemble_lakes.argtypes = [vp, vp, u64, u32, vp]
     L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)

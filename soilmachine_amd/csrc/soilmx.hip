@@ -44,6 +44,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_lbm.h"
 #include "soil_observe.h"
 #include "soil_fork.h"
+#include "soil_lakes.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
 
@@ -366,6 +367,44 @@ __global__ void __launch_bounds__(256) k_fork_planes(ForkSrc s, const ForkDst* _
   const ForkDst d = tab ? tab[blockIdx.y] : one;
   fork_planes_lane(s, d, (uint64_t)blockIdx.x * 256 + threadIdx.x, (uint64_t)gridDim.x * 256);
 }
+
+// ---------------- the lake census (smx_lakes / smx_ensemble_lakes; bodies: soil_lakes.h) ----------------
+// Member blockIdx.y of the table, workgroup blockIdx.x of ITS tiles / cells (the grid is sized for the largest member). A tile is 16
+// columns of 64 cells: a wavefront reads 64 consecutive 32-byte records, the tile's labels are 4 KB of LDS; the statistics table
+// holds 512 cells' worth of lakes (30 KB of LDS).
+constexpr int LAKE_TX = 16, LAKE_TY = 64, LAKE_LANES = 256, LAKE_SLOTS = 512;
+__global__ void __launch_bounds__(LAKE_LANES) k_lake_tiles(const LakeMember* __restrict__ tab, uint32_t* A, LakeAcc* acc) {
+  __shared__ uint32_t lab[LAKE_TX * LAKE_TY];
+  const LakeMember m = tab[blockIdx.y];
+  const uint32_t nt = lake_tiles(m, LAKE_TX, LAKE_TY);
+  if (blockIdx.x >= nt) return;
+  ObsGroup g;
+  lake_tile_group<LAKE_TX, LAKE_TY>(m, g, blockIdx.x, nt, lab, A, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_lake_merge(const LakeMember* __restrict__ tab, uint32_t* A) {
+  const LakeMember m = tab[blockIdx.y];
+  if (blockIdx.x >= lake_tiles(m, LAKE_TX, LAKE_TY)) return;
+  ObsGroup g;
+  lake_merge_group<LAKE_TX, LAKE_TY>(m, g, blockIdx.x, A);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_lake_flatten(const LakeMember* __restrict__ tab, uint32_t* A) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  lake_flatten_group(m, g, blockIdx.x, A);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_lake_stats(const LakeMember* __restrict__ tab, uint32_t* A, const uint32_t* __restrict__ B, LakeAcc* acc,
+                                                           uint32_t* nlakes) {
+  __shared__ LakeTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  lake_stats_group<LAKE_SLOTS>(m, g, blockIdx.x, t, A, B, acc, nlakes + blockIdx.y);
+}
+struct LakeMarkFn {   // the scan's input: 1 where plane word g is a root
+  const uint32_t* A;
+  __host__ __device__ uint32_t operator()(uint32_t g) const { return lake_mark(A, g); }
+};
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
 // Particles per wave (env SMX_SPEC_LANES, default 1): a phase has only ~10^3 particles while the chip has 1024
@@ -1435,6 +1474,15 @@ struct ForkScratch {
   ForkDst* tab = nullptr; uint32_t tab_cap = 0;
 };
 
+// smx_lakes / smx_ensemble_lakes: the two u32 planes, rocPRIM's temporary storage, the member table with its pinned source and the
+// results with their pinned landing place (allocated by the first census, grown on demand, kept with the context or the ensemble)
+struct LakeScratch {
+  uint32_t* A = nullptr; uint32_t* B = nullptr; size_t words = 0;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
+  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
+};
+
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
@@ -1492,6 +1540,7 @@ struct smx_ctx : EventTimer {
   uint32_t* d_tdone = nullptr; uint32_t* d_tpend[2] = {nullptr, nullptr}; uint32_t* d_tcount = nullptr; uint32_t* h_tcount = nullptr; void* d_tsort = nullptr; size_t tsort_bytes = 0; uint32_t tsort_cap = 0;   // grid pass: tile states, pending lists
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
+  LakeScratch lakes;                  // smx_lakes
 };
 
 // a failed HIP call: its text and the runtime's message go to the `err` of `obj` (a context, an ensemble, a lattice), the function returns -1
@@ -2952,6 +3001,7 @@ struct smx_ensemble : EventTimer {
   void* d_obs = nullptr; size_t d_obs_cap = 0;
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
+  LakeScratch lakes;                      // smx_ensemble_lakes
 };
 
 static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
@@ -3405,6 +3455,124 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
     members[i] = made[(size_t)i];
   }
   return 0;
+}
+
+// ---------------- the lake census (smx_lakes / smx_ensemble_lakes; kernels: soil_lakes.h) ----------------
+// One path for both calls: the maps ms[0..nm) share the two planes (member i at words [off_i, off_i + cells_i)), one table upload,
+// k_lake_tiles, k_lake_merge, k_lake_flatten, rocPRIM's exclusive scan of the root marks, k_lake_stats, the counts and the records
+// (and the label plane, where asked for) copied back, one synchronisation -- whatever the maps hold and however many there are.
+// (`mem`: the owner the scratch lives in -- the context's or the ensemble's)
+static_assert(sizeof(smx_lake) == 64 && sizeof(LakeRec) == sizeof(smx_lake) && offsetof(smx_lake, flags) == offsetof(LakeRec, flags), "smx_lake layout");
+static void lakes_drop(LakeScratch& k, DevMem& mem) {
+  mem.drop(k.A); mem.drop(k.B); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
+  k = LakeScratch();
+}
+static int lakes_run(const char* who, LakeScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_lake* out, uint64_t struct_size,
+                     uint32_t cap, uint32_t* nlakes, uint32_t* labels, std::string& err) {
+  std::vector<LakeMember> tab(nm);
+  uint64_t words = 0, nrec = 0;
+  size_t tiles = 1, flat = 1, stat = 1;
+  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = ms[i];
+    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side (the bounding boxes are 16-bit)"; return -2; }
+    LakeMember& m = tab[i];
+    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
+    const uint64_t most = (uint64_t)((m.dimx + 1) / 2) * (uint64_t)((m.dimy + 1) / 2);   // (the four cells of a 2 x 2 block are one lake)
+    m.cap = (uint32_t)std::min<uint64_t>(cap, most);
+    words += (uint64_t)c->ncells; nrec += m.cap;
+    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one census"; return -2; }
+    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
+    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
+    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
+  }
+  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(LakeAcc);
+  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.A});
+  size_t tb = 0;
+  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
+  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
+    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
+    if (ok && words > k.words) {
+      mem.drop(k.A); mem.drop(k.B); k.words = 0;
+      ok = mem.dev(k.A, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess;
+      if (ok) k.words = (size_t)words;
+    }
+    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
+    if (ok && nm > k.tab_cap) {
+      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
+      ok = mem.dev(k.d_tab, nm) == hipSuccess && mem.pinned(k.h_tab, nm) == hipSuccess;
+      if (ok) k.tab_cap = nm;
+    }
+    if (ok && res_bytes > k.res_cap) {
+      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
+      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
+      if (ok) k.res_cap = res_bytes;
+    }
+    if (!ok) {
+      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
+      lakes_drop(k, mem);
+      err = std::string(who) + ": out of memory for the census scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
+      return -1;
+    }
+  }
+  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
+  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
+  LakeAcc* acc = reinterpret_cast<LakeAcc*>(k.d_res + rec_at);
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_lake_tiles, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A, acc);
+    hipLaunchKernelGGL(k_lake_merge, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A);
+    hipLaunchKernelGGL(k_lake_flatten, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A);
+    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.A});
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_lake_stats, dim3((unsigned)stat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A, k.B, acc, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && labels) ok = hipMemcpyAsync(labels, k.A, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;   // (smx_lakes only: one map, off = 0)
+  const hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the census failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
+  const LakeAcc* a = reinterpret_cast<const LakeAcc*>(k.h_res + rec_at);
+  const size_t take = struct_size < sizeof(smx_lake) ? (size_t)struct_size : sizeof(smx_lake);
+  for (uint32_t i = 0; i < nm; i++) {
+    nlakes[i] = n[i];
+    const uint32_t w = std::min(n[i], tab[i].cap);   // (= min(cap, n): a map holds at most tab[i].cap lakes where cap was cut)
+    for (uint32_t r = 0; r < w; r++) {
+      LakeRec rec;
+      lake_finish(a[tab[i].rec0 + r], rec);
+      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
+    }
+  }
+  return 0;
+}
+
+int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
+  if (!ctx) return -2;
+  FULLMAP("smx_lakes")
+  if (struct_size == 0) { ctx->err = "smx_lakes: struct_size is 0 (pass sizeof(smx_lake) of the header you compiled against)"; return -2; }
+  if (!nlakes) { ctx->err = "smx_lakes: nlakes is null"; return -2; }
+  if (!out && cap) { ctx->err = "smx_lakes: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_lakes: a context without a device"; return -3; }
+  roctx_range rr("soilmx:lakes");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return lakes_run("smx_lakes", ctx->lakes, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nlakes, labels, ctx->err);
+}
+int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nlakes) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_lakes: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_lakes: struct_size is 0 (pass sizeof(smx_lake) of the header you compiled against)"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!nlakes) { e->err = "smx_ensemble_lakes: nlakes is null (one count per member)"; return -2; }
+  if (!out && cap_per_member) { e->err = "smx_ensemble_lakes: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  roctx_range rr("soilmx:ensemble_lakes");
+  HIPCHK(e, hipSetDevice(e->device));
+  return lakes_run("smx_ensemble_lakes", e->lakes, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nlakes, nullptr, e->err);
 }
 
 // ---------------- point operations ----------------

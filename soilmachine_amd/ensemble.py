@@ -230,6 +230,30 @@ class Ensemble:
                                                   capi.ptr(out.get("vmin")), capi.ptr(out.get("vmax")), capi.ptr(out.get("nonzero"))))
         return out
 
+    def lakes(self, cap: int | None = None) -> list:
+        """The lake census of every member (``smx_ensemble_lakes``: the same launches whatever the member count): one list of lake
+        dicts per member, in member order, each as ``Layermap.lakes()`` gives it. ``cap`` None: two calls, a count with no records
+        and the fetch sized by the largest count; else at most ``cap`` lakes per member. Members may differ in size."""
+        self._check_members()
+        n = len(self.members)
+        if n == 0:
+            return []
+        counts = np.zeros(n, np.uint32)
+        if cap is None:
+            self._chk(self.L.smx_ensemble_lakes(self.h, None, C.sizeof(capi.Lake), 0, capi.ptr(counts)))
+            cap = int(counts.max())
+        cap = int(cap)
+        out = (capi.Lake * max(1, n * cap))()
+        self._chk(self.L.smx_ensemble_lakes(self.h, out, C.sizeof(capi.Lake), cap, capi.ptr(counts)))
+        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
+    def lake_counts(self) -> list:
+        """The number of lakes of every member (``smx_ensemble_lakes`` with no records)."""
+        self._check_members()
+        counts = np.zeros(len(self.members), np.uint32)
+        self._chk(self.L.smx_ensemble_lakes(self.h, None, C.sizeof(capi.Lake), 0, capi.ptr(counts)))
+        return [int(c) for c in counts]
+
     def timing(self) -> dict:
         t = capi.Timing()
         self._chk(self.L.smx_ensemble_get_timing(self.h, C.byref(t), C.sizeof(t)))

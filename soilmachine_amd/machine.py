@@ -189,6 +189,25 @@ class Layermap:
         return {"sumh": sh.value, "nsec": int(ns.value), "typehash": f"{th.value:016x}",
                 "rand_calls": self.counters()["rand_calls"]}
 
+    def lakes(self, labels: bool = False, cap: int | None = None):
+        """The lake census (``smx_lakes``): one dict per lake in rank order -- ``first_cell`` (the lake's smallest cell index
+        x*dimy+y, its identity), ``cells``, ``volume_q40`` (the exact integer sum of floor(size * 2^40)) and ``volume`` (that as a
+        float), ``level_min`` / ``level_max`` (extremes of the water level floor + size), ``depth_max``, the inclusive box ``x0, y0,
+        x1, y1`` and ``flags`` (1: touches the map border, 2: the volume is unreliable). A lake is a maximal set of wet cells -- top
+        section Air -- connected through the eight neighbours. ``labels``: also the (dimx, dimy) uint32 plane of ranks, 0xFFFFFFFF
+        for a dry cell. ``cap`` None: two calls, a count and the fetch; else at most ``cap`` lakes. Sees every tick queued before
+        it and changes nothing."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.smx_lakes(self.h, None, C.sizeof(capi.Lake), 0, C.byref(n), None))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (capi.Lake * max(1, cap))()
+        plane = np.zeros(self.dimx * self.dimy, np.uint32) if labels else None
+        self._chk(self.L.smx_lakes(self.h, out, C.sizeof(capi.Lake), cap, C.byref(n), capi.ptr(plane)))
+        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
+        return (recs, plane.reshape(self.dimx, self.dimy)) if labels else recs
+
     def counters(self) -> dict:
         c = capi.Counters()
         self._chk(self.L.smx_get_counters_sized(self.h, C.byref(c), C.sizeof(c)))
