@@ -293,6 +293,52 @@ typedef struct smx_lake {                /* 64 bytes */
  * fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels);
 int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nlakes);
+/* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
+ *      columns under listed cells -- without exporting the map ----
+ * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,
+ * k_strata_thickness, k_core_count, k_core_scatter; bodies in soil_strata.h). Every link is validated as the fork validates it
+ * (prev < pool_capacity, no more links than pool_capacity): a bad chain returns -5, the error text names the lowest bad cell (and,
+ * in the ensemble call, the first member that has one) and nothing is written to the caller's outputs. Every call runs on the
+ * context's / the ensemble's stream (it sees every tick queued before it), changes no map, flag, counter or generator, serves a
+ * context of any engine and returns -2 for a strip context or a null argument. The totals calls synchronise once; the thickness and
+ * cores calls wait once for the verdict (and the total) and once more for the results they then copy out. The scratch is allocated
+ * at first use and kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable.
+ *
+ * SOIL TOTALS. Record t describes the sections of type t, top sections included; every field is an integer, so no result depends
+ * on the launch shape or on an order of summation. volume_q40 * 2^-40 lies below the exact sum of the sizes by less than
+ * sections * 2^-40; a section smaller than 2^-40 contributes 0. Records 0..ntypes-1 (ntypes 1..64, else -2) are always written,
+ * zeros where a type is absent; sections of a type >= ntypes are only counted, into *other_sections (NULL = skip). In the ensemble
+ * call member i's records start at record i * ntypes and other_sections holds one count per member; one table upload and the same
+ * launch whatever the member count; an empty ensemble: 0, nothing written. */
+enum { SMX_TOTALS_MAX_TYPES = 64 };
+typedef struct smx_soil_total {   /* 48 bytes; a caller passes sizeof(ITS struct) and gets that prefix of each record */
+  uint64_t sections;              /* sections of this type, top sections included */
+  uint64_t cells;                 /* columns that hold at least one section of this type */
+  uint64_t top_cells;             /* columns whose TOP section is of this type (type 0: smx_member_figures.wet_cells) */
+  uint64_t volume_q40;            /* sum over those sections of floor(size * 2^40): an exact integer */
+  uint64_t held_q40;              /* sum of floor((size * sat) * 2^40), the product rounded once in f64: pore water before porosity */
+  uint32_t flags;                 /* bit 0: volume unreliable, bit 1: held unreliable -- a term was not finite, was < 0 (-0 is 0) or
+                                     was >= 2^24 (such a term contributes 0), or the 64-bit sum wrapped */
+  uint32_t reserved;              /* written as 0 */
+} smx_soil_total;
+int smx_soil_totals(smx_ctx* ctx, smx_soil_total* out, uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections);
+int smx_ensemble_soil_totals(smx_ensemble* e, smx_soil_total* out, uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections);
+/* THICKNESS PLANES. Each output may be NULL; each holds ntypes planes in cell order x*dimy+y, type-major ([k*ncells + c]). All three
+ * come from ONE walk of the column with f64 accumulation in walk order (top -> bottom) and no contraction, so a host loop over the
+ * exported column, reversed, gives the same bits:
+ *   thickness   the sum of the sizes of the sections of type types[k], starting from +0.0
+ *   cover       the sum of the sizes of ALL sections above the highest section of types[k] (the running sum before that section is
+ *               added); -1.0 where the column has none
+ *   sections    how many sections of that type the column holds
+ * A repeated type or an ntypes outside 1..8 returns -2. */
+int smx_soil_thickness(smx_ctx* ctx, const uint32_t* types, int32_t ntypes /* 1..8 */, double* thickness, double* cover, uint32_t* sections);
+/* CORES. The columns of the n listed cells (indices x*dimy+y; repeats allowed) in the snapshot layout: columns in list order, sections
+ * bottom -> top, count[i] sections for cells[i], the bits exactly those the column export holds for those cells. *total = the number
+ * of sections the list holds; where it exceeds cap (the room of each section array), count and *total are written, the section
+ * arrays are left untouched and the call returns 1. A cell index >= dimx*dimy returns -2 and the text names it; n == 0 returns 0.
+ * Count, scan and scatter run on the device, as the fork's do; only the listed columns come back. */
+int smx_cores(smx_ctx* ctx, const uint32_t* cells, uint32_t n, uint32_t* count, uint64_t cap, uint64_t* total,
+              uint32_t* type, double* size, double* floor, double* sat);
 
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */

@@ -92,6 +92,22 @@ class Lake(C.Structure):
         return d
 
 
+class SoilTotal(C.Structure):
+    """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
+    _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
+                ("held_q40", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        d["volume"] = d["volume_q40"] * 2.0 ** -40            # below the exact sum of the sizes by less than sections * 2^-40
+        d["held"] = d["held_q40"] * 2.0 ** -40
+        return d
+
+
+TOTALS_MAX_TYPES = 64                  # SMX_TOTALS_MAX_TYPES
+TOTAL_VOLUME_UNRELIABLE, TOTAL_HELD_UNRELIABLE = 1, 2                  # smx_soil_total.flags
+THICKNESS_MAX_TYPES = 8
+
 LAKE_DRY = 0xFFFFFFFF                  # a dry cell of the label plane
 LAKE_BORDER, LAKE_VOLUME_UNRELIABLE = 1, 2                             # smx_lake.flags
 
@@ -115,6 +131,7 @@ SYMBOLS = [
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
     "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
     "smx_lakes", "smx_ensemble_lakes",
+    "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
 
@@ -237,6 +254,10 @@ def load() -> C.CDLL:
     L.smx_ensemble_fork.argtypes = [vp, vp, i32, u64, vp, C.POINTER(vp)]
     L.smx_lakes.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp]
     L.smx_ensemble_lakes.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.smx_cores.argtypes = [vp, vp, u32, vp, u64, C.POINTER(u64), vp, vp, vp, vp]
     L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)

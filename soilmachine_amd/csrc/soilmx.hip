@@ -12,6 +12,8 @@
 //                                    table, and the streaming kernels of the serial tick with the member in blockIdx.y
 //   k_ens_figures / k_ens_plane_stats   an ensemble observed in one call (soil_observe.h): one workgroup per member folds its
 //                                    digest and water figures; one thread per cell folds a plane over the selected members
+//   k_strata_totals / k_strata_thickness / k_core_count / k_core_scatter   the strata read on the device (soil_strata.h): one lane
+//                                    per column walks the chain -- per-type totals, thickness planes, the columns of listed cells
 //   k_init_terrain                   Layermap::initialize (layermap.h:163-216): FBm OpenSimplex2 per cell + column build
 //   k_heights / k_surface / k_normals / k_bilinear   whole-map read-side primitives (layermap.h:341-439)
 //   k_fill_vertices                  Layermap::update(Vertexpool&) (layermap.h:475-555): the 44-byte vertex stream
@@ -45,6 +47,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_observe.h"
 #include "soil_fork.h"
 #include "soil_lakes.h"
+#include "soil_strata.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
 
@@ -404,6 +407,39 @@ __global__ void __launch_bounds__(LAKE_LANES) k_lake_stats(const LakeMember* __r
 struct LakeMarkFn {   // the scan's input: 1 where plane word g is a root
   const uint32_t* A;
   __host__ __device__ uint32_t operator()(uint32_t g) const { return lake_mark(A, g); }
+};
+
+// ---------------- reading the strata (smx_soil_totals / smx_soil_thickness / smx_cores; bodies: soil_strata.h) ----------------
+// One lane per column, pointer chasing: a workgroup is ONE wavefront (a deep column holds up nothing else) and strides over the map.
+// k_strata_totals: member blockIdx.y of the table, workgroup blockIdx.x of gridDim.x on ITS columns (the grid is sized for the largest).
+__global__ void __launch_bounds__(STRATA_LANES) k_strata_totals(const StrataMap* __restrict__ tab, uint32_t ntypes, StrataRec* acc, uint64_t* other, uint64_t* bad) {
+  __shared__ StrataTable t;
+  const StrataMap m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * STRATA_LANES >= m.ncells) return;   // (none of its columns exists)
+  ObsGroup g;
+  strata_totals_group(m, g, blockIdx.x, gridDim.x, ntypes, t, acc, other, bad);
+}
+__global__ void __launch_bounds__(STRATA_LANES) k_strata_thickness(StrataMap m, StrataTypes ty, double* __restrict__ thickness, double* __restrict__ cover,
+                                                                   uint32_t* __restrict__ sections, uint64_t* bad) {
+  ObsGroup g;
+  strata_thickness_group(m, g, blockIdx.x, gridDim.x, ty, thickness, cover, sections, bad);
+}
+__global__ void __launch_bounds__(STRATA_LANES) k_core_count(StrataMap m, const uint32_t* __restrict__ list, uint64_t n, uint32_t* __restrict__ count, uint64_t* bad) {
+  ObsGroup g;
+  core_count_group(m, g, blockIdx.x, gridDim.x, list, n, count, bad);
+}
+// the sections the list holds, next to the error word (one lane, behind the scan)
+__global__ void k_core_total(const uint32_t* __restrict__ count, const uint64_t* __restrict__ base, uint64_t n, uint64_t* total) {
+  *total = base[n - 1] + count[n - 1];
+}
+__global__ void __launch_bounds__(STRATA_LANES) k_core_scatter(StrataMap m, const uint32_t* __restrict__ list, uint64_t n, const uint32_t* __restrict__ count,
+                                                               const uint64_t* __restrict__ base, uint64_t room, uint32_t* __restrict__ type,
+                                                               double* __restrict__ size, double* __restrict__ floor, double* __restrict__ sat) {
+  ObsGroup g;
+  core_scatter_group(m, g, blockIdx.x, gridDim.x, list, n, count, base, room, type, size, floor, sat);
+}
+struct CoreWidenFn {   // the scan's input: a count as a 64-bit word
+  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
 };
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
@@ -1483,6 +1519,15 @@ struct LakeScratch {
   char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
 };
 
+// smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
+// lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
+// pinned source of the table and landing place of the small results (h_buf). Allocated at first use, grown on demand, kept.
+struct StrataScratch {
+  char* d_buf = nullptr; size_t buf_cap = 0;
+  char* d_sec = nullptr; size_t sec_cap = 0;
+  char* h_buf = nullptr; size_t h_cap = 0;
+};
+
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
@@ -1541,6 +1586,7 @@ struct smx_ctx : EventTimer {
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
   LakeScratch lakes;                  // smx_lakes
+  StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
 // a failed HIP call: its text and the runtime's message go to the `err` of `obj` (a context, an ensemble, a lattice), the function returns -1
@@ -3002,6 +3048,7 @@ struct smx_ensemble : EventTimer {
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
   LakeScratch lakes;                      // smx_ensemble_lakes
+  StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
 static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
@@ -3573,6 +3620,198 @@ int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uin
   roctx_range rr("soilmx:ensemble_lakes");
   HIPCHK(e, hipSetDevice(e->device));
   return lakes_run("smx_ensemble_lakes", e->lakes, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nlakes, nullptr, e->err);
+}
+
+// ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------
+static_assert(sizeof(smx_soil_total) == 48 && sizeof(StrataRec) == sizeof(smx_soil_total) && offsetof(smx_soil_total, flags) == offsetof(StrataRec, flags) &&
+              (int)SMX_TOTALS_MAX_TYPES == STRATA_MAX_TYPES, "smx_soil_total layout");
+constexpr size_t STRATA_GRID = 8192;   // workgroups of one launch at most: 32 wavefronts per compute unit, the rest is strided
+static size_t strata_blocks(uint64_t items, size_t most) { return (size_t)std::max<uint64_t>(1, std::min<uint64_t>((items + STRATA_LANES - 1) / STRATA_LANES, most)); }
+static size_t strata_pad(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+static StrataMap strata_map(const smx_ctx* c) {
+  StrataMap m;
+  m.cells = c->d.cells; m.pool = c->d.pool; m.cap = c->cfg.pool_capacity; m.ncells = c->ncells; m.rec0 = 0u; m.index = 0u;
+  return m;
+}
+// room for `buf`, `sec` and `host` bytes (0: not needed by this call); a failure leaves no scratch, no sticky error and a text
+static int strata_room(const char* who, StrataScratch& k, DevMem& mem, size_t buf, size_t sec, size_t host, std::string& err) {
+  // (every call that uses the scratch has waited for its stream before it returned: nothing queued still reads what is dropped)
+  const bool ok = mem.grow(k.d_buf, k.buf_cap, buf, buf) == hipSuccess && mem.grow(k.d_sec, k.sec_cap, sec, sec) == hipSuccess &&
+                  mem.grow(k.h_buf, k.h_cap, host, host, true) == hipSuccess;
+  if (ok) return 0;
+  (void)hipGetLastError();
+  mem.drop(k.d_buf); mem.drop(k.d_sec); mem.drop(k.h_buf);
+  k = StrataScratch();
+  err = std::string(who) + ": out of memory for the scratch (" + std::to_string(buf + sec) + " bytes on the device, " + std::to_string(host) + " pinned)";
+  return -1;
+}
+static std::string strata_bad_text(const char* who, const smx_ctx* c, uint64_t word, int member) {
+  const unsigned long long cell = strata_bad_cell(word), dy = (unsigned long long)c->cfg.dimy;
+  return std::string(who) + ": corrupt section chain" + (member >= 0 ? " in member " + std::to_string(member) : std::string()) + ", cell " + std::to_string(cell) +
+         " (x " + std::to_string(cell / dy) + ", y " + std::to_string(cell % dy) + "): it leaves the pool or has more links than the pool holds (nothing was written)";
+}
+
+// One path for both totals calls: one table upload, one memset of the results, one launch, the results back, one synchronisation.
+static int totals_run(const char* who, StrataScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, bool ensemble, smx_soil_total* out,
+                      uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections, std::string& err) {
+  const size_t tab_bytes = strata_pad((size_t)nm * sizeof(StrataMap)), nrec = (size_t)nm * ntypes;
+  const size_t res_bytes = (size_t)nm * 16 + nrec * sizeof(StrataRec);   // error words, counts of other sections, records
+  if (int rc = strata_room(who, k, mem, tab_bytes + res_bytes, 0, tab_bytes + res_bytes, err)) return rc;
+  StrataMap* tab = reinterpret_cast<StrataMap*>(k.h_buf);
+  uint64_t most = 0;
+  for (uint32_t i = 0; i < nm; i++) {
+    tab[i] = strata_map(ms[i]);
+    tab[i].rec0 = i * ntypes; tab[i].index = i;
+    most = std::max<uint64_t>(most, ms[i]->ncells);
+  }
+  uint64_t* d_bad = reinterpret_cast<uint64_t*>(k.d_buf + tab_bytes);
+  uint64_t* d_other = d_bad + nm;
+  StrataRec* d_acc = reinterpret_cast<StrataRec*>(d_other + nm);
+  bool ok = hipMemcpyAsync(k.d_buf, k.h_buf, (size_t)nm * sizeof(StrataMap), hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemsetAsync(d_bad, 0, res_bytes, st) == hipSuccess;
+  if (ok) {
+    const size_t bx = strata_blocks(most, std::max<size_t>(1, STRATA_GRID / nm));
+    hipLaunchKernelGGL(k_strata_totals, dim3((unsigned)bx, nm), dim3(STRATA_LANES), 0, st, reinterpret_cast<const StrataMap*>(k.d_buf), ntypes, d_acc, d_other, d_bad);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(k.h_buf + tab_bytes, d_bad, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+  }
+  const hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the totals failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const uint64_t* bad = reinterpret_cast<const uint64_t*>(k.h_buf + tab_bytes);
+  const uint64_t* oth = bad + nm;
+  const StrataRec* acc = reinterpret_cast<const StrataRec*>(oth + nm);
+  for (uint32_t i = 0; i < nm; i++)
+    if (bad[i]) { err = strata_bad_text(who, ms[i], bad[i], ensemble ? (int)i : -1); return -5; }
+  const size_t take = struct_size < sizeof(smx_soil_total) ? (size_t)struct_size : sizeof(smx_soil_total);
+  for (size_t r = 0; r < nrec; r++) memcpy(reinterpret_cast<char*>(out) + r * (size_t)struct_size, acc + r, take);
+  if (other_sections) memcpy(other_sections, oth, (size_t)nm * 8);
+  return 0;
+}
+int smx_soil_totals(smx_ctx* ctx, smx_soil_total* out, uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections) {
+  if (!ctx) return -2;
+  FULLMAP("smx_soil_totals")
+  if (!out) { ctx->err = "smx_soil_totals: out is null"; return -2; }
+  if (struct_size == 0) { ctx->err = "smx_soil_totals: struct_size is 0 (pass sizeof(smx_soil_total) of the header you compiled against)"; return -2; }
+  if (ntypes < 1u || ntypes > (uint32_t)SMX_TOTALS_MAX_TYPES) { ctx->err = "smx_soil_totals: ntypes is " + std::to_string(ntypes) + ", outside 1..64"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_soil_totals: a context without a device"; return -3; }
+  roctx_range rr("soilmx:soil_totals");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return totals_run("smx_soil_totals", ctx->strata, ctx->mem, ctx->stream, &ctx, 1u, false, out, struct_size, ntypes, other_sections, ctx->err);
+}
+int smx_ensemble_soil_totals(smx_ensemble* e, smx_soil_total* out, uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_soil_totals: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_soil_totals: struct_size is 0 (pass sizeof(smx_soil_total) of the header you compiled against)"; return -2; }
+  if (ntypes < 1u || ntypes > (uint32_t)SMX_TOTALS_MAX_TYPES) { e->err = "smx_ensemble_soil_totals: ntypes is " + std::to_string(ntypes) + ", outside 1..64"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!out) { e->err = "smx_ensemble_soil_totals: out is null (ntypes records per member)"; return -2; }
+  roctx_range rr("soilmx:ensemble_soil_totals");
+  HIPCHK(e, hipSetDevice(e->device));
+  return totals_run("smx_ensemble_soil_totals", e->strata, e->mem, e->stream, e->members.data(), nm, true, out, struct_size, ntypes, other_sections, e->err);
+}
+
+int smx_soil_thickness(smx_ctx* ctx, const uint32_t* types, int32_t ntypes, double* thickness, double* cover, uint32_t* sections) {
+  if (!ctx) return -2;
+  FULLMAP("smx_soil_thickness")
+  if (!types) { ctx->err = "smx_soil_thickness: types is null"; return -2; }
+  if (ntypes < 1 || ntypes > STRATA_MAX_LIST) { ctx->err = "smx_soil_thickness: ntypes is " + std::to_string(ntypes) + ", outside 1..8"; return -2; }
+  StrataTypes ty{};
+  ty.n = (uint32_t)ntypes;
+  for (int32_t a = 0; a < ntypes; a++) {
+    ty.t[a] = types[a];
+    for (int32_t b = 0; b < a; b++)
+      if (types[a] == types[b]) { ctx->err = "smx_soil_thickness: type " + std::to_string(types[a]) + " is listed twice (entries " + std::to_string(b) + " and " + std::to_string(a) + ")"; return -2; }
+  }
+  if (!ctx->stream) { ctx->err = "smx_soil_thickness: a context without a device"; return -3; }
+  roctx_range rr("soilmx:soil_thickness");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  StrataScratch& k = ctx->strata;
+  const size_t vals = (size_t)ntypes * ctx->ncells;
+  const size_t at_cover = thickness ? vals * 8 : 0, at_sec = at_cover + (cover ? vals * 8 : 0), sec_bytes = at_sec + (sections ? vals * 4 : 0);
+  if (int rc = strata_room("smx_soil_thickness", k, ctx->mem, 64, sec_bytes, 64, ctx->err)) return rc;
+  uint64_t* d_bad = reinterpret_cast<uint64_t*>(k.d_buf);
+  double* d_th = thickness ? reinterpret_cast<double*>(k.d_sec) : nullptr;
+  double* d_cv = cover ? reinterpret_cast<double*>(k.d_sec + at_cover) : nullptr;
+  uint32_t* d_n = sections ? reinterpret_cast<uint32_t*>(k.d_sec + at_sec) : nullptr;
+  HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+  hipLaunchKernelGGL(k_strata_thickness, dim3((unsigned)strata_blocks(ctx->ncells, STRATA_GRID)), dim3(STRATA_LANES), 0, ctx->stream, strata_map(ctx), ty, d_th, d_cv, d_n, d_bad);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(k.h_buf, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the verdict first: a bad chain writes nothing to the caller
+  const uint64_t bad = *reinterpret_cast<const uint64_t*>(k.h_buf);
+  if (bad) { ctx->err = strata_bad_text("smx_soil_thickness", ctx, bad, -1); return -5; }
+  if (thickness) HIPCHK(ctx, hipMemcpyAsync(thickness, d_th, vals * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (cover) HIPCHK(ctx, hipMemcpyAsync(cover, d_cv, vals * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (sections) HIPCHK(ctx, hipMemcpyAsync(sections, d_n, vals * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int smx_cores(smx_ctx* ctx, const uint32_t* cells, uint32_t n, uint32_t* count, uint64_t cap, uint64_t* total, uint32_t* type, double* size, double* floor,
+              double* sat) {
+  if (!ctx) return -2;
+  FULLMAP("smx_cores")
+  if (!total) { ctx->err = "smx_cores: total is null"; return -2; }
+  if (n == 0) { *total = 0; return 0; }
+  if (!cells || !count) { ctx->err = std::string("smx_cores: ") + (cells ? "count" : "cells") + " is null"; return -2; }
+  if (cap && (!type || !size || !floor || !sat)) { ctx->err = "smx_cores: a section array is null while cap is " + std::to_string(cap); return -2; }
+  for (uint32_t i = 0; i < n; i++)
+    if (cells[i] >= ctx->ncells) {
+      ctx->err = "smx_cores: cells[" + std::to_string(i) + "] is " + std::to_string(cells[i]) + ", outside the map of " + std::to_string(ctx->ncells) + " cells";
+      return -2;
+    }
+  if (!ctx->stream) { ctx->err = "smx_cores: a context without a device"; return -3; }
+  roctx_range rr("soilmx:cores");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  StrataScratch& k = ctx->strata;
+  hipStream_t st = ctx->stream;
+  const size_t at_list = 64, at_count = at_list + strata_pad((size_t)n * 4), at_base = at_count + strata_pad((size_t)n * 4), at_temp = at_base + strata_pad((size_t)n * 8);
+  size_t tb = 0;
+  {
+    const auto in = rocprim::make_transform_iterator(static_cast<const uint32_t*>(nullptr), CoreWidenFn{});
+    HIPCHK(ctx, rocprim::exclusive_scan(nullptr, tb, in, static_cast<uint64_t*>(nullptr), 0ull, (size_t)n, rocprim::plus<uint64_t>(), st));
+  }
+  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
+  if (int rc = strata_room("smx_cores", k, ctx->mem, at_temp + tb, 0, 64, ctx->err)) return rc;
+  uint64_t* d_word = reinterpret_cast<uint64_t*>(k.d_buf);   // [0] the error word, [1] the total
+  uint32_t* d_list = reinterpret_cast<uint32_t*>(k.d_buf + at_list);
+  uint32_t* d_count = reinterpret_cast<uint32_t*>(k.d_buf + at_count);
+  uint64_t* d_base = reinterpret_cast<uint64_t*>(k.d_buf + at_base);
+  const StrataMap m = strata_map(ctx);
+  const unsigned nb = (unsigned)strata_blocks(n, STRATA_GRID);
+  HIPCHK(ctx, hipMemsetAsync(d_word, 0, 16, st));
+  HIPCHK(ctx, hipMemcpyAsync(d_list, cells, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_core_count, dim3(nb), dim3(STRATA_LANES), 0, st, m, d_list, (uint64_t)n, d_count, d_word);
+  {
+    const auto in = rocprim::make_transform_iterator(static_cast<const uint32_t*>(d_count), CoreWidenFn{});
+    HIPCHK(ctx, rocprim::exclusive_scan(k.d_buf + at_temp, tb, in, d_base, 0ull, (size_t)n, rocprim::plus<uint64_t>(), st));
+  }
+  hipLaunchKernelGGL(k_core_total, dim3(1), dim3(1), 0, st, d_count, d_base, (uint64_t)n, d_word + 1);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(k.h_buf, d_word, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));   // the verdict and the total first: they size what follows
+  const uint64_t bad = reinterpret_cast<const uint64_t*>(k.h_buf)[0], tot = reinterpret_cast<const uint64_t*>(k.h_buf)[1];
+  if (bad) { ctx->err = strata_bad_text("smx_cores", ctx, bad, -1); return -5; }
+  *total = tot;
+  HIPCHK(ctx, hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  if (tot > cap || tot == 0) {
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return tot > cap ? 1 : 0;
+  }
+  const size_t t8 = strata_pad((size_t)tot * 8);
+  if (int rc = strata_room("smx_cores", k, ctx->mem, 0, 3 * t8 + (size_t)tot * 4, 0, ctx->err)) { hipStreamSynchronize(st); return rc; }
+  double* d_size = reinterpret_cast<double*>(k.d_sec);
+  double* d_floor = reinterpret_cast<double*>(k.d_sec + t8);
+  double* d_sat = reinterpret_cast<double*>(k.d_sec + 2 * t8);
+  uint32_t* d_type = reinterpret_cast<uint32_t*>(k.d_sec + 3 * t8);
+  hipLaunchKernelGGL(k_core_scatter, dim3(nb), dim3(STRATA_LANES), 0, st, m, d_list, (uint64_t)n, d_count, d_base, tot, d_type, d_size, d_floor, d_sat);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(type, d_type, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(size, d_size, (size_t)tot * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(floor, d_floor, (size_t)tot * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(sat, d_sat, (size_t)tot * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  return 0;
 }
 
 // ---------------- point operations ----------------

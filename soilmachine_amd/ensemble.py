@@ -254,6 +254,18 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_lakes(self.h, None, C.sizeof(capi.Lake), 0, capi.ptr(counts)))
         return [int(c) for c in counts]
 
+    def soil_totals(self, ntypes: int, other: bool = False) -> list:
+        """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
+        one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,
+        the lists and each member's number of sections of a type >= ntypes. Members may differ in size and soil table."""
+        self._check_members()
+        n, nt = len(self.members), int(ntypes)
+        out = (capi.SoilTotal * max(1, n * max(nt, 0)))()
+        rest = np.zeros(max(1, n), np.uint64)
+        self._chk(self.L.smx_ensemble_soil_totals(self.h, out, C.sizeof(capi.SoilTotal), nt, capi.ptr(rest)))
+        recs = [[out[i * nt + t].as_dict() for t in range(nt)] for i in range(n)]
+        return (recs, [int(v) for v in rest[:n]]) if other else recs
+
     def timing(self) -> dict:
         t = capi.Timing()
         self._chk(self.L.smx_ensemble_get_timing(self.h, C.byref(t), C.sizeof(t)))

@@ -208,6 +208,74 @@ class Layermap:
         recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
         return (recs, plane.reshape(self.dimx, self.dimy)) if labels else recs
 
+    # -- the strata read on the device --
+    def soil_totals(self, ntypes: int | None = None, other: bool = False):
+        """How much of each soil the map holds (``smx_soil_totals``): one dict per type 0..ntypes-1 -- ``sections`` (top sections
+        included), ``cells`` (columns holding the type), ``top_cells`` (columns whose top section it is), ``volume_q40`` / ``held_q40``
+        (the exact integer sums of floor(size * 2^40) and floor(size * sat * 2^40)), ``volume`` / ``held`` (those times 2^-40) and
+        ``flags`` (1: volume unreliable, 2: held unreliable). ``ntypes`` None: the context's soil count, capped at 64. ``other``:
+        also the number of sections of a type >= ntypes. Sees every tick queued before it and changes nothing."""
+        nt = min(len(self._soils), capi.TOTALS_MAX_TYPES) if ntypes is None else int(ntypes)
+        out = (capi.SoilTotal * max(1, nt))()
+        rest = C.c_uint64()
+        self._chk(self.L.smx_soil_totals(self.h, out, C.sizeof(capi.SoilTotal), nt, C.byref(rest)))
+        recs = [out[t].as_dict() for t in range(nt)]
+        return (recs, int(rest.value)) if other else recs
+
+    def soil_thickness(self, types, cover: bool = False, sections: bool = False):
+        """Per-cell planes for up to eight soil types from one walk of every column (``smx_soil_thickness``): ``thickness`` of shape
+        (len(types), dimx, dimy), the summed sizes of the type's sections; with ``cover`` also the summed sizes of everything above the
+        type's highest section (-1.0 where the column has none); with ``sections`` also the section counts (uint32). f64 sums in walk
+        order, top to bottom. Returns the plane, or a tuple in the order thickness, cover, sections."""
+        ty = np.ascontiguousarray(list(types), np.uint32)
+        shape = (max(1, len(ty)), self.dimx * self.dimy)
+        th = np.zeros(shape)
+        cv = np.zeros(shape) if cover else None
+        ns = np.zeros(shape, np.uint32) if sections else None
+        self._chk(self.L.smx_soil_thickness(self.h, capi.ptr(ty), len(ty), capi.ptr(th), capi.ptr(cv), capi.ptr(ns)))
+        out = [a.reshape(len(ty), self.dimx, self.dimy) for a in (th, cv, ns) if a is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def cores(self, cells):
+        """The columns under the listed cells (``smx_cores``; indices x*dimy + y, repeats allowed): ``count, type, size, floor, sat``
+        in the snapshot layout -- columns in list order, sections bottom to top, ``count[i]`` of them for ``cells[i]``. Two calls, a
+        count and the fetch; only the listed columns cross the host."""
+        cl = np.ascontiguousarray(list(cells) if not isinstance(cells, np.ndarray) else cells, np.uint32)
+        n = len(cl)
+        count = np.zeros(n, np.uint32)
+        total = C.c_uint64()
+        rc = self.L.smx_cores(self.h, capi.ptr(cl), n, capi.ptr(count), 0, C.byref(total), None, None, None, None)
+        if rc not in (0, 1):
+            self._chk(rc)
+        cap = int(total.value)
+        ty, size, floor, sat = np.zeros(cap, np.uint32), np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        if rc == 1:
+            self._chk(self.L.smx_cores(self.h, capi.ptr(cl), n, capi.ptr(count), cap, C.byref(total), capi.ptr(ty), capi.ptr(size), capi.ptr(floor), capi.ptr(sat)))
+        return count, ty, size, floor, sat
+
+    @staticmethod
+    def transect_cells(p0, p1) -> list:
+        """The cells (x, y) on the line from p0 to p1, both included. With dx = x1 - x0, dy = y1 - y0 and N = max(|dx|, |dy|), point i
+        of 0..N is x0 + sgn(dx) * ((2*i*|dx| + N) // (2*N)) and likewise for y: the longer axis advances one cell per point, the
+        shorter one rounds half away from p0. N = 0 is the single cell."""
+        (x0, y0), (x1, y1) = (int(p0[0]), int(p0[1])), (int(p1[0]), int(p1[1]))
+        dx, dy = x1 - x0, y1 - y0
+        n = max(abs(dx), abs(dy))
+        if n == 0:
+            return [(x0, y0)]
+        sx, sy = (dx > 0) - (dx < 0), (dy > 0) - (dy < 0)
+        return [(x0 + sx * ((2 * i * abs(dx) + n) // (2 * n)), y0 + sy * ((2 * i * abs(dy) + n) // (2 * n))) for i in range(n + 1)]
+
+    def transect(self, p0, p1):
+        """The cores of the cells on the line from (x0, y0) to (x1, y1), in order (the rule: ``transect_cells``): ``cells`` (the
+        indices x*dimy + y) and ``count, type, size, floor, sat`` as ``cores`` gives them. Both ends must lie on the map."""
+        pts = self.transect_cells(p0, p1)
+        for x, y in (pts[0], pts[-1]):
+            if not (0 <= x < self.dimx and 0 <= y < self.dimy):
+                raise ValueError(f"transect: ({x}, {y}) is outside the {self.dimx} x {self.dimy} map")
+        cells = np.array([x * self.dimy + y for x, y in pts], np.uint32)
+        return (cells,) + self.cores(cells)
+
     def counters(self) -> dict:
         c = capi.Counters()
         self._chk(self.L.smx_get_counters_sized(self.h, C.byref(c), C.sizeof(c)))
