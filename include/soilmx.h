@@ -293,6 +293,42 @@ typedef struct smx_lake {                /* 64 bytes */
  * fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels);
 int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nlakes);
+/* ---- drainage: where the water goes -- every dry cell's receiver, the basin every cell drains into, the contributing area ----
+ * Cells are indexed c = x*dimy+y; h(c) is Layermap::height (floor + size of the top record in one f64 addition, 0.0 for an empty
+ * column); a WET cell and a LAKE are those of smx_lakes. A wet cell has no RECEIVER. A dry cell's receiver is the in-map cell n among
+ * its eight neighbours (cells do not connect across the map border) with h(n) < h(c) and the smallest (h(n), n): plain f64 `<` on h,
+ * then the smaller cell index -- so -0.0 and +0.0 tie, and a NaN height is never lower and never has a lower neighbour. A dry cell
+ * without one is a SINK. Every path strictly descends in h, so it ends at a sink or at the first wet cell it meets. A BASIN is the set
+ * of cells whose path ends at one sink or in one lake (a wet cell belongs to its own lake's basin); its IDENTITY first_cell is the
+ * sink's index or the lake's first_cell -- join on it with the records of smx_lakes --, basins are listed in ascending first_cell,
+ * and basin k of that order has RANK k. area(c) = 1 + the sum of area(d) over the cells d whose receiver is c, as u32: the basin's
+ * size at a sink, one plus the dry land that enters the lake there at a wet cell; over all sinks and wet cells it sums to dimx*dimy.
+ * Every figure is a comparison, an integer or an order-free extreme: a host restatement reproduces each bit. */
+typedef struct smx_basin {               /* 48 bytes; a caller passes sizeof(ITS struct) and gets that prefix of each record */
+  uint32_t first_cell;                   /* the sink's cell, or the lake's first_cell */
+  uint32_t cells;                        /* cells of the basin, wet ones included */
+  uint32_t wet_cells;                    /* 0 for a sink's basin, the lake's cells otherwise */
+  uint32_t flags;                        /* bit 0: the terminal is a lake; bit 1: the sink lies on, or the lake touches, the map border */
+  double   height_min, height_max;       /* extremes of h over the basin, -0 < +0 as in smx_lake */
+  uint16_t x0, y0, x1, y1;               /* the inclusive bounding box of the basin */
+  uint32_t reserved[2];                  /* written as 0 */
+} smx_basin;
+/* *nbasins = the number of basins, whatever cap is; the first min(cap, *nbasins) records are written in rank order, record k at byte
+ * k * struct_size; out may be NULL when cap is 0 (counting only). The planes (NULL = skip) hold dimx*dimy words in cell order:
+ * receivers -- the receiver's cell index, 0xFFFFFFFF for a sink and for a wet cell; labels -- the rank of the cell's basin (no cell is
+ * without one); area -- as defined above (with area == NULL the two accumulation launches are skipped). In the ensemble call member
+ * i's records start at out + i * cap_per_member records and nbasins holds one count per member; an empty ensemble: 0, nothing written.
+ * Both calls run on the context's / the ensemble's stream (they see every tick queued before them), launch the same kernels whatever
+ * the map holds and however many members there are (one table upload; k_lake_tiles, k_lake_merge, k_lake_flatten on the call's own
+ * scratch, k_drain_recv, k_drain_resolve, a prefix sum, k_drain_stats, and for the area k_drain_pending, k_drain_area; the RESULTS
+ * copied back), synchronise once and change no map, flag, counter or generator. Only the 32-byte top records are read, so a context
+ * of any engine serves; a strip context, a null argument, struct_size == 0 and records asked for with out == NULL return -2. The
+ * scratch -- three u32 planes per cell, five once an area was asked for, and the records asked for -- is the call's own (smx_lakes
+ * keeps its own), allocated at first use and kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable.
+ * Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_drainage(smx_ctx* ctx, smx_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
+                 uint32_t* receivers, uint32_t* labels, uint32_t* area);
+int smx_ensemble_drainage(smx_ensemble* e, smx_basin* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

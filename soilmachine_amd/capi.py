@@ -92,6 +92,16 @@ class Lake(C.Structure):
         return d
 
 
+class Basin(C.Structure):
+    """smx_basin: one basin of smx_drainage / smx_ensemble_drainage (48 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("wet_cells", C.c_uint32), ("flags", C.c_uint32),
+                ("height_min", C.c_double), ("height_max", C.c_double), ("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16),
+                ("y1", C.c_uint16), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -110,6 +120,8 @@ THICKNESS_MAX_TYPES = 8
 
 LAKE_DRY = 0xFFFFFFFF                  # a dry cell of the label plane
 LAKE_BORDER, LAKE_VOLUME_UNRELIABLE = 1, 2                             # smx_lake.flags
+DRAIN_NONE = 0xFFFFFFFF                # the receiver plane: a sink or a wet cell
+BASIN_LAKE, BASIN_BORDER = 1, 2                                        # smx_basin.flags
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
@@ -130,7 +142,7 @@ SYMBOLS = [
     "smx_ensemble_create", "smx_ensemble_destroy", "smx_ensemble_last_error", "smx_ensemble_add", "smx_ensemble_remove", "smx_ensemble_size",
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
     "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
-    "smx_lakes", "smx_ensemble_lakes",
+    "smx_lakes", "smx_ensemble_lakes", "smx_drainage", "smx_ensemble_drainage",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -254,6 +266,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_fork.argtypes = [vp, vp, i32, u64, vp, C.POINTER(vp)]
     L.smx_lakes.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp]
     L.smx_ensemble_lakes.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_drainage.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
+    L.smx_ensemble_drainage.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -47,6 +47,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_observe.h"
 #include "soil_fork.h"
 #include "soil_lakes.h"
+#include "soil_drain.h"
 #include "soil_strata.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
@@ -408,6 +409,44 @@ struct LakeMarkFn {   // the scan's input: 1 where plane word g is a root
   const uint32_t* A;
   __host__ __device__ uint32_t operator()(uint32_t g) const { return lake_mark(A, g); }
 };
+
+// ---------------- drainage (smx_drainage / smx_ensemble_drainage; bodies: soil_drain.h) ----------------
+// The census's tiles, lanes and table size: the height tile with its halo of one is 18 x 66 doubles (9.3 KB of LDS), the statistics
+// table holds 512 cells' worth of basins (24 KB).
+__global__ void __launch_bounds__(LAKE_LANES) k_drain_recv(const LakeMember* __restrict__ tab, uint32_t* T, uint32_t* R, BasinAcc* acc) {
+  __shared__ double hs[(LAKE_TX + 2) * (LAKE_TY + 2)];
+  const LakeMember m = tab[blockIdx.y];
+  const uint32_t nt = lake_tiles(m, LAKE_TX, LAKE_TY);
+  if (blockIdx.x >= nt) return;
+  ObsGroup g;
+  drain_recv_group<LAKE_TX, LAKE_TY>(m, g, blockIdx.x, nt, hs, T, R, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_drain_resolve(const LakeMember* __restrict__ tab, uint32_t* T) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  drain_resolve_group(m, g, blockIdx.x, T);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_drain_stats(const LakeMember* __restrict__ tab, uint32_t* T, const uint32_t* __restrict__ B, BasinAcc* acc,
+                                                            uint32_t* nbasins) {
+  __shared__ BasinTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  drain_stats_group<LAKE_SLOTS>(m, g, blockIdx.x, t, T, B, acc, nbasins + blockIdx.y);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_drain_pending(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ R, uint32_t* P, uint32_t* AR) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  drain_pending_group(m, g, blockIdx.x, R, P, AR);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_drain_area(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ R, uint32_t* P, uint32_t* AR) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  drain_area_group(m, g, blockIdx.x, R, P, AR);
+}
 
 // ---------------- reading the strata (smx_soil_totals / smx_soil_thickness / smx_cores; bodies: soil_strata.h) ----------------
 // One lane per column, pointer chasing: a workgroup is ONE wavefront (a deep column holds up nothing else) and strides over the map.
@@ -1519,6 +1558,17 @@ struct LakeScratch {
   char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
 };
 
+// smx_drainage / smx_ensemble_drainage: the u32 planes (T, B, R; P and AR once an area was asked for), rocPRIM's temporary storage, the
+// member table with its pinned source and the results with their pinned landing place. Its own, apart from the census's: allocated
+// by the first call, grown on demand, kept with the context or the ensemble.
+struct DrainScratch {
+  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; size_t words = 0;
+  uint32_t* P = nullptr; uint32_t* AR = nullptr; size_t area_words = 0;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
+  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
+};
+
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
 // lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
 // pinned source of the table and landing place of the small results (h_buf). Allocated at first use, grown on demand, kept.
@@ -1586,6 +1636,7 @@ struct smx_ctx : EventTimer {
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
   LakeScratch lakes;                  // smx_lakes
+  DrainScratch drain;                 // smx_drainage
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3048,6 +3099,7 @@ struct smx_ensemble : EventTimer {
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
   LakeScratch lakes;                      // smx_ensemble_lakes
+  DrainScratch drain;                     // smx_ensemble_drainage
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -3620,6 +3672,142 @@ int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uin
   roctx_range rr("soilmx:ensemble_lakes");
   HIPCHK(e, hipSetDevice(e->device));
   return lakes_run("smx_ensemble_lakes", e->lakes, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nlakes, nullptr, e->err);
+}
+
+// ---------------- drainage (smx_drainage / smx_ensemble_drainage; kernels: soil_drain.h and the census's) ----------------
+// One path for both calls, shaped as lakes_run: one table upload; k_lake_tiles, k_lake_merge and k_lake_flatten label the wet cells on
+// the drainage scratch (the table's cap is 0 for them: they touch no record); k_drain_recv, k_drain_resolve, rocPRIM's exclusive scan
+// of the terminal marks, k_drain_stats; k_drain_pending and k_drain_area where the area plane is asked for; the counts, the records and
+// the planes asked for copied back, one synchronisation -- whatever the maps hold and however many there are.
+static_assert(sizeof(smx_basin) == 48 && sizeof(BasinRec) == sizeof(smx_basin) && offsetof(smx_basin, height_min) == offsetof(BasinRec, height_min) &&
+              offsetof(smx_basin, x0) == offsetof(BasinRec, x0), "smx_basin layout");
+static void drain_drop(DrainScratch& k, DevMem& mem) {
+  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.P); mem.drop(k.AR); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
+  k = DrainScratch();
+}
+static int drain_run(const char* who, DrainScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_basin* out, uint64_t struct_size,
+                     uint32_t cap, uint32_t* nbasins, uint32_t* receivers, uint32_t* labels, uint32_t* area, std::string& err) {
+  std::vector<LakeMember> tab(nm);
+  uint64_t words = 0, nrec = 0;
+  size_t tiles = 1, flat = 1, stat = 1;
+  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = ms[i];
+    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side (the bounding boxes are 16-bit)"; return -2; }
+    LakeMember& m = tab[i];
+    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
+    m.cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)c->ncells);   // (every cell of a plateau is a basin)
+    words += (uint64_t)c->ncells; nrec += m.cap;
+    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one call"; return -2; }
+    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
+    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
+    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
+  }
+  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(BasinAcc);
+  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
+  size_t tb = 0;
+  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
+  if (ok && (words > k.words || (area && words > k.area_words) || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
+    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
+    if (ok && words > k.words) {
+      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); k.words = 0;
+      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess;
+      if (ok) k.words = (size_t)words;
+    }
+    if (ok && area && words > k.area_words) {
+      mem.drop(k.P); mem.drop(k.AR); k.area_words = 0;
+      ok = mem.dev(k.P, (size_t)words) == hipSuccess && mem.dev(k.AR, (size_t)words) == hipSuccess;
+      if (ok) k.area_words = (size_t)words;
+    }
+    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
+    if (ok && nm > k.tab_cap) {
+      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
+      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess;
+      if (ok) k.tab_cap = nm;
+    }
+    if (ok && res_bytes > k.res_cap) {
+      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
+      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
+      if (ok) k.res_cap = res_bytes;
+    }
+    if (!ok) {
+      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
+      drain_drop(k, mem);
+      err = std::string(who) + ": out of memory for the drainage scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
+      return -1;
+    }
+  }
+  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
+  // two tables: the members as the drainage kernels see them, and, behind them, the same members with cap 0 for the census's kernels
+  // (k_lake_tiles writes the identities of ITS records for ranks below cap: none here)
+  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
+  for (uint32_t i = 0; i < nm; i++) { k.h_tab[nm + i] = tab[i]; k.h_tab[nm + i].cap = 0u; }
+  const LakeMember* wet_tab = k.d_tab + nm;
+  BasinAcc* acc = reinterpret_cast<BasinAcc*>(k.d_res + rec_at);
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  ok = hipMemcpyAsync(k.d_tab, k.h_tab, 2 * (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_lake_tiles, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T, (LakeAcc*)nullptr);
+    hipLaunchKernelGGL(k_lake_merge, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T);
+    hipLaunchKernelGGL(k_lake_flatten, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T);
+    hipLaunchKernelGGL(k_drain_recv, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T, k.R, acc);
+    hipLaunchKernelGGL(k_drain_resolve, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T);
+    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_drain_stats, dim3((unsigned)stat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T, k.B, acc, d_n);
+    if (area) {
+      hipLaunchKernelGGL(k_drain_pending, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.R, k.P, k.AR);
+      hipLaunchKernelGGL(k_drain_area, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.R, k.P, k.AR);
+    }
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+  // (smx_drainage only: one map, off = 0, so a plane index is a cell index)
+  if (ok && receivers) ok = hipMemcpyAsync(receivers, k.R, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && labels) ok = hipMemcpyAsync(labels, k.T, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && area) ok = hipMemcpyAsync(area, k.AR, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  const hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": drainage failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
+  const BasinAcc* a = reinterpret_cast<const BasinAcc*>(k.h_res + rec_at);
+  const size_t take = struct_size < sizeof(smx_basin) ? (size_t)struct_size : sizeof(smx_basin);
+  for (uint32_t i = 0; i < nm; i++) {
+    nbasins[i] = n[i];
+    const uint32_t w = std::min(n[i], tab[i].cap);
+    for (uint32_t r = 0; r < w; r++) {
+      BasinRec rec;
+      drain_finish(a[tab[i].rec0 + r], rec);
+      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
+    }
+  }
+  return 0;
+}
+
+int smx_drainage(smx_ctx* ctx, smx_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* receivers, uint32_t* labels, uint32_t* area) {
+  if (!ctx) return -2;
+  FULLMAP("smx_drainage")
+  if (struct_size == 0) { ctx->err = "smx_drainage: struct_size is 0 (pass sizeof(smx_basin) of the header you compiled against)"; return -2; }
+  if (!nbasins) { ctx->err = "smx_drainage: nbasins is null"; return -2; }
+  if (!out && cap) { ctx->err = "smx_drainage: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_drainage: a context without a device"; return -3; }
+  roctx_range rr("soilmx:drainage");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return drain_run("smx_drainage", ctx->drain, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, receivers, labels, area, ctx->err);
+}
+int smx_ensemble_drainage(smx_ensemble* e, smx_basin* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_drainage: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_drainage: struct_size is 0 (pass sizeof(smx_basin) of the header you compiled against)"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!nbasins) { e->err = "smx_ensemble_drainage: nbasins is null (one count per member)"; return -2; }
+  if (!out && cap_per_member) { e->err = "smx_ensemble_drainage: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  roctx_range rr("soilmx:ensemble_drainage");
+  HIPCHK(e, hipSetDevice(e->device));
+  return drain_run("smx_ensemble_drainage", e->drain, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, e->err);
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------

@@ -254,6 +254,30 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_lakes(self.h, None, C.sizeof(capi.Lake), 0, capi.ptr(counts)))
         return [int(c) for c in counts]
 
+    def drainage(self, cap: int | None = None) -> list:
+        """The basins of every member (``smx_ensemble_drainage``: the same launches whatever the member count): one list of basin
+        dicts per member, in member order, each as ``Layermap.drainage()`` gives it. ``cap`` None: two calls, a count with no records
+        and the fetch sized by the largest count; else at most ``cap`` basins per member. Members may differ in size."""
+        self._check_members()
+        n = len(self.members)
+        if n == 0:
+            return []
+        counts = np.zeros(n, np.uint32)
+        if cap is None:
+            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
+            cap = int(counts.max())
+        cap = int(cap)
+        out = (capi.Basin * max(1, n * cap))()
+        self._chk(self.L.smx_ensemble_drainage(self.h, out, C.sizeof(capi.Basin), cap, capi.ptr(counts)))
+        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
+    def basin_counts(self) -> list:
+        """The number of basins of every member (``smx_ensemble_drainage`` with no records)."""
+        self._check_members()
+        counts = np.zeros(len(self.members), np.uint32)
+        self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
+        return [int(c) for c in counts]
+
     def soil_totals(self, ntypes: int, other: bool = False) -> list:
         """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
         one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,

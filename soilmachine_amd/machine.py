@@ -208,6 +208,28 @@ class Layermap:
         recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
         return (recs, plane.reshape(self.dimx, self.dimy)) if labels else recs
 
+    def drainage(self, receivers: bool = False, labels: bool = False, area: bool = False, cap: int | None = None):
+        """Where the water goes (``smx_drainage``): one dict per basin in rank order -- ``first_cell`` (the sink's cell index
+        x*dimy+y or the lake's ``first_cell``: join on it with ``lakes()``), ``cells``, ``wet_cells`` (0 for a sink's basin),
+        ``flags`` (1: the terminal is a lake, 2: the sink lies on, or the lake touches, the map border), ``height_min`` /
+        ``height_max`` and the inclusive box ``x0, y0, x1, y1``. A dry cell drains to the lowest of its eight neighbours that is lower
+        than itself (ties: the smaller cell index); a path ends at a sink or at the first wet cell. With a plane asked for the result
+        is ``(records, planes)``, ``planes`` a dict of (dimx, dimy) uint32 arrays: ``receivers`` (the receiver's cell index,
+        0xFFFFFFFF for a sink and a wet cell), ``labels`` (the basin's rank) and ``area`` (1 + the areas of the cells draining into
+        the cell). ``cap`` None: two calls, a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it and
+        changes nothing."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (capi.Basin * max(1, cap))()
+        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, want in (("receivers", receivers), ("labels", labels), ("area", area)) if want}
+        self._chk(self.L.smx_drainage(self.h, out, C.sizeof(capi.Basin), cap, C.byref(n), capi.ptr(planes.get("receivers")), capi.ptr(planes.get("labels")),
+                                      capi.ptr(planes.get("area"))))
+        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
+        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+
     # -- the strata read on the device --
     def soil_totals(self, ntypes: int | None = None, other: bool = False):
         """How much of each soil the map holds (``smx_soil_totals``): one dict per type 0..ntypes-1 -- ``sections`` (top sections
