@@ -440,6 +440,16 @@ int smx_set_relax_wind(smx_ctx* ctx, uint32_t min_running, int32_t steps_per_epo
  * profiles/r06_persistent_epochs.md); tail_at: from this many running particles down one workgroup runs whole epochs back to back
  * (k_relax_tail; 0..256, default 256). -1 = leave as is / back to the default. */
 int smx_set_relax_launch(smx_ctx* ctx, int32_t persistent, int32_t tail_at);
+/* relaxed schedule, dense epochs (water, and relaxed wind): the LAUNCH SHAPE of what follows apply -- never the result (tests/test_gpu_relaxed_settle.py).
+ * mode: 1 = ONE dataflow launch (k_relax_settle: classify every flagged cell, cascade the isolated ones at once and the crowded ones in colour order
+ * behind per-cell waits) in every epoch whose worst-case grid is resident on the device all at once, 0 = two launches (k_relax_filter, then the colour
+ * lists through k_relax_cascade_flow), -1 = the default. Contexts under column strips and processes with SMX_RELAX_CASC_FLOW=0 always take the two
+ * launches. max_waves > 0 caps the resident wavefronts the fused launch may count on (a small value forces the two-launch path: the fall-back, testable on
+ * a small map); lanes = flagged cells per wavefront of k_relax_settle / k_relax_filter, 1..64 (0 = the rule in relax_settle_lanes). */
+int smx_set_relax_settle(smx_ctx* ctx, int32_t mode, int32_t max_waves, int32_t lanes);
+/* ... and what the context did so far: cells that went through the waiting (crowded) path of k_relax_settle, dense epochs that took the fused launch,
+ * dense epochs that took the two launches. Synchronises the context's stream. Any pointer may be null. */
+int smx_get_relax_settle(smx_ctx* ctx, uint64_t* crowded_cells, uint64_t* epochs_fused, uint64_t* epochs_split);
 /* REMOVED in round 5 (nested particles run inside their parent since then; there is nothing to interleave): kept as a symbol that fails
  * loudly (-2, smx_last_error says so) so that a round-4 caller neither crashes at load time nor silently runs another schedule. */
 int smx_set_grid_interleave(smx_ctx* ctx, int32_t k);

@@ -96,7 +96,27 @@ SMX_D bool relax_floods_due(const BatchShared& bs, uint32_t epoch, uint32_t nflo
 // own launch, gives exactly the state the nine colour passes would leave (the restatement, oracle/soil_oracle.cpp r_water_generation,
 // still runs every cell through its colour: tests/test_relaxed.py, test_gpu_relaxed.py compare full states). What is left for the
 // colour passes is the residue: cells in pits and channels where particles crowd (measured: profiles/r04_relaxed.md).
-template <class P>
+// The isolation test with all its loads in flight at once (the dense launches k_relax_filter and k_relax_settle, soilmx.hip): is any OTHER
+// cell within two cells of (x, y) flagged in this epoch? 24 unconditional loads at clamped indices; the positions outside the held columns /
+// the map are masked afterwards. The loop in relax_filter asks the same question one dependent load after the other, over variable bounds.
+SMX_D bool relax_crowded(const DevState& s, const BatchShared& bs, int x, int y) {
+  uint32_t f[25];
+#pragma unroll
+  for (int k = 0; k < 25; k++) {
+    const int xx = x + k / 5 - 2, yy = y + k % 5 - 2;
+    const int xc = xx < s.x_lo ? s.x_lo : (xx >= s.x_hi ? s.x_hi - 1 : xx), yc = yy < 0 ? 0 : (yy >= s.dimy ? s.dimy - 1 : yy);
+    f[k] = k == 12 ? 0u : bs.cflag[(size_t)xc * (size_t)s.dimy + (size_t)yc];
+  }
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < 25; k++) {
+    const int xx = x + k / 5 - 2, yy = y + k % 5 - 2;
+    if (k != 12 && xx >= s.x_lo && xx < s.x_hi && yy >= 0 && yy < s.dimy && f[k] == bs.rtag) any = true;
+  }
+  return any;
+}
+// (BATCHED: the isolation test through relax_crowded -- k_relax_filter alone; the tail and the persistent kernel keep the loop, and with it their code)
+template <class P, bool BATCHED = false>
 SMX_D void relax_filter(Sim<P>& sim, const BatchShared& bs, uint32_t c, bool valid, uint32_t epoch) {
   const DevState& s = sim.s;
   bool need = false; uint32_t col = 0u;
@@ -108,11 +128,14 @@ SMX_D void relax_filter(Sim<P>& sim, const BatchShared& bs, uint32_t c, bool val
     if (!need) sim.n_casc++;                                  // (a listed cell counts in cascade_blk)
     else {
       bool alone = true;                                      // (flags outside the columns this context holds cannot be set by it)
-      const int xa = x - 2 < s.x_lo ? s.x_lo : x - 2, xb = x + 2 >= s.x_hi ? s.x_hi - 1 : x + 2;
-      const int ya = y - 2 < 0 ? 0 : y - 2, yb = y + 2 >= s.dimy ? s.dimy - 1 : y + 2;
-      for (int xx = xa; xx <= xb; xx++)
-        for (int yy = ya; yy <= yb; yy++)
-          if ((xx != x || yy != y) && bs.cflag[(size_t)xx * (size_t)s.dimy + (size_t)yy] == bs.rtag) alone = false;
+      if constexpr (BATCHED) alone = !relax_crowded(s, bs, x, y);
+      else {
+        const int xa = x - 2 < s.x_lo ? s.x_lo : x - 2, xb = x + 2 >= s.x_hi ? s.x_hi - 1 : x + 2;
+        const int ya = y - 2 < 0 ? 0 : y - 2, yb = y + 2 >= s.dimy ? s.dimy - 1 : y + 2;
+        for (int xx = xa; xx <= xb; xx++)
+          for (int yy = ya; yy <= yb; yy++)
+            if ((xx != x || yy != y) && bs.cflag[(size_t)xx * (size_t)s.dimy + (size_t)yy] == bs.rtag) alone = false;
+      }
       if (alone) { sim.cascade_blk(x, y, b); need = false; }
     }
     col = (uint32_t)((x % 3) * 3 + (y % 3));

@@ -630,16 +630,19 @@ __device__ __forceinline__ void relax_commit_flood_steps(const DevState& s, unsi
   for (int off = 32; off > 0; off >>= 1) n += (unsigned long long)__shfl_down((long long)n, off);
   if ((threadIdx.x & 63u) == 0 && n) atomicAdd(&s.ctr[C_FLOOD_NESTED_STEPS], n);
 }
-__global__ void __launch_bounds__(64) k_relax_filter(DevState s, BatchShared bs, uint32_t epoch) {
+// `lpw` flagged cells per wavefront (relax_settle_lanes): an isolated cell cascades right in its lane, a branchy path of ~13 us, and a wavefront
+// costs the UNION of its lanes' paths -- the launch lasted as long as its slowest wavefront of 64 cells, not as long as its work (round 14).
+__global__ void __launch_bounds__(64) k_relax_filter(DevState s, BatchShared bs, uint32_t epoch, uint32_t lpw) {
   const uint32_t par = epoch & 1u;
   uint32_t n = bs.ctrl[BC_NFLAG + par];
   if (n > bs.flag_cap) n = bs.flag_cap;
-  if (blockIdx.x * 64u >= n) return;                         // (the launch is sized for the worst case: most blocks leave here)
+  if (blockIdx.x * lpw >= n) return;                         // (the launch is sized for the worst case: most blocks leave here)
   SMX_LOAD_SOILS(sh)
-  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  const uint32_t i = blockIdx.x * lpw + threadIdx.x;
+  const bool valid = threadIdx.x < lpw && i < n;
   BatchPolicy pol(s, bs);
   Sim<BatchPolicy> sim(s, sh, pol);
-  relax_filter(sim, bs, i < n ? bs.flagl[par][i] : 0u, i < n, epoch);   // (isolated cells cascade in here)
+  relax_filter<BatchPolicy, true>(sim, bs, valid ? bs.flagl[par][i] : 0u, valid, epoch);   // (isolated cells cascade in here)
   sim.flush_counters(); pol.finish(s);
   relax_commit_cascade_counters(s, pol.a_casc, pol.a_tr);
 }
@@ -680,6 +683,43 @@ __device__ __forceinline__ bool spin_wait_while(const uint32_t* f, uint32_t busy
   }
   return true;
 }
+// Publish a cell's state to the wavefronts that poll it, on any XCD: write back what this wavefront stored, WAIT for it, then the flag (agent scope, sc1).
+// Spelled out instead of a release store: where the compiler can prove the vector-memory counter empty on some path into the release, it drops the
+// s_waitcnt vmcnt(0) behind buffer_wbl2 and the flag overtakes the cascade's stores (seen in k_relax_settle's code: the headline's digest moved, the
+// 64 x 64 tests did not notice). The inline wait is invisible to that pass.
+__device__ __forceinline__ void relax_publish(uint32_t* f, uint32_t v) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The dependencies of ONE cell `c` of colour `q`, polled by the whole wavefront (c and q are wavefront-uniform; every lane calls): lane k < 25 watches
+// the k-th cell of the 5 x 5 square around c -- up to 24 independent words, where lane 0 used to poll them one round trip after the other.
+//   SETTLE = false (k_relax_cascade_flow): wait while a cell of an EARLIER colour is listed and not done (cstate == 2T);
+//   SETTLE = true  (k_relax_settle): every FLAGGED cell there must be classified (cstate >= 2T), those of an earlier colour done (2T + 1).
+// Budget and stall flag as spin_wait_while: false = stalled (the caller stops waiting and lets the kernel drain; the host fails the call, -9).
+template <bool SETTLE>
+__device__ __forceinline__ bool relax_wait_block(const DevState& s, const BatchShared& bs, uint32_t c, uint32_t q, uint32_t budget) {
+  const uint32_t lane = threadIdx.x & 63u, t2 = 2u * bs.rtag;
+  const int x = (int)(c / (uint32_t)s.dimy), y = (int)(c - (uint32_t)x * (uint32_t)s.dimy);
+  const int xx = x + (int)(lane / 5u) - 2, yy = y + (int)(lane % 5u) - 2;
+  const bool inr = lane < 25u && lane != 12u && xx >= s.x_lo && xx < s.x_hi && yy >= 0 && yy < s.dimy;
+  const size_t ci = inr ? (size_t)xx * (size_t)s.dimy + (size_t)yy : (size_t)c;     // (a lane with nothing to watch never loads)
+  const bool earlier = inr && (uint32_t)((xx % 3) * 3 + (yy % 3)) < q;
+  const bool watch = SETTLE ? (inr && bs.cflag[ci] == bs.rtag) : earlier;
+  uint32_t* stalled = &bs.ctrl[BC_STALLED];
+  uint32_t spins = 0;
+  while (true) {
+    bool ok = true;
+    if (watch) {
+      const uint32_t st = __hip_atomic_load(&bs.cstate[ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ok = SETTLE ? (st >= t2 && (!earlier || st == t2 + 1u)) : st != t2;
+    }
+    if (__ballot(!ok) == 0ull) return true;
+    __builtin_amdgcn_s_sleep(2);
+    if (++spins > budget) { if (lane == 0u) __hip_atomic_store(stalled, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+    if ((spins & 1023u) == 0u && __hip_atomic_load(stalled, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;   // (one word: uniform)
+  }
+}
 __global__ void __launch_bounds__(64) k_relax_cascade_flow(DevState s, BatchShared bs, uint32_t epoch, uint32_t budget) {
   const uint32_t par = epoch & 1u;
   uint32_t cnt[9], total = 0;
@@ -687,40 +727,100 @@ __global__ void __launch_bounds__(64) k_relax_cascade_flow(DevState s, BatchShar
   for (uint32_t q = 0; q < 9u; q++) { uint32_t n = bs.ctrl[BC_NCASC + 9u * par + q]; if (n > bs.clist_cap) n = bs.clist_cap; cnt[q] = n; total += n; }
   if (total == 0u) return;
   SMX_LOAD_SOILS(sh)
-  __shared__ uint32_t s_i;
+  __shared__ uint32_t s_i, s_c, s_q;
   unsigned long long nc = 0, nt = 0;
   const uint32_t pending = 2u * bs.rtag;
   bool live = true;
   while (true) {
-    if (threadIdx.x == 0) s_i = atomicAdd(&bs.ctrl[BC_CASC_CURSOR], 1u);
+    if (threadIdx.x == 0) {
+      uint32_t i = atomicAdd(&bs.ctrl[BC_CASC_CURSOR], 1u), q = 0;
+      s_i = i;
+      if (i < total) {
+#pragma unroll
+        for (uint32_t k = 0; k < 9u; k++) { if (q == k && i >= cnt[k]) { i -= cnt[k]; q = k + 1u; } }
+        s_c = bs.clist[par][(size_t)q * bs.clist_cap + i]; s_q = q;
+      }
+    }
     __syncthreads();
-    uint32_t i = s_i;
+    const uint32_t i = s_i, c = s_c, q = s_q;
     __syncthreads();
     if (i >= total) break;
+    if (live && !relax_wait_block<false>(s, bs, c, q, budget)) live = false;   // (stalled: the call fails; stop waiting, let the kernel drain)
     if (threadIdx.x == 0) {
-      uint32_t q = 0;
-#pragma unroll
-      for (uint32_t k = 0; k < 9u; k++) { if (q == k && i >= cnt[k]) { i -= cnt[k]; q = k + 1u; } }
-      const uint32_t c = bs.clist[par][(size_t)q * bs.clist_cap + i];
-      const int x = (int)(c / (uint32_t)s.dimy), y = (int)(c - (uint32_t)x * (uint32_t)s.dimy);
-      const int xa = x - 2 < s.x_lo ? s.x_lo : x - 2, xb = x + 2 >= s.x_hi ? s.x_hi - 1 : x + 2;
-      const int ya = y - 2 < 0 ? 0 : y - 2, yb = y + 2 >= s.dimy ? s.dimy - 1 : y + 2;
-      for (int xx = xa; xx <= xb; xx++)
-        for (int yy = ya; yy <= yb; yy++) {
-          if ((uint32_t)((xx % 3) * 3 + (yy % 3)) >= q) continue;            // (only cells of an earlier colour; the cell itself has colour q)
-          uint32_t* f = &bs.cstate[(size_t)xx * (size_t)s.dimy + (size_t)yy];
-          if (live && !spin_wait_while(f, pending, &bs.ctrl[BC_STALLED], budget, 2u, 0u)) live = false;   // (stalled: the call fails; stop waiting, let the kernel drain)
-        }
       __atomic_thread_fence(__ATOMIC_ACQUIRE);
       BatchPolicy pol(s, bs);
       Sim<BatchPolicy> sim(s, sh, pol);
       relax_cascade(sim, c);
       sim.flush_counters(); pol.finish(s);
       nc += pol.a_casc; nt += pol.a_tr;
-      __hip_atomic_store(&bs.cstate[c], pending + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      relax_publish(&bs.cstate[c], pending + 1u);
     }
   }
   if (threadIdx.x == 0) { if (nc) atomicAdd(&s.ctr[C_CASCADE_CALLS], nc); if (nt) atomicAdd(&s.ctr[C_CASCADE_TRANSFERS], nt); }
+}
+// ONE launch after apply (round 14): what k_relax_filter and k_relax_cascade_flow do in two, without colour lists, cursor or tickets. A flagged cell
+// (cflag == T, T = bs.rtag) goes through three states in bs.cstate: unclassified (anything below 2T), classified and waiting (2T), done (2T + 1).
+//   classify  one flagged cell per lane, one pass per wavefront, exactly as relax_filter: load the 3x3 block, cascade_precheck (a cell that needs nothing
+//             counts its call and is done), the isolation test (relax_crowded); publish 2T + 1 or 2T (relax_publish). Nothing here waits.
+//   isolated  cells cascade in their own lane, as in the filter, and publish 2T + 1.
+//   crowded   cells are served by their wavefront one at a time, in ascending colour: the lanes poll the up to 24 cells around it (relax_wait_block) until
+//             every flagged one is classified and every one of an earlier colour is done; acquire fence; the owning lane runs relax_cascade and
+//             publishes 2T + 1 (relax_publish).
+// Why the first wait: relax_filter takes its `need` decision on the map after apply and BEFORE any crowded cascade (a cell that needs nothing then is never
+// cascaded, whatever a neighbour's cascade does to its block later), and two cells' 3x3 blocks overlap exactly when the cells are within two of each other:
+// a crowded cell must not write before all such neighbours have read. With both waits the order between conflicting cells is that of nine colour passes
+// with a barrier each -- what the restatement and the host-thread build define.
+// Forward progress (as for spin_wait_while: only a fault reaches the budget). The host launches at most as many wavefronts as are resident together
+// (relax_settle_plan), so every wavefront of the launch runs. Classification precedes every wait in every wavefront, hence every flagged cell gets
+// classified. Each wavefront holds at most one cell per lane and serves its crowded cells in ascending colour, one at a time; take the unfinished
+// crowded cells of the lowest colour q: all they wait for -- classified neighbours, done neighbours of colours < q -- has happened, and in a wavefront that
+// holds one of them the current cell has colour q too (nothing below q is unfinished), so it proceeds. By induction over the cells everything finishes.
+// Every wait honours the spin budget and BC_STALLED.
+__global__ void __launch_bounds__(64) k_relax_settle(DevState s, BatchShared bs, uint32_t epoch, uint32_t lpw, uint32_t budget, unsigned long long* ncrowded) {
+  const uint32_t par = epoch & 1u;
+  uint32_t n = bs.ctrl[BC_NFLAG + par];
+  if (n > bs.flag_cap) n = bs.flag_cap;
+  if (blockIdx.x * lpw >= n) return;                         // (the launch is sized for the worst case: most blocks leave here)
+  SMX_LOAD_SOILS(sh)
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * lpw + lane, t2 = 2u * bs.rtag;
+  const bool valid = lane < lpw && i < n;
+  const uint32_t c = valid ? bs.flagl[par][i] : 0u;
+  BatchPolicy pol(s, bs);
+  Sim<BatchPolicy> sim(s, sh, pol);
+  uint32_t kind = 0u, col = 0u;                              // 0: nothing to do, 1: isolated, 2: crowded
+  if (valid) {                                               // ---- classify
+    const int x = (int)(c / (uint32_t)s.dimy), y = (int)(c - (uint32_t)x * (uint32_t)s.dimy);
+    Blk b;
+    sim.template load_block<2>(x, y, b);
+    if (!sim.cascade_precheck(b)) sim.n_casc++;              // (a listed cell counts in cascade_blk)
+    else kind = relax_crowded(s, bs, x, y) ? 2u : 1u;
+    col = (uint32_t)((x % 3) * 3 + (y % 3));
+    relax_publish(&bs.cstate[c], kind ? t2 : t2 + 1u);       // (after the loads of the block: a crowded neighbour may write from here on)
+  }
+  const unsigned long long crowd = __ballot(kind == 2u);
+  if (lane == 0u && crowd) atomicAdd(ncrowded, (unsigned long long)__popcll(crowd));
+  bool live = true;
+  for (int q = -1; q < 9; q++) {                             // ---- pass -1: the isolated cells, all lanes at once; passes 0..8: the crowded cells of that colour, one at a time
+    unsigned long long m = __ballot(q < 0 ? kind == 1u : (kind == 2u && col == (uint32_t)q));
+    while (m) {
+      bool mine;
+      if (q < 0) { mine = kind == 1u; m = 0ull; }
+      else {
+        const int owner = __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const uint32_t cc = (uint32_t)__shfl((int)c, owner);
+        if (live && !relax_wait_block<true>(s, bs, cc, (uint32_t)q, budget)) live = false;   // (stalled: the call fails; stop waiting, let the kernel drain)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        mine = (int)lane == owner;
+      }
+      if (mine) {                                            // (one site for both kinds: the cascade's code once in the kernel)
+        relax_cascade(sim, c);
+        relax_publish(&bs.cstate[c], t2 + 1u);
+      }
+    }
+  }
+  sim.flush_counters(); pol.finish(s);
+  relax_commit_cascade_counters(s, pol.a_casc, pol.a_tr);
 }
 // the floods of the relaxed schedule: batch_water_epoch over this epoch's list of ended particles; who is not done joins the next
 // list. The launch has a fixed number of wavefronts; the floods are spread over them as thinly as the list allows (a wavefront costs
@@ -1622,6 +1722,11 @@ struct smx_ctx : EventTimer {
   bool mega_off = false;              // ... the device refused a cooperative launch: the per-phase launches run instead (said once on stderr)
   int relax_persistent = -1, relax_tail_at = -1;   // smx_set_relax_launch (-1: the defaults / the environment's)
   uint32_t flood_launch_no = 0;       // k_relax_floods launches so far (every 7th is bracketed by HIP events)
+  int relax_settle = -1;              // smx_set_relax_settle: -1 default, 0 k_relax_filter + k_relax_cascade_flow, 1 k_relax_settle where residency allows
+  int settle_max_waves = 0, settle_lanes = 0;   // ... a cap on the resident wavefronts it may count on / cells per wavefront (0: the device's / the rule's)
+  int settle_resident = 0;            // wavefronts of k_relax_settle the device holds at once (0: not asked yet, < 0: the occupancy query failed)
+  unsigned long long* d_settle_crowded = nullptr;   // cells that went through the waiting path of k_relax_settle (device counter)
+  uint64_t settle_epochs_fused = 0, settle_epochs_split = 0;   // dense per-phase epochs through k_relax_settle / through the two launches
   uint32_t relax_cap = 0;             // slots the relaxed schedule's buffers are sized for
   int strips_n = 1, strips_a = 16, strips_b = 48;
   int own_x0 = 0, own_x1 = -1;        // strips on several devices: the columns this context owns (-1: to the map's edge)
@@ -1888,6 +1993,22 @@ int smx_set_grid_interleave(smx_ctx* ctx, int32_t) {
 int smx_set_relax_launch(smx_ctx* ctx, int32_t persistent, int32_t tail_at) {
   if (tail_at > 256) { ctx->err = "smx_set_relax_launch: the tail kernel holds at most 256 particles (one per thread of its workgroup)"; return -2; }
   ctx->relax_persistent = persistent < 0 ? -1 : (persistent ? 1 : 0); ctx->relax_tail_at = tail_at < 0 ? -1 : tail_at;
+  return 0;
+}
+int smx_set_relax_settle(smx_ctx* ctx, int32_t mode, int32_t max_waves, int32_t lanes) {
+  if (mode > 1 || lanes > 64) { ctx->err = "smx_set_relax_settle: mode -1, 0 or 1; at most 64 cells per wavefront"; return -2; }
+  ctx->relax_settle = mode < 0 ? -1 : mode; ctx->settle_max_waves = max_waves < 0 ? 0 : max_waves; ctx->settle_lanes = lanes < 0 ? 0 : lanes;
+  return 0;
+}
+int smx_get_relax_settle(smx_ctx* ctx, uint64_t* crowded_cells, uint64_t* epochs_fused, uint64_t* epochs_split) {
+  unsigned long long nc = 0;
+  if (ctx->d_settle_crowded) {
+    HIPCHK(ctx, hipMemcpyAsync(&nc, ctx->d_settle_crowded, sizeof(nc), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (crowded_cells) *crowded_cells = nc;
+  if (epochs_fused) *epochs_fused = ctx->settle_epochs_fused;
+  if (epochs_split) *epochs_split = ctx->settle_epochs_split;
   return 0;
 }
 int smx_set_relax_wind(smx_ctx* ctx, uint32_t min_running, int32_t steps_per_epoch) {
@@ -2545,6 +2666,38 @@ static int relax_epochs_launch(smx_ctx* ctx, uint32_t nlive, uint32_t epoch, uin
   }
   return 0;
 }
+// Flagged cells per wavefront of the two dense launches after apply, k_relax_settle and k_relax_filter: as thin as `waves` wavefronts allow for the worst
+// case of `worst` flagged cells (every entry of every running particle flags another cell), as batch_lanes_per_wave spreads particles. 0: even 64 per
+// wavefront need more. Which lane holds a cell has no influence on results.
+// The count the rule starts from, measured on the headline (profiles/r14_settle.md; generations of 8 000 particles, k_relax_settle):
+//   cells per wavefront      4        8       16       32       64
+//   ms per tick         1 175.6  1 157.3  1 160.5  1 167.6  1 178.1     (water phase: 790.9  774.0  774.1  779.4  788.9)
+// thinner than 8, dispatching wavefronts that read the count and leave costs more than the shorter union of paths saves.
+constexpr uint32_t RELAX_SETTLE_LANES = 8;
+static uint32_t relax_settle_lanes(size_t worst, size_t waves, uint32_t forced) {
+  uint32_t l = forced ? forced : RELAX_SETTLE_LANES;
+  while (l < 64u && (worst + l - 1u) / l > waves) l = std::min(64u, l * 2u);
+  return (worst + l - 1u) / l > waves ? 0u : l;
+}
+// k_relax_settle waits between wavefronts: ALL wavefronts of a launch must be resident together (the argument above the kernel). How many the device
+// holds is asked once per context; an epoch whose worst-case grid exceeds it takes the two launches. 0: this epoch cannot be fused.
+constexpr int RELAX_SETTLE_DEFAULT = 1;   // (three runs each, ms per tick: parent 1 229.9, two launches 1 196.3, fused 1 160.7 -- profiles/r14_settle.md)
+static uint32_t relax_settle_plan(smx_ctx* ctx, size_t worst) {
+  if (!ctx->settle_resident) {
+    int dev = 0, ncu = 0, per_cu = 0;
+    hipGetDevice(&dev);
+    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax_settle, 64, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+    ctx->settle_resident = ncu * per_cu > 0 ? ncu * per_cu : -1;
+  }
+  if (ctx->settle_resident < 0) return 0u;
+  if (!ctx->d_settle_crowded) {
+    if (ctx->mem.dev(ctx->d_settle_crowded, 1) != hipSuccess) { (void)hipGetLastError(); ctx->settle_resident = -1; return 0u; }
+    hipMemsetAsync(ctx->d_settle_crowded, 0, sizeof(unsigned long long), ctx->stream);
+  }
+  const size_t waves = ctx->settle_max_waves > 0 ? std::min<size_t>((size_t)ctx->settle_max_waves, (size_t)ctx->settle_resident) : (size_t)ctx->settle_resident;
+  return relax_settle_lanes(worst, waves, (uint32_t)ctx->settle_lanes);
+}
 // One CHUNK of a particle phase on the context's current generation: the schedule for `nlive_sched` running particles (all strips
 // together), fresh reservations where the schedule asks for them, then the chunk's epochs over the `nlive` slots of bs.live.
 // Shared by the single-context driver (batch_generations) and the step-wise one of the column strips (smx_d_chunk).
@@ -2610,6 +2763,15 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
       const unsigned ncb = (unsigned)(((size_t)nlive * (size_t)(wind ? ctx->bs.rstride : ctx->bs.rsteps) + 63u) / 64u);   // worst case of the flagged / one cascade list
       static const unsigned fb_min = (unsigned)env_int("SMX_RELAX_FLOOD_BLOCKS");
       const unsigned nfb = std::max(fb_min, (unsigned)((nslots + 63u) / 64u));   // floods: at least 1024 wavefronts to spread over
+      static const unsigned casc_blocks = (unsigned)env_int("SMX_RELAX_CASC_BLOCKS");
+      static const unsigned casc_flow = (unsigned)env_int("SMX_RELAX_CASC_FLOW");   // 0: nine launches (round 4)
+      const size_t worst = (size_t)nlive * (size_t)(wind ? ctx->bs.rstride : ctx->bs.rsteps);   // (what ncb holds 64 of per wavefront)
+      // after apply: ONE dataflow launch where every wavefront of its worst-case grid is resident (smx_set_relax_settle; not under column strips, whose
+      // partition nothing on one device can measure; SMX_RELAX_CASC_FLOW=0 keeps meaning filter + nine colour launches) -- else filter + colour lists
+      const bool settle_on = (ctx->relax_settle >= 0 ? ctx->relax_settle : RELAX_SETTLE_DEFAULT) == 1 && !strips && casc_flow && bs.cstate;
+      const uint32_t settle_lpw = settle_on ? relax_settle_plan(ctx, worst) : 0u;
+      uint32_t filter_lpw = relax_settle_lanes(worst, 4096u, (uint32_t)ctx->settle_lanes);      // (no residency to respect: a bound on the grid)
+      if (!filter_lpw) filter_lpw = 64u;
       for (int k = 0; k < chunk_epochs; k++, epoch++) {
         ctx->bs.rtag = ++ctx->relax_tag;
         {
@@ -2622,13 +2784,17 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
           else LAUNCH_WIND_WATER(wind, k_relax_step, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
         }
         hipLaunchKernelGGL(k_relax_apply, dim3(nb64), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
-        hipLaunchKernelGGL(k_relax_filter, dim3(ncb), dim3(64), 0, st, ctx->d, bs, epoch);
-        static const unsigned casc_blocks = (unsigned)env_int("SMX_RELAX_CASC_BLOCKS");
-        static const unsigned casc_flow = (unsigned)env_int("SMX_RELAX_CASC_FLOW");   // 0: nine launches (round 4)
-        if (casc_flow && bs.cstate) hipLaunchKernelGGL(k_relax_cascade_flow, dim3(std::min(ncb, casc_flow)), dim3(64), 0, st, ctx->d, bs, epoch, spin_budget(1u << 24));
-        else {
-          const unsigned ncc = std::min(ncb, std::max(1u, casc_blocks));
-          for (uint32_t col = 0; col < 9u; col++) hipLaunchKernelGGL(k_relax_cascade, dim3(ncc), dim3(64), 0, st, ctx->d, bs, epoch, col);
+        if (settle_lpw) {                                    // filter and colour lists as ONE dataflow launch (k_relax_settle)
+          ctx->settle_epochs_fused++;
+          hipLaunchKernelGGL(k_relax_settle, dim3((unsigned)((worst + settle_lpw - 1u) / settle_lpw)), dim3(64), 0, st, ctx->d, bs, epoch, settle_lpw, spin_budget(1u << 24), ctx->d_settle_crowded);
+        } else {
+          ctx->settle_epochs_split++;
+          hipLaunchKernelGGL(k_relax_filter, dim3((unsigned)((worst + filter_lpw - 1u) / filter_lpw)), dim3(64), 0, st, ctx->d, bs, epoch, filter_lpw);
+          if (casc_flow && bs.cstate) hipLaunchKernelGGL(k_relax_cascade_flow, dim3(std::min(ncb, casc_flow)), dim3(64), 0, st, ctx->d, bs, epoch, spin_budget(1u << 24));
+          else {
+            const unsigned ncc = std::min(ncb, std::max(1u, casc_blocks));
+            for (uint32_t col = 0; col < 9u; col++) hipLaunchKernelGGL(k_relax_cascade, dim3(ncc), dim3(64), 0, st, ctx->d, bs, epoch, col);
+          }
         }
         if (!wind) {                                         // (bracketed every 7th launch of the context: a stride coprime to the every-4th-epoch rule of relax_floods_due)
           ctx->timing.launches_floods_all++;

@@ -315,6 +315,18 @@ class Layermap:
         0 = five launches per epoch; tail_at = running particles from which one workgroup runs whole epochs (0..256); -1 = default"""
         self._chk(self.L.smx_set_relax_launch(self.h, int(persistent), int(tail_at)))
 
+    def set_relax_settle(self, mode: int = -1, max_waves: int = 0, lanes: int = 0):
+        """relaxed epochs, what follows apply: launch shape only, never the result (smx_set_relax_settle): mode 1 = one dataflow launch
+        (k_relax_settle) where all its wavefronts are resident, 0 = filter + colour lists as two launches, -1 = default; max_waves caps the
+        resident wavefronts the fused launch may count on (0 = the device's), lanes = flagged cells per wavefront (0 = the rule's)"""
+        self._chk(self.L.smx_set_relax_settle(self.h, int(mode), int(max_waves), int(lanes)))
+
+    def relax_settle_stats(self) -> dict:
+        """cells that went through the waiting (crowded) path of k_relax_settle; dense epochs that took the fused / the two-launch path"""
+        c, f, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.L.smx_get_relax_settle(self.h, C.byref(c), C.byref(f), C.byref(s)))
+        return {"crowded_cells": int(c.value), "epochs_fused": int(f.value), "epochs_split": int(s.value)}
+
     def set_water_generations(self, k: int):
         """throughput engines: the water phase's particles as k consecutive generations of n/k (smx_set_water_generations)"""
         self._chk(self.L.smx_set_water_generations(self.h, int(k)))
