@@ -104,7 +104,8 @@ typedef struct smx_timing {
    * and the generations of suspended nested particles the grid pass leaves behind (part of ms_grid) */
   double ms_kernel_epochs, ms_kernel_tail, ms_kernel_grid_children;
   uint64_t launches_kernel_epochs, epochs_kernel_epochs, launches_kernel_tail, epochs_kernel_tail, launches_kernel_grid_children;
-  /* k_relax_floods: every 7th launch of a context is bracketed (ms / launches_kernel_floods); launches_floods_all counts every launch */
+  /* k_relax_floods: every 7th launch of a context is bracketed (ms / launches_kernel_floods); launches_floods_all counts every launch. Under
+   * smx_set_relax_settle mode 2 the launch is k_relax_settle_floods: the figures then time the JOINED launch, settle included. */
   double ms_kernel_floods;
   uint64_t launches_kernel_floods, launches_floods_all;
 } smx_timing;
@@ -443,13 +444,19 @@ int smx_set_relax_launch(smx_ctx* ctx, int32_t persistent, int32_t tail_at);
 /* relaxed schedule, dense epochs (water, and relaxed wind): the LAUNCH SHAPE of what follows apply -- never the result (tests/test_gpu_relaxed_settle.py).
  * mode: 1 = ONE dataflow launch (k_relax_settle: classify every flagged cell, cascade the isolated ones at once and the crowded ones in colour order
  * behind per-cell waits) in every epoch whose worst-case grid is resident on the device all at once, 0 = two launches (k_relax_filter, then the colour
- * lists through k_relax_cascade_flow), -1 = the default. Contexts under column strips and processes with SMX_RELAX_CASC_FLOW=0 always take the two
+ * lists through k_relax_cascade_flow), 2 = as 1, and in water epochs the floods join that launch (k_relax_settle_floods: a flood that will act waits only
+ * for the flagged cells within one cell of the tiles it holds) where settle and flood wavefronts are resident together, else mode 1's two launches
+ * (k_relax_settle, k_relax_floods); -1 = the default. Contexts under column strips and processes with SMX_RELAX_CASC_FLOW=0 always take the two
  * launches. max_waves > 0 caps the resident wavefronts the fused launch may count on (a small value forces the two-launch path: the fall-back, testable on
  * a small map); lanes = flagged cells per wavefront of k_relax_settle / k_relax_filter, 1..64 (0 = the rule in relax_settle_lanes). */
 int smx_set_relax_settle(smx_ctx* ctx, int32_t mode, int32_t max_waves, int32_t lanes);
 /* ... and what the context did so far: cells that went through the waiting (crowded) path of k_relax_settle, dense epochs that took the fused launch,
  * dense epochs that took the two launches. Synchronises the context's stream. Any pointer may be null. */
 int smx_get_relax_settle(smx_ctx* ctx, uint64_t* crowded_cells, uint64_t* epochs_fused, uint64_t* epochs_split);
+/* ... and of the fused epochs, the mode-2 part: water epochs that took k_relax_settle_floods (they count under epochs_fused too), floods that acted in
+ * them, and those of them that found at least one cell flagged in the epoch in their tiles' rectangle widened by one cell -- a function of the input,
+ * not of timing (whether the flood had to spin is not counted). Synchronises the context's stream. Any pointer may be null. */
+int smx_get_relax_flood_flow(smx_ctx* ctx, uint64_t* epochs_joined, uint64_t* floods_acted, uint64_t* floods_gated);
 /* REMOVED in round 5 (nested particles run inside their parent since then; there is nothing to interleave): kept as a symbol that fails
  * loudly (-2, smx_last_error says so) so that a round-4 caller neither crashes at load time nor silently runs another schedule. */
 int smx_set_grid_interleave(smx_ctx* ctx, int32_t k);

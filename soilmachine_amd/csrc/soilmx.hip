@@ -776,6 +776,49 @@ __global__ void __launch_bounds__(64) k_relax_cascade_flow(DevState s, BatchShar
 // crowded cells of the lowest colour q: all they wait for -- classified neighbours, done neighbours of colours < q -- has happened, and in a wavefront that
 // holds one of them the current cell has colour q too (nothing below q is unfinished), so it proceeds. By induction over the cells everything finishes.
 // Every wait honours the spin budget and BC_STALLED.
+// (The body of a settle block behind its early exit, for blocks [0, S) of k_relax_settle_floods: the text of k_relax_settle's own body below, which stays
+//  spelled out there -- calling this function from it changes that kernel's register allocation and with it its machine code. Keep the two equal.)
+__device__ __forceinline__ void relax_settle_block(const DevState& s, const BatchShared& bs, const SoilP* sh, uint32_t par, uint32_t n, uint32_t lpw, uint32_t budget, unsigned long long* ncrowded) {
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * lpw + lane, t2 = 2u * bs.rtag;
+  const bool valid = lane < lpw && i < n;
+  const uint32_t c = valid ? bs.flagl[par][i] : 0u;
+  BatchPolicy pol(s, bs);
+  Sim<BatchPolicy> sim(s, sh, pol);
+  uint32_t kind = 0u, col = 0u;                              // 0: nothing to do, 1: isolated, 2: crowded
+  if (valid) {                                               // ---- classify
+    const int x = (int)(c / (uint32_t)s.dimy), y = (int)(c - (uint32_t)x * (uint32_t)s.dimy);
+    Blk b;
+    sim.template load_block<2>(x, y, b);
+    if (!sim.cascade_precheck(b)) sim.n_casc++;              // (a listed cell counts in cascade_blk)
+    else kind = relax_crowded(s, bs, x, y) ? 2u : 1u;
+    col = (uint32_t)((x % 3) * 3 + (y % 3));
+    relax_publish(&bs.cstate[c], kind ? t2 : t2 + 1u);       // (after the loads of the block: a crowded neighbour may write from here on)
+  }
+  const unsigned long long crowd = __ballot(kind == 2u);
+  if (lane == 0u && crowd) atomicAdd(ncrowded, (unsigned long long)__popcll(crowd));
+  bool live = true;
+  for (int q = -1; q < 9; q++) {                             // ---- pass -1: the isolated cells, all lanes at once; passes 0..8: the crowded cells of that colour, one at a time
+    unsigned long long m = __ballot(q < 0 ? kind == 1u : (kind == 2u && col == (uint32_t)q));
+    while (m) {
+      bool mine;
+      if (q < 0) { mine = kind == 1u; m = 0ull; }
+      else {
+        const int owner = __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const uint32_t cc = (uint32_t)__shfl((int)c, owner);
+        if (live && !relax_wait_block<true>(s, bs, cc, (uint32_t)q, budget)) live = false;   // (stalled: the call fails; stop waiting, let the kernel drain)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        mine = (int)lane == owner;
+      }
+      if (mine) {                                            // (one site for both kinds: the cascade's code once in the kernel)
+        relax_cascade(sim, c);
+        relax_publish(&bs.cstate[c], t2 + 1u);
+      }
+    }
+  }
+  sim.flush_counters(); pol.finish(s);
+  relax_commit_cascade_counters(s, pol.a_casc, pol.a_tr);
+}
 __global__ void __launch_bounds__(64) k_relax_settle(DevState s, BatchShared bs, uint32_t epoch, uint32_t lpw, uint32_t budget, unsigned long long* ncrowded) {
   const uint32_t par = epoch & 1u;
   uint32_t n = bs.ctrl[BC_NFLAG + par];
@@ -853,6 +896,127 @@ __global__ void __launch_bounds__(64) k_relax_floods(DevState s, BatchShared bs,
   }
   unsigned long long nst = 0;
   if (act) slot = bs.flist[par][i];
+  if (act) {
+    BatchPolicy pol(s, bs);
+    Sim<BatchPolicy> sim(s, sh, pol);
+    Frame st[MAX_FRAMES];
+    const unsigned long long t0 = prof ? wall_clock64() : 0ull;
+    batch_water_epoch(sim, bs, slot, epoch, st);
+    sim.flush_counters(); nst = pol.a_nsteps; pol.finish(s);
+    again = bs.water[slot].state == B_ENDED;
+    if (prof) {
+      const unsigned long long dt = wall_clock64() - t0;
+      if (again) atomicAdd(&g_flood_prof[66], 1ull);
+      else { const int b = 63 - __clzll((long long)(dt | 1ull)); atomicAdd(&g_flood_prof[b > 31 ? 31 : b], 1ull); atomicAdd(&g_flood_prof[32 + (b > 31 ? 31 : b)], nst); atomicAdd(&g_flood_prof[64], 1ull); atomicAdd(&g_flood_prof[65], dt); }
+    }
+  }
+  relax_flood_later(bs, slot, par ^ 1u, again);
+  relax_commit_flood_steps(s, nst);
+}
+// The gate of ONE flood in k_relax_settle_floods, run by the whole wavefront (the rectangle is wavefront-uniform; every lane calls): the flood holds the
+// tiles `r` and will write map cells inside them. The lanes scan bs.cflag over the tiles' cells widened by one cell (clamped to the held columns and the
+// map, as relax_wait_block clamps), 256 cells per round with the four flag loads of a lane in flight together -- a flood of spill 3 holds at most 3 x 3
+// tiles of 4 x 4 cells: 14 x 14 = 196 words, one round -- and the lanes that found a cell flagged in this epoch poll its bs.cstate until it reads done
+// (2T + 1). Budget and stall flag as relax_wait_block: false = stalled. `any`: was a flagged cell found at all (a function of the input, not of timing).
+__device__ __forceinline__ bool relax_flood_gate(const DevState& s, const BatchShared& bs, const BRect& r, uint32_t budget, bool& any) {
+  const uint32_t lane = threadIdx.x & 63u, done = 2u * bs.rtag + 1u;
+  int cx0 = (r.tx0 << bs.tshift) - 1, cx1 = (r.tx1 + 1) << bs.tshift, cy0 = (r.ty0 << bs.tshift) - 1, cy1 = (r.ty1 + 1) << bs.tshift;
+  if (cx0 < s.x_lo) cx0 = s.x_lo;
+  if (cx1 > s.x_hi - 1) cx1 = s.x_hi - 1;
+  if (cy0 < 0) cy0 = 0;
+  if (cy1 > s.dimy - 1) cy1 = s.dimy - 1;
+  any = false;
+  if (cx1 < cx0 || cy1 < cy0) return true;
+  const uint32_t h = (uint32_t)(cy1 - cy0 + 1), total = (uint32_t)(cx1 - cx0 + 1) * h;
+  uint32_t* stalled = &bs.ctrl[BC_STALLED];
+  uint32_t spins = 0;
+  for (uint32_t k0 = 0; k0 < total; k0 += 256u) {
+    size_t ci[4]; uint32_t f[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) {                        // (consecutive lanes along y: consecutive words)
+      const uint32_t k = k0 + 64u * j + lane, kc = k < total ? k : 0u;
+      ci[j] = (size_t)(cx0 + (int)(kc / h)) * (size_t)s.dimy + (size_t)(cy0 + (int)(kc % h));
+      f[j] = bs.cflag[ci[j]];
+      if (k >= total) f[j] = bs.rtag - 1u;                     // (nothing to watch)
+    }
+    uint32_t watch = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) if (f[j] == bs.rtag) watch |= 1u << j;
+    if (__ballot(watch != 0u) == 0ull) continue;
+    any = true;
+    while (true) {
+#pragma unroll
+      for (uint32_t j = 0; j < 4u; j++)
+        if ((watch >> j) & 1u) { if (__hip_atomic_load(&bs.cstate[ci[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == done) watch &= ~(1u << j); }
+      if (__ballot(watch != 0u) == 0ull) break;
+      __builtin_amdgcn_s_sleep(2);
+      if (++spins > budget) { if (lane == 0u) __hip_atomic_store(stalled, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+      if ((spins & 1023u) == 0u && __hip_atomic_load(stalled, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;   // (one word: uniform)
+    }
+  }
+  return true;
+}
+// Settle and floods of a dense water epoch as ONE launch (round 15; smx_set_relax_settle mode 2). After k_relax_settle the floods of the epoch waited for the
+// whole settle launch to drain -- the longest chain of crowded cells anywhere on the map, plus a kernel boundary -- where a flood needs only the few flagged
+// cells next to its own tiles settled. Here the floods join the dataflow over bs.cstate:
+//   blocks [0, S)      are the blocks of k_relax_settle (relax_settle_block): classification, isolated pass, crowded passes, waits, publishes;
+//   blocks [S, S + F)  take the epoch's flood list as k_relax_floods does, with the same due test; a list that is not due moves on (relax_flood_later).
+//                      A listed flood that will not act (it does not hold its tiles, or what it needs next lies outside them) re-claims for the next
+//                      epoch as today: it touches no map cell and waits for nothing. A flood that WILL act passes relax_flood_gate first; a wavefront
+//                      with several of them gates them one after the other, then an agent-scope acquire fence, then batch_water_epoch for all its lanes.
+// Why the state after the launch is the one the two launches leave:
+//   * a flood reads and writes no map cell outside the claim tiles it holds (batch_water_epoch: pol.region = held; run_nested and flood_fits suspend
+//     whatever would leave them), a settle cascade touches the 3x3 block of its flagged cell and nothing else (Particle::cascade(.., 0)): a cell's block
+//     overlaps the flood's tiles exactly when the cell lies within one cell of the tiles' rectangle -- what the gate scans;
+//   * every flag of the epoch is set before the launch starts (k_relax_step), and the claim plane and the slot's record that decide whether a flood acts are
+//     written by nobody in this launch but the flood's own lane (floods claim in the NEXT epoch's plane);
+//   * every flagged cell ends at 2T + 1 -- at classification if it needs nothing, otherwise after its cascade (relax_publish: the cascade's stores first);
+//   * so after the wait and the acquire the cells the flood can see are exactly as k_relax_settle leaves them, and no later cascade can reach them;
+//   * floods write nothing settle reads: flist of the next parity, the claim plane of the next epoch, map cells inside their tiles after the wait.
+// Forward progress: flood wavefronts wait for settle wavefronts, never the other way round, and settle wavefronts among themselves as in k_relax_settle, so
+// that kernel's argument carries over once all S + F wavefronts are resident together -- relax_settle_floods_plan sizes the grid from THIS kernel's
+// occupancy. Every wait honours the spin budget and BC_STALLED.
+// nflow: [0] floods that acted, [1] those of them whose gate found a flagged cell (smx_get_relax_flood_flow). prof: SMX_FLOOD_PROF as in k_relax_floods.
+__global__ void __launch_bounds__(64) k_relax_settle_floods(DevState s, BatchShared bs, uint32_t epoch, uint32_t lpw, uint32_t nsettle, uint32_t budget, uint32_t prof,
+                                                            unsigned long long* ncrowded, unsigned long long* nflow) {
+  const uint32_t par = epoch & 1u;
+  const bool settle = blockIdx.x < nsettle;
+  const uint32_t fb = blockIdx.x - nsettle, nfb = gridDim.x - nsettle;
+  uint32_t n = bs.ctrl[(settle ? BC_NFLAG : BC_NFLOOD) + par];
+  if (n > (settle ? bs.flag_cap : bs.list_cap)) n = settle ? bs.flag_cap : bs.list_cap;
+  uint32_t flpw = (n + nfb - 1u) / nfb;                       // floods per wavefront: as thin as the list allows
+  if (flpw > 64u) flpw = 64u;                                 // (n > 64 * nfb cannot happen: the host sizes F for the generation's slots)
+  if ((settle ? blockIdx.x * lpw : fb * flpw) >= n) return;   // (sized for the worst case: most blocks leave here)
+  SMX_LOAD_SOILS(sh)
+  if (settle) { relax_settle_block(s, bs, sh, par, n, lpw, budget, ncrowded); return; }
+  const uint32_t i = fb * flpw + threadIdx.x;
+  const bool act = threadIdx.x < flpw && i < n;
+  bool again = false;
+  const uint32_t slot = act ? bs.flist[par][i] : 0u;
+  if (!relax_floods_due(bs, epoch, n, bs.ctrl[BC_NRUN + par])) {  // not this epoch: the whole list moves on
+    relax_flood_later(bs, slot, par ^ 1u, act);
+    return;
+  }
+  BRect rect = BRect{0, -1, 0, -1};
+  bool acts = false;                                          // will batch_water_epoch flood? (its own tests, on words nobody else writes in this launch)
+  if (act) {
+    const BWater& q = bs.water[slot];
+    rect = q.rect;
+    acts = q.state == B_ENDED && bs.maxsteps > 0 && water_floods(q.w) && brect_contains(rect, water_intent_flood(s, bs, q.w))
+           && rect.tx0 >= bs.txb && rect.tx1 < bs.txe && bholds(bs, (int)par, rect, btag(epoch, slot));
+  }
+  bool live = true; uint32_t gated = 0u;
+  const unsigned long long acting = __ballot(acts);
+  for (unsigned long long m = acting; m; m &= m - 1ull) {
+    const int owner = __ffsll((long long)m) - 1;
+    const BRect r = BRect{__shfl(rect.tx0, owner), __shfl(rect.tx1, owner), __shfl(rect.ty0, owner), __shfl(rect.ty1, owner)};
+    bool any = false;
+    if (live && !relax_flood_gate(s, bs, r, budget, any)) live = false;   // (stalled: the call fails; stop waiting, let the kernel drain)
+    gated += any ? 1u : 0u;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (threadIdx.x == 0u && acting) { atomicAdd(&nflow[0], (unsigned long long)__popcll(acting)); if (gated) atomicAdd(&nflow[1], (unsigned long long)gated); }
+  unsigned long long nst = 0;
   if (act) {
     BatchPolicy pol(s, bs);
     Sim<BatchPolicy> sim(s, sh, pol);
@@ -1722,11 +1886,15 @@ struct smx_ctx : EventTimer {
   bool mega_off = false;              // ... the device refused a cooperative launch: the per-phase launches run instead (said once on stderr)
   int relax_persistent = -1, relax_tail_at = -1;   // smx_set_relax_launch (-1: the defaults / the environment's)
   uint32_t flood_launch_no = 0;       // k_relax_floods launches so far (every 7th is bracketed by HIP events)
-  int relax_settle = -1;              // smx_set_relax_settle: -1 default, 0 k_relax_filter + k_relax_cascade_flow, 1 k_relax_settle where residency allows
+  int relax_settle = -1;              // smx_set_relax_settle: -1 default, 0 k_relax_filter + k_relax_cascade_flow, 1 k_relax_settle where residency allows,
+                                      // 2 k_relax_settle_floods (water epochs: settle and floods in one launch) where its residency allows, else as 1
   int settle_max_waves = 0, settle_lanes = 0;   // ... a cap on the resident wavefronts it may count on / cells per wavefront (0: the device's / the rule's)
   int settle_resident = 0;            // wavefronts of k_relax_settle the device holds at once (0: not asked yet, < 0: the occupancy query failed)
-  unsigned long long* d_settle_crowded = nullptr;   // cells that went through the waiting path of k_relax_settle (device counter)
-  uint64_t settle_epochs_fused = 0, settle_epochs_split = 0;   // dense per-phase epochs through k_relax_settle / through the two launches
+  int joined_resident = 0;            // ... and of k_relax_settle_floods
+  unsigned long long* d_settle_crowded = nullptr;   // device counters: [0] cells that went through the waiting path of k_relax_settle(_floods),
+                                                    // [1] floods that acted in k_relax_settle_floods, [2] those whose gate found a flagged cell
+  uint64_t settle_epochs_fused = 0, settle_epochs_split = 0;   // dense per-phase epochs through k_relax_settle(_floods) / through the two launches
+  uint64_t settle_epochs_joined = 0;  // ... of the fused ones: water epochs through k_relax_settle_floods
   uint32_t relax_cap = 0;             // slots the relaxed schedule's buffers are sized for
   int strips_n = 1, strips_a = 16, strips_b = 48;
   int own_x0 = 0, own_x1 = -1;        // strips on several devices: the columns this context owns (-1: to the map's edge)
@@ -1783,7 +1951,7 @@ static void drain_events(EventTimer* ctx) {
       case PH_K_TAIL: ctx->timing.ms_kernel_tail += ms; ctx->timing.launches_kernel_tail++; ctx->timing.epochs_kernel_tail += p.launches; break;          // k_relax_tail (p.launches = its epochs)
       case PH_K_EPOCHS: ctx->timing.ms_kernel_epochs += ms; ctx->timing.launches_kernel_epochs++; ctx->timing.epochs_kernel_epochs += p.launches; break;   // k_relax_epochs
       case PH_K_GRID_CHILDREN: ctx->timing.ms_kernel_grid_children += ms; ctx->timing.launches_kernel_grid_children += p.launches; break;
-      case PH_K_FLOODS: ctx->timing.ms_kernel_floods += ms; ctx->timing.launches_kernel_floods += p.launches; break;       // k_relax_floods, the bracketed launches
+      case PH_K_FLOODS: ctx->timing.ms_kernel_floods += ms; ctx->timing.launches_kernel_floods += p.launches; break;       // k_relax_floods (k_relax_settle_floods where it replaces it), the bracketed launches
     }
     ctx->evpool.push_back(p.a); ctx->evpool.push_back(p.b);
   }
@@ -1996,7 +2164,7 @@ int smx_set_relax_launch(smx_ctx* ctx, int32_t persistent, int32_t tail_at) {
   return 0;
 }
 int smx_set_relax_settle(smx_ctx* ctx, int32_t mode, int32_t max_waves, int32_t lanes) {
-  if (mode > 1 || lanes > 64) { ctx->err = "smx_set_relax_settle: mode -1, 0 or 1; at most 64 cells per wavefront"; return -2; }
+  if (mode > 2 || lanes > 64) { ctx->err = "smx_set_relax_settle: mode -1, 0, 1 or 2; at most 64 cells per wavefront"; return -2; }
   ctx->relax_settle = mode < 0 ? -1 : mode; ctx->settle_max_waves = max_waves < 0 ? 0 : max_waves; ctx->settle_lanes = lanes < 0 ? 0 : lanes;
   return 0;
 }
@@ -2009,6 +2177,17 @@ int smx_get_relax_settle(smx_ctx* ctx, uint64_t* crowded_cells, uint64_t* epochs
   if (crowded_cells) *crowded_cells = nc;
   if (epochs_fused) *epochs_fused = ctx->settle_epochs_fused;
   if (epochs_split) *epochs_split = ctx->settle_epochs_split;
+  return 0;
+}
+int smx_get_relax_flood_flow(smx_ctx* ctx, uint64_t* epochs_joined, uint64_t* floods_acted, uint64_t* floods_gated) {
+  unsigned long long nf[2] = {0, 0};
+  if (ctx->d_settle_crowded) {
+    HIPCHK(ctx, hipMemcpyAsync(nf, ctx->d_settle_crowded + 1, sizeof(nf), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (epochs_joined) *epochs_joined = ctx->settle_epochs_joined;
+  if (floods_acted) *floods_acted = nf[0];
+  if (floods_gated) *floods_gated = nf[1];
   return 0;
 }
 int smx_set_relax_wind(smx_ctx* ctx, uint32_t min_running, int32_t steps_per_epoch) {
@@ -2681,22 +2860,46 @@ static uint32_t relax_settle_lanes(size_t worst, size_t waves, uint32_t forced) 
 }
 // k_relax_settle waits between wavefronts: ALL wavefronts of a launch must be resident together (the argument above the kernel). How many the device
 // holds is asked once per context; an epoch whose worst-case grid exceeds it takes the two launches. 0: this epoch cannot be fused.
-constexpr int RELAX_SETTLE_DEFAULT = 1;   // (three runs each, ms per tick: parent 1 229.9, two launches 1 196.3, fused 1 160.7 -- profiles/r14_settle.md)
-static uint32_t relax_settle_plan(smx_ctx* ctx, size_t worst) {
-  if (!ctx->settle_resident) {
-    int dev = 0, ncu = 0, per_cu = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_relax_settle, 64, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-    ctx->settle_resident = ncu * per_cu > 0 ? ncu * per_cu : -1;
-  }
-  if (ctx->settle_resident < 0) return 0u;
+constexpr int RELAX_SETTLE_DEFAULT = 2;   // (three runs each, ms per tick: parent 1 229.9, two launches 1 196.3, fused 1 160.7 -- profiles/r14_settle.md;
+                                          //  with the floods inside the fused launch, mode 2: profiles/r15_settle_floods.md)
+static int relax_resident_waves(const void* kernel) {                  // wavefronts of a one-wavefront-per-workgroup kernel the device holds at once (-1: the query failed)
+  int dev = 0, ncu = 0, per_cu = 0;
+  hipGetDevice(&dev);
+  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+  return ncu * per_cu > 0 ? ncu * per_cu : -1;
+}
+static bool relax_settle_counters(smx_ctx* ctx) {
   if (!ctx->d_settle_crowded) {
-    if (ctx->mem.dev(ctx->d_settle_crowded, 1) != hipSuccess) { (void)hipGetLastError(); ctx->settle_resident = -1; return 0u; }
-    hipMemsetAsync(ctx->d_settle_crowded, 0, sizeof(unsigned long long), ctx->stream);
+    if (ctx->mem.dev(ctx->d_settle_crowded, 3) != hipSuccess) { (void)hipGetLastError(); return false; }
+    hipMemsetAsync(ctx->d_settle_crowded, 0, 3 * sizeof(unsigned long long), ctx->stream);
   }
+  return true;
+}
+static uint32_t relax_settle_plan(smx_ctx* ctx, size_t worst) {
+  if (!ctx->settle_resident) ctx->settle_resident = relax_resident_waves((const void*)k_relax_settle);
+  if (ctx->settle_resident < 0) return 0u;
+  if (!relax_settle_counters(ctx)) { ctx->settle_resident = -1; return 0u; }
   const size_t waves = ctx->settle_max_waves > 0 ? std::min<size_t>((size_t)ctx->settle_max_waves, (size_t)ctx->settle_resident) : (size_t)ctx->settle_resident;
   return relax_settle_lanes(worst, waves, (uint32_t)ctx->settle_lanes);
+}
+// k_relax_settle_floods: S settle and F flood wavefronts must be resident TOGETHER (flood wavefronts wait for settle wavefronts). The resident count is
+// this kernel's own (the flood body's registers: about one wavefront per SIMD, half of k_relax_settle's). F >= ceil(nslots / 64), because the host does
+// not know the length of the flood list; the settle lanes per wavefront double from the rule's 8 until S fits beside that (8 and 16 lanes are one run's
+// noise apart, profiles/r14_settle.md); the floods then spread over what is left, up to the `nfb` wavefronts k_relax_floods gets. false: it does not fit,
+// the epoch takes k_relax_settle and k_relax_floods.
+static bool relax_settle_floods_plan(smx_ctx* ctx, size_t worst, uint32_t nslots, unsigned nfb, uint32_t& lpw, unsigned& nsettle, unsigned& nfloods) {
+  if (!ctx->joined_resident) ctx->joined_resident = relax_resident_waves((const void*)k_relax_settle_floods);
+  if (ctx->joined_resident < 0) return false;
+  if (!relax_settle_counters(ctx)) { ctx->joined_resident = -1; return false; }
+  const size_t waves = ctx->settle_max_waves > 0 ? std::min<size_t>((size_t)ctx->settle_max_waves, (size_t)ctx->joined_resident) : (size_t)ctx->joined_resident;
+  const size_t fmin = std::max<size_t>(1u, ((size_t)nslots + 63u) / 64u);
+  if (waves <= fmin) return false;
+  lpw = relax_settle_lanes(worst, waves - fmin, (uint32_t)ctx->settle_lanes);
+  if (!lpw) return false;
+  nsettle = (unsigned)((worst + lpw - 1u) / lpw);
+  nfloods = (unsigned)std::min<size_t>(waves - nsettle, std::max<size_t>(nfb, fmin));
+  return true;
 }
 // One CHUNK of a particle phase on the context's current generation: the schedule for `nlive_sched` running particles (all strips
 // together), fresh reservations where the schedule asks for them, then the chunk's epochs over the `nlive` slots of bs.live.
@@ -2768,8 +2971,11 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
       const size_t worst = (size_t)nlive * (size_t)(wind ? ctx->bs.rstride : ctx->bs.rsteps);   // (what ncb holds 64 of per wavefront)
       // after apply: ONE dataflow launch where every wavefront of its worst-case grid is resident (smx_set_relax_settle; not under column strips, whose
       // partition nothing on one device can measure; SMX_RELAX_CASC_FLOW=0 keeps meaning filter + nine colour launches) -- else filter + colour lists
-      const bool settle_on = (ctx->relax_settle >= 0 ? ctx->relax_settle : RELAX_SETTLE_DEFAULT) == 1 && !strips && casc_flow && bs.cstate;
-      const uint32_t settle_lpw = settle_on ? relax_settle_plan(ctx, worst) : 0u;
+      const int settle_mode = ctx->relax_settle >= 0 ? ctx->relax_settle : RELAX_SETTLE_DEFAULT;
+      const bool settle_on = settle_mode >= 1 && !strips && casc_flow && bs.cstate;
+      uint32_t joined_lpw = 0u; unsigned joined_s = 0u, joined_f = 0u;   // water: settle and floods as ONE launch (k_relax_settle_floods) where S + F wavefronts are resident
+      const bool joined = settle_on && settle_mode == 2 && !wind && relax_settle_floods_plan(ctx, worst, nslots, nfb, joined_lpw, joined_s, joined_f);
+      const uint32_t settle_lpw = settle_on && !joined ? relax_settle_plan(ctx, worst) : 0u;
       uint32_t filter_lpw = relax_settle_lanes(worst, 4096u, (uint32_t)ctx->settle_lanes);      // (no residency to respect: a bound on the grid)
       if (!filter_lpw) filter_lpw = 64u;
       for (int k = 0; k < chunk_epochs; k++, epoch++) {
@@ -2784,6 +2990,15 @@ static int run_chunk(smx_ctx* ctx, bool wind, uint32_t nlive_sched, uint32_t nli
           else LAUNCH_WIND_WATER(wind, k_relax_step, dim3(nbl), dim3(64), st, ctx->d, bs, nlive, epoch, lpw);
         }
         hipLaunchKernelGGL(k_relax_apply, dim3(nb64), dim3(64), 0, st, ctx->d, bs, nlive, epoch);
+        if (joined) {                                        // settle and floods as ONE dataflow launch: counted and bracketed as the flood launch it replaces
+          ctx->settle_epochs_fused++; ctx->settle_epochs_joined++;
+          ctx->timing.launches_floods_all++;
+          const uint32_t fprof = flood_prof();
+          const bool timed = ctx->flood_launch_no++ % 7u == 0u;
+          if (timed) { PhaseTimer tk(ctx, PH_K_FLOODS, 1u); hipLaunchKernelGGL(k_relax_settle_floods, dim3(joined_s + joined_f), dim3(64), 0, st, ctx->d, bs, epoch, joined_lpw, joined_s, spin_budget(1u << 24), fprof, ctx->d_settle_crowded, ctx->d_settle_crowded + 1); }
+          else hipLaunchKernelGGL(k_relax_settle_floods, dim3(joined_s + joined_f), dim3(64), 0, st, ctx->d, bs, epoch, joined_lpw, joined_s, spin_budget(1u << 24), fprof, ctx->d_settle_crowded, ctx->d_settle_crowded + 1);
+          continue;
+        }
         if (settle_lpw) {                                    // filter and colour lists as ONE dataflow launch (k_relax_settle)
           ctx->settle_epochs_fused++;
           hipLaunchKernelGGL(k_relax_settle, dim3((unsigned)((worst + settle_lpw - 1u) / settle_lpw)), dim3(64), 0, st, ctx->d, bs, epoch, settle_lpw, spin_budget(1u << 24), ctx->d_settle_crowded);

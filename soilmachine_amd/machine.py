@@ -317,7 +317,8 @@ class Layermap:
 
     def set_relax_settle(self, mode: int = -1, max_waves: int = 0, lanes: int = 0):
         """relaxed epochs, what follows apply: launch shape only, never the result (smx_set_relax_settle): mode 1 = one dataflow launch
-        (k_relax_settle) where all its wavefronts are resident, 0 = filter + colour lists as two launches, -1 = default; max_waves caps the
+        (k_relax_settle) where all its wavefronts are resident, 0 = filter + colour lists as two launches, 2 = as 1 with the water epochs' floods
+        inside the same launch (k_relax_settle_floods) where settle and flood wavefronts are resident together, -1 = default; max_waves caps the
         resident wavefronts the fused launch may count on (0 = the device's), lanes = flagged cells per wavefront (0 = the rule's)"""
         self._chk(self.L.smx_set_relax_settle(self.h, int(mode), int(max_waves), int(lanes)))
 
@@ -326,6 +327,13 @@ class Layermap:
         c, f, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._chk(self.L.smx_get_relax_settle(self.h, C.byref(c), C.byref(f), C.byref(s)))
         return {"crowded_cells": int(c.value), "epochs_fused": int(f.value), "epochs_split": int(s.value)}
+
+    def relax_flood_flow_stats(self) -> dict:
+        """water epochs that took k_relax_settle_floods (set_relax_settle mode 2), floods that acted in them, and those of them that found a
+        flagged cell next to their tiles (a function of the input, not of timing)"""
+        j, a, g = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.L.smx_get_relax_flood_flow(self.h, C.byref(j), C.byref(a), C.byref(g)))
+        return {"epochs_joined": int(j.value), "floods_acted": int(a.value), "floods_gated": int(g.value)}
 
     def set_water_generations(self, k: int):
         """throughput engines: the water phase's particles as k consecutive generations of n/k (smx_set_water_generations)"""
