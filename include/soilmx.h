@@ -330,6 +330,52 @@ typedef struct smx_basin {               /* 48 bytes; a caller passes sizeof(ITS
 int smx_drainage(smx_ctx* ctx, smx_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
                  uint32_t* receivers, uint32_t* labels, uint32_t* area);
 int smx_ensemble_drainage(smx_ensemble* e, smx_basin* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
+/* ---- streams: the channel network on top of the drainage -- Strahler order, Shreve magnitude, reach, one record per segment ----
+ * Cells, h(c), wet cells, lakes, receivers, sinks, basins and area are those of smx_drainage; threshold is a u32 >= 1. A CHANNEL cell
+ * is a dry cell with area(c) >= threshold; area strictly grows downstream, so the receiver of a channel cell is a channel cell or a
+ * wet cell, and threshold 1 makes every dry cell a channel cell. The channel DONORS of c are the channel cells whose receiver is c
+ * (0 to 8). A HEAD is a channel cell with no channel donor, a CONFLUENCE one with two or more. order(c) is the Strahler order: 1 at
+ * a head; else, with m the largest order among the channel donors, m where exactly one donor has it and m + 1 where two or more do.
+ * heads(c) is the Shreve magnitude: 1 at a head, else the u32 sum of the donors' heads. reach(c) is the number of cells on the
+ * longest channel path from a head down to and including c: 1 at a head, else 1 + the largest reach among the donors. All three are
+ * 0 off the channels. A SEGMENT starts at a head or at a confluence -- its IDENTITY first_cell -- and runs downstream through channel
+ * cells that have exactly one channel donor; its last_cell is the cell whose receiver is a confluence (the segment ends above it) or
+ * a wet cell (the segment enters a lake), or which is a sink. The segments partition the channel cells, order and heads are constant
+ * along one, segments are listed in ascending first_cell, and segment k of that order has RANK k. Every figure is a comparison, an
+ * integer or a copied double: a host restatement reproduces each bit, whatever the launch shape and the order of arrival. */
+typedef struct smx_segment {              /* 64 bytes; a caller passes sizeof(ITS struct) and gets that prefix of each record */
+  uint32_t first_cell, last_cell;        /* the two end cells (the same cell for a one-cell segment) */
+  uint32_t cells;                        /* cells of the segment */
+  uint32_t order;                        /* the Strahler order */
+  uint32_t down;                         /* first_cell of the segment it joins (the confluence below last_cell), else 0xFFFFFFFF */
+  uint32_t basin;                        /* first_cell of the basin it lies in: join with smx_drainage / smx_lakes */
+  uint32_t flags;                        /* 1: last_cell drains into a wet cell  2: last_cell is a sink  4: first_cell is a head (else a
+                                            confluence)  8: last_cell lies on the map border */
+  uint32_t heads;                        /* the Shreve magnitude */
+  uint32_t straight, diagonal;           /* receiver steps from first_cell to last_cell PLUS the step that leaves last_cell (where it has
+                                            a receiver), split by whether both x and y change: length = straight + diagonal * sqrt(2),
+                                            the caller's arithmetic */
+  uint32_t area_first, area_last;        /* area at the two end cells */
+  double   height_first, height_last;    /* h of the two end cells, bits as stored */
+} smx_segment;
+/* *nstreams = the number of segments, whatever cap is; the first min(cap, *nstreams) records are written in rank order, record k at
+ * byte k * struct_size; out may be NULL when cap is 0 (counting only). The planes (NULL = skip) hold dimx*dimy words in cell order:
+ * order, reach and heads as defined above; segments -- the rank of the cell's segment, 0xFFFFFFFF off the channels. In the ensemble
+ * call member i's records start at out + i * cap_per_member records and nstreams holds one count per member; an empty ensemble: 0,
+ * nothing written. Both calls run on the context's / the ensemble's stream (they see every tick queued before them), launch the same
+ * kernels whatever the map holds and however many members there are (one table upload; the drainage chain with the area on the
+ * call's own scratch -- k_lake_tiles, k_lake_merge, k_lake_flatten, k_drain_recv, k_drain_resolve, k_drain_pending, k_drain_area --,
+ * then k_stream_mark, k_stream_order, a prefix sum, k_stream_segments; the RESULTS copied back), synchronise once and change no map,
+ * flag, counter or generator; the results and the scratch of smx_drainage and smx_lakes are not touched. No kernel waits for
+ * another lane: k_stream_order takes at most as many turns per lane as the longest channel path has cells, k_stream_segments as
+ * many as the segment has. A strip context, a null argument, struct_size == 0, threshold == 0 and records asked for with out == NULL
+ * return -2, a context without a device -3. The scratch -- ten u32 planes per cell and the records asked for -- is allocated at
+ * first use and kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a
+ * side and 2^32 - 2 cells per call. */
+int smx_streams(smx_ctx* ctx, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap, uint32_t* nstreams,
+                uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads);
+int smx_ensemble_streams(smx_ensemble* e, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap_per_member,
+                         uint32_t* nstreams);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

@@ -102,6 +102,17 @@ class Basin(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class Stream(C.Structure):
+    """smx_segment: one segment of smx_streams / smx_ensemble_streams (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("last_cell", C.c_uint32), ("cells", C.c_uint32), ("order", C.c_uint32),
+                ("down", C.c_uint32), ("basin", C.c_uint32), ("flags", C.c_uint32), ("heads", C.c_uint32),
+                ("straight", C.c_uint32), ("diagonal", C.c_uint32), ("area_first", C.c_uint32), ("area_last", C.c_uint32),
+                ("height_first", C.c_double), ("height_last", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -122,6 +133,8 @@ LAKE_DRY = 0xFFFFFFFF                  # a dry cell of the label plane
 LAKE_BORDER, LAKE_VOLUME_UNRELIABLE = 1, 2                             # smx_lake.flags
 DRAIN_NONE = 0xFFFFFFFF                # the receiver plane: a sink or a wet cell
 BASIN_LAKE, BASIN_BORDER = 1, 2                                        # smx_basin.flags
+STREAM_NONE = 0xFFFFFFFF               # smx_segment.down: the segment joins no other; the segments plane: no channel cell
+STREAM_WET, STREAM_SINK, STREAM_HEAD, STREAM_BORDER = 1, 2, 4, 8       # smx_segment.flags
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
@@ -143,6 +156,7 @@ SYMBOLS = [
     "smx_ensemble_tick", "smx_ensemble_sync", "smx_ensemble_get_timing", "smx_ensemble_timing_reset",
     "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
     "smx_lakes", "smx_ensemble_lakes", "smx_drainage", "smx_ensemble_drainage",
+    "smx_streams", "smx_ensemble_streams",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -271,6 +285,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_lakes.argtypes = [vp, vp, u64, u32, vp]
     L.smx_drainage.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
     L.smx_ensemble_drainage.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_streams.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp]
+    L.smx_ensemble_streams.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -48,6 +48,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_fork.h"
 #include "soil_lakes.h"
 #include "soil_drain.h"
+#include "soil_streams.h"
 #include "soil_strata.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
@@ -447,6 +448,35 @@ __global__ void __launch_bounds__(LAKE_LANES) k_drain_area(const LakeMember* __r
   ObsGroup g;
   drain_area_group(m, g, blockIdx.x, R, P, AR);
 }
+
+// ---------------- the stream network (smx_streams / smx_ensemble_streams; bodies: soil_streams.h) ----------------
+// One lane per cell, the census's workgroup width. k_stream_order and k_stream_segments are lane-serial walks: a wavefront is busy as
+// long as its longest walk.
+struct StreamPlanes {   // the u32 planes of one call (soil_streams.h)
+  uint32_t *T, *R, *P, *AR, *D, *O, *H, *RE, *B, *SG;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_stream_mark(const LakeMember* __restrict__ tab, uint32_t threshold, StreamPlanes p) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  stream_mark_group(m, g, blockIdx.x, threshold, p.R, p.AR, p.D, p.P, p.O, p.H, p.RE, p.SG);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_stream_order(const LakeMember* __restrict__ tab, uint32_t threshold, StreamPlanes p) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  stream_order_group(m, g, blockIdx.x, threshold, p.R, p.AR, p.D, p.P, p.O, p.H, p.RE);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_stream_segments(const LakeMember* __restrict__ tab, int with_plane, StreamPlanes p, StreamRec* out, uint32_t* nstreams) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  stream_segments_group(m, g, blockIdx.x, with_plane != 0, p.T, p.R, p.AR, p.D, p.O, p.H, p.B, p.SG, out, nstreams + blockIdx.y);
+}
+struct StreamMarkFn {   // the scan's input: 1 where plane word g starts a segment
+  const uint32_t* D;
+  __host__ __device__ uint32_t operator()(uint32_t g) const { return stream_mark(D, g); }
+};
 
 // ---------------- reading the strata (smx_soil_totals / smx_soil_thickness / smx_cores; bodies: soil_strata.h) ----------------
 // One lane per column, pointer chasing: a workgroup is ONE wavefront (a deep column holds up nothing else) and strides over the map.
@@ -1833,6 +1863,16 @@ struct DrainScratch {
   char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
 };
 
+// smx_streams / smx_ensemble_streams: ten u32 planes (the drainage chain's T, R, P and AR and the six of soil_streams.h), rocPRIM's
+// temporary storage, the member table with its pinned source and the results with their pinned landing place. Its own, apart from
+// the drainage's and the census's: allocated by the first call, grown on demand, kept with the context or the ensemble.
+struct StreamScratch {
+  uint32_t* plane[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t words = 0;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
+  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
+};
+
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
 // lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
 // pinned source of the table and landing place of the small results (h_buf). Allocated at first use, grown on demand, kept.
@@ -1910,6 +1950,7 @@ struct smx_ctx : EventTimer {
   ForkScratch fork;                   // smx_copy_state into this context
   LakeScratch lakes;                  // smx_lakes
   DrainScratch drain;                 // smx_drainage
+  StreamScratch streams;              // smx_streams
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3481,6 +3522,7 @@ struct smx_ensemble : EventTimer {
   ForkScratch fork;                       // smx_ensemble_fork
   LakeScratch lakes;                      // smx_ensemble_lakes
   DrainScratch drain;                     // smx_ensemble_drainage
+  StreamScratch streams;                  // smx_ensemble_streams
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4189,6 +4231,142 @@ int smx_ensemble_drainage(smx_ensemble* e, smx_basin* out, uint64_t struct_size,
   roctx_range rr("soilmx:ensemble_drainage");
   HIPCHK(e, hipSetDevice(e->device));
   return drain_run("smx_ensemble_drainage", e->drain, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, e->err);
+}
+
+// ---------------- the stream network (smx_streams / smx_ensemble_streams; kernels: soil_streams.h, soil_drain.h and the census's) ----------------
+// One path for both calls, shaped as drain_run, on a scratch of its own: one table upload; k_lake_tiles, k_lake_merge, k_lake_flatten,
+// k_drain_recv, k_drain_resolve, k_drain_pending and k_drain_area (the table's cap is 0 for them: they touch no record; the basins'
+// scan and statistics are not needed, T stays the terminal plane); k_stream_mark, k_stream_order, rocPRIM's exclusive scan of the
+// start marks, k_stream_segments; the counts, the records and the planes asked for copied back, one synchronisation -- whatever the
+// maps hold and however many there are. smx_drainage's scratch and results are not touched.
+static_assert(sizeof(smx_segment) == 64 && sizeof(StreamRec) == sizeof(smx_segment) && offsetof(smx_segment, down) == offsetof(StreamRec, down) &&
+              offsetof(smx_segment, straight) == offsetof(StreamRec, straight) && offsetof(smx_segment, height_first) == offsetof(StreamRec, height_first), "smx_segment layout");
+static void streams_drop(StreamScratch& k, DevMem& mem) {
+  for (uint32_t*& q : k.plane) mem.drop(q);
+  mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
+  k = StreamScratch();
+}
+static int streams_run(const char* who, StreamScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, uint32_t threshold, smx_segment* out,
+                       uint64_t struct_size, uint32_t cap, uint32_t* nstreams, uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads, std::string& err) {
+  std::vector<LakeMember> tab(nm);
+  uint64_t words = 0, nrec = 0;
+  size_t tiles = 1, flat = 1;
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = ms[i];
+    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
+    LakeMember& m = tab[i];
+    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
+    m.cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)c->ncells);   // (threshold 1 on a plateau: every cell is a segment)
+    words += (uint64_t)c->ncells; nrec += m.cap;
+    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one call"; return -2; }
+    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
+    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
+  }
+  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(StreamRec);
+  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), StreamMarkFn{k.plane[4]});
+  size_t tb = 0;
+  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.plane[8], 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
+  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
+    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
+    if (ok && words > k.words) {
+      for (uint32_t*& q : k.plane) mem.drop(q);
+      k.words = 0;
+      for (uint32_t*& q : k.plane) ok = ok && mem.dev(q, (size_t)words) == hipSuccess;
+      if (ok) k.words = (size_t)words;
+    }
+    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
+    if (ok && nm > k.tab_cap) {
+      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
+      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess;
+      if (ok) k.tab_cap = nm;
+    }
+    if (ok && res_bytes > k.res_cap) {
+      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
+      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
+      if (ok) k.res_cap = res_bytes;
+    }
+    if (!ok) {
+      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
+      streams_drop(k, mem);
+      err = std::string(who) + ": out of memory for the stream scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
+      return -1;
+    }
+  }
+  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
+  // two tables: the members with their record caps for k_stream_segments, and, behind them, the same members with cap 0 for the
+  // census's and the drainage's kernels (they write the identities of THEIR records for ranks below cap: none here)
+  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
+  for (uint32_t i = 0; i < nm; i++) { k.h_tab[nm + i] = tab[i]; k.h_tab[nm + i].cap = 0u; }
+  const LakeMember* bare = k.d_tab + nm;
+  const StreamPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.plane[4], k.plane[5], k.plane[6], k.plane[7], k.plane[8], k.plane[9]};
+  StreamRec* recs = reinterpret_cast<StreamRec*>(k.d_res + rec_at);
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), wg(LAKE_LANES);
+  ok = hipMemcpyAsync(k.d_tab, k.h_tab, 2 * (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, bare, p.T, (LakeAcc*)nullptr);
+    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, bare, p.T);
+    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, bare, p.T);
+    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, bare, p.T, p.R, (BasinAcc*)nullptr);
+    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, bare, p.T);
+    hipLaunchKernelGGL(k_drain_pending, gf, wg, 0, st, bare, p.R, p.P, p.AR);
+    hipLaunchKernelGGL(k_drain_area, gf, wg, 0, st, bare, p.R, p.P, p.AR);
+    hipLaunchKernelGGL(k_stream_mark, gf, wg, 0, st, bare, threshold, p);
+    hipLaunchKernelGGL(k_stream_order, gf, wg, 0, st, bare, threshold, p);
+    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), StreamMarkFn{p.D});
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, in, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_stream_segments, gf, wg, 0, st, k.d_tab, segments ? 1 : 0, p, recs, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+  // (smx_streams only: one map, off = 0, so a plane index is a cell index)
+  if (ok && order) ok = hipMemcpyAsync(order, p.O, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && segments) ok = hipMemcpyAsync(segments, p.SG, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && reach) ok = hipMemcpyAsync(reach, p.RE, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && heads) ok = hipMemcpyAsync(heads, p.H, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  const hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the stream network failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
+  const char* a = k.h_res + rec_at;
+  const size_t take = struct_size < sizeof(smx_segment) ? (size_t)struct_size : sizeof(smx_segment);
+  for (uint32_t i = 0; i < nm; i++) {
+    nstreams[i] = n[i];
+    const uint32_t w = std::min(n[i], tab[i].cap);
+    for (uint32_t r = 0; r < w; r++)
+      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, a + ((size_t)tab[i].rec0 + r) * sizeof(StreamRec), take);
+  }
+  return 0;
+}
+
+int smx_streams(smx_ctx* ctx, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap, uint32_t* nstreams, uint32_t* order, uint32_t* segments,
+                uint32_t* reach, uint32_t* heads) {
+  if (!ctx) return -2;
+  FULLMAP("smx_streams")
+  if (struct_size == 0) { ctx->err = "smx_streams: struct_size is 0 (pass sizeof(smx_segment) of the header you compiled against)"; return -2; }
+  if (threshold == 0) { ctx->err = "smx_streams: threshold is 0 (a channel cell has an area of at least threshold >= 1)"; return -2; }
+  if (!nstreams) { ctx->err = "smx_streams: nstreams is null"; return -2; }
+  if (!out && cap) { ctx->err = "smx_streams: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_streams: a context without a device"; return -3; }
+  roctx_range rr("soilmx:streams");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return streams_run("smx_streams", ctx->streams, ctx->mem, ctx->stream, &ctx, 1u, threshold, out, struct_size, cap, nstreams, order, segments, reach, heads, ctx->err);
+}
+int smx_ensemble_streams(smx_ensemble* e, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nstreams) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_streams: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_streams: struct_size is 0 (pass sizeof(smx_segment) of the header you compiled against)"; return -2; }
+  if (threshold == 0) { e->err = "smx_ensemble_streams: threshold is 0 (a channel cell has an area of at least threshold >= 1)"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!nstreams) { e->err = "smx_ensemble_streams: nstreams is null (one count per member)"; return -2; }
+  if (!out && cap_per_member) { e->err = "smx_ensemble_streams: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  roctx_range rr("soilmx:ensemble_streams");
+  HIPCHK(e, hipSetDevice(e->device));
+  return streams_run("smx_ensemble_streams", e->streams, e->mem, e->stream, e->members.data(), nm, threshold, out, struct_size, cap_per_member, nstreams, nullptr, nullptr,
+                     nullptr, nullptr, e->err);
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------

@@ -278,6 +278,24 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
         return [int(c) for c in counts]
 
+    def streams(self, threshold: int, cap: int | None = None) -> list:
+        """The channel segments of every member (``smx_ensemble_streams``: the same launches whatever the member count): one list of
+        segment dicts per member, in member order, each as ``Layermap.streams(threshold)`` gives it. ``cap`` None: two calls, a count
+        with no records and the fetch sized by the largest count; else at most ``cap`` segments per member. Members may differ in size."""
+        self._check_members()
+        n = len(self.members)
+        if n == 0:
+            return []
+        threshold = int(threshold)
+        counts = np.zeros(n, np.uint32)
+        if cap is None:
+            self._chk(self.L.smx_ensemble_streams(self.h, threshold, None, C.sizeof(capi.Stream), 0, capi.ptr(counts)))
+            cap = int(counts.max())
+        cap = int(cap)
+        out = (capi.Stream * max(1, n * cap))()
+        self._chk(self.L.smx_ensemble_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, capi.ptr(counts)))
+        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
     def soil_totals(self, ntypes: int, other: bool = False) -> list:
         """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
         one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,

@@ -230,6 +230,30 @@ class Layermap:
         recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
         return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
 
+    def streams(self, threshold: int, order: bool = False, segments: bool = False, reach: bool = False, heads: bool = False, cap: int | None = None):
+        """The channel network (``smx_streams``): one dict per segment in rank order (ascending ``first_cell``) -- ``first_cell``,
+        ``last_cell``, ``cells``, ``order`` (Strahler), ``down`` (``first_cell`` of the segment it joins, 0xFFFFFFFF where it ends
+        in a lake or at a sink), ``basin`` (join on it with ``drainage()`` / ``lakes()``), ``flags`` (1: enters a lake, 2: ends at
+        a sink, 4: starts at a head, 8: ``last_cell`` on the map border), ``heads`` (Shreve magnitude), ``straight`` / ``diagonal``
+        (length = straight + diagonal * sqrt(2)), ``area_first`` / ``area_last``, ``height_first`` / ``height_last``. A channel cell
+        is a dry cell with a contributing area of at least ``threshold`` (>= 1); a segment runs from a head or a confluence down to
+        the next confluence, a lake or a sink. With a plane asked for the result is ``(records, planes)``, ``planes`` a dict of
+        (dimx, dimy) uint32 arrays: ``order``, ``reach`` (cells on the longest channel path down to the cell) and ``heads`` (0 off
+        the channels) and ``segments`` (the segment's rank, 0xFFFFFFFF off the channels). ``cap`` None: two calls, a count and the
+        fetch; else at most ``cap`` segments. Sees every tick queued before it and changes nothing."""
+        n = C.c_uint32()
+        threshold = int(threshold)
+        if cap is None:
+            self._chk(self.L.smx_streams(self.h, threshold, None, C.sizeof(capi.Stream), 0, C.byref(n), None, None, None, None))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (capi.Stream * max(1, cap))()
+        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, want in (("order", order), ("segments", segments), ("reach", reach), ("heads", heads)) if want}
+        self._chk(self.L.smx_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, C.byref(n), capi.ptr(planes.get("order")), capi.ptr(planes.get("segments")),
+                                     capi.ptr(planes.get("reach")), capi.ptr(planes.get("heads"))))
+        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
+        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+
     # -- the strata read on the device --
     def soil_totals(self, ntypes: int | None = None, other: bool = False):
         """How much of each soil the map holds (``smx_soil_totals``): one dict per type 0..ntypes-1 -- ``sections`` (top sections
