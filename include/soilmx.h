@@ -376,6 +376,57 @@ int smx_streams(smx_ctx* ctx, uint32_t threshold, smx_segment* out, uint64_t str
                 uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads);
 int smx_ensemble_streams(smx_ensemble* e, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap_per_member,
                          uint32_t* nstreams);
+/* ---- spill analysis: where a lake or a pit overflows, into which basin, how much more it holds, how high water must rise before
+ *      it leaves the map -- pour points, fill levels, storage and the filled surface ----
+ * Cells, h(c), wet cells, lakes, basins, their identity first_cell and their rank are those of smx_drainage. Heights are ORDERED by
+ * their ordered image K(v): the bits of v with the sign bit set where v is positive, all bits inverted where it is negative -- a total
+ * order on bit patterns in which -0 is below +0 and a positive NaN above +inf. "max" and "min" of heights below mean "by K", and the
+ * height of a pass is a copied double, never computed.
+ * A PASS of basin a is a pair (c, n) with c in a and n an in-map cell among c's eight neighbours that lies in another basin; its height
+ * is w = max(h(c), h(n)). Every cell c of a on the map border also has the off-map pass (c, 0xFFFFFFFF) with w = h(c): water leaves
+ * the map there. Every basin has at least one pass. The POUR POINT of a basin is its pass with the smallest (K(w), c, n), compared
+ * lexicographically -- so at an equal height and the same c an in-map neighbour beats the off-map pass.
+ * The FILL LEVEL L(a) = min over the passes (c, n) of a of max(w, L(basin(n))), and w itself for an off-map pass: the minimax height
+ * over basin-to-basin routes to the edge of the map. The value is unique, so any order of evaluation gives the same bits. A lake
+ * counts as one pool: moving inside it costs nothing. filled(c) = max(h(c), L(basin(c))): where the map has no wet cell this is
+ * exactly the priority-flood surface (the minimax over 8-connected cell paths to off-map), with wet cells it is never above it.
+ * storage_q40 is the sum, over the basin's cells with K(h(c)) < K(pour_height), of floor((pour_height - h(c)) * 2^40) as u64 -- an
+ * exact integer, as smx_lake.volume_q40 --, cells_below counts those cells, fill_storage_q40 is the same sum against fill_height. A
+ * difference that is not finite, is negative or is >= 2^24 contributes 0 and sets the "unreliable" flag; a wrapped sum sets it too.
+ * Every figure is a comparison, an exact integer or a copied double: a host restatement reproduces each bit. */
+typedef struct smx_spill_record {        /* 64 bytes; record k belongs to basin k of smx_drainage on the same state */
+  uint32_t first_cell;                   /* the basin's identity */
+  uint32_t pour_cell, pour_to;           /* c and n of the pour point; pour_to 0xFFFFFFFF: off the map */
+  uint32_t to_basin;                     /* first_cell of basin(pour_to), 0xFFFFFFFF off the map */
+  uint32_t flags;                        /* 1 lake terminal  2 pours off the map  4 K(fill_height) > K(pour_height) (nested in a larger
+                                            depression)  8 storage_q40 unreliable  16 fill_storage_q40 unreliable */
+  uint32_t cells_below;
+  double   pour_height, fill_height;
+  uint64_t storage_q40, fill_storage_q40;
+  uint32_t reserved[2];                  /* written as 0 */
+} smx_spill_record;
+/* *nbasins = the number of basins, whatever cap is; the first min(cap, *nbasins) records are written in rank order, record k at byte
+ * k * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each record); out may be NULL when cap is 0 (counting
+ * only). filled (NULL = skip): dimx*dimy doubles in cell order. In the ensemble call member i's records start at out + i *
+ * cap_per_member records and nbasins holds one count per member; an empty ensemble: 0, nothing written. Both calls run on the
+ * context's / the ensemble's stream (they see every tick queued before them) and change no map, flag, counter or generator; the
+ * scratch and the results of smx_lakes, smx_drainage and smx_streams are not touched. The launches, each one for all members: the
+ * drainage chain through k_drain_stats on the call's own scratch; k_spill_init, k_spill_pass twice (the key (K(w), c, n) is wider
+ * than 64 bits: first the lowest K(w) per basin, then the lowest (c, n) among the passes that attain it), a prefix sum of the
+ * boundary marks, k_spill_list, k_spill_point; k_spill_relax, ONE SWEEP per launch, each boundary cell lowering its basin's level in
+ * place with fetch_min(max(w, L[basin(n)])); k_spill_store. No kernel waits for another lane or workgroup. THE NUMBER OF SWEEPS
+ * DEPENDS ON THE MAP, so this call, unlike its siblings, SYNCHRONISES MORE THAN ONCE: once behind the drainage chain (the basins'
+ * table is sized by the counts), then once per batch of 8 sweeps -- the host reads the sweeps' change counts and stops after the
+ * batch that holds the first sweep that changed nothing --, once at the end. After more sweeps than the largest member has basins,
+ * plus 2, the call gives up with -1 (that cannot happen). smx_get_spill_sweeps gives the sweeps launched and the batches of the
+ * context's / the ensemble's last call. A strip context, a null argument, struct_size == 0 and records asked for with out == NULL
+ * return -2, a context without a device -3. The scratch -- four u32 planes and one f64 plane per cell and 64 bytes per basin -- is
+ * allocated at first use and kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable. Maps of up to
+ * 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_spill(smx_ctx* ctx, smx_spill_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, double* filled);
+int smx_ensemble_spill(smx_ensemble* e, smx_spill_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
+int smx_get_spill_sweeps(smx_ctx* ctx, uint32_t* sweeps, uint32_t* batches);
+int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* batches);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

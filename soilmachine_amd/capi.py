@@ -113,6 +113,19 @@ class Stream(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Spill(C.Structure):
+    """smx_spill_record: one basin's record of smx_spill / smx_ensemble_spill (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("pour_cell", C.c_uint32), ("pour_to", C.c_uint32), ("to_basin", C.c_uint32),
+                ("flags", C.c_uint32), ("cells_below", C.c_uint32), ("pour_height", C.c_double), ("fill_height", C.c_double),
+                ("storage_q40", C.c_uint64), ("fill_storage_q40", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        d["storage"] = int(self.storage_q40) * 2.0 ** -40      # below the exact sum of the differences by less than cells_below * 2^-40
+        d["fill_storage"] = int(self.fill_storage_q40) * 2.0 ** -40
+        return d
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -136,6 +149,9 @@ BASIN_LAKE, BASIN_BORDER = 1, 2                                        # smx_bas
 STREAM_NONE = 0xFFFFFFFF               # smx_segment.down: the segment joins no other; the segments plane: no channel cell
 STREAM_WET, STREAM_SINK, STREAM_HEAD, STREAM_BORDER = 1, 2, 4, 8       # smx_segment.flags
 
+SPILL_NONE = 0xFFFFFFFF                # smx_spill_record.pour_to / to_basin: off the map
+SPILL_LAKE, SPILL_OFFMAP, SPILL_NESTED, SPILL_STORAGE_UNRELIABLE, SPILL_FILL_STORAGE_UNRELIABLE = 1, 2, 4, 8, 16   # smx_spill_record.flags
+
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
 
@@ -157,6 +173,7 @@ SYMBOLS = [
     "smx_ensemble_figures", "smx_ensemble_plane_stats", "smx_copy_state", "smx_ensemble_fork",
     "smx_lakes", "smx_ensemble_lakes", "smx_drainage", "smx_ensemble_drainage",
     "smx_streams", "smx_ensemble_streams",
+    "smx_spill", "smx_ensemble_spill", "smx_get_spill_sweeps", "smx_ensemble_get_spill_sweeps",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -287,6 +304,10 @@ def load() -> C.CDLL:
     L.smx_ensemble_drainage.argtypes = [vp, vp, u64, u32, vp]
     L.smx_streams.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp]
     L.smx_ensemble_streams.argtypes = [vp, u32, vp, u64, u32, vp]
+    L.smx_spill.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp]
+    L.smx_ensemble_spill.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_get_spill_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.smx_ensemble_get_spill_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -48,6 +48,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_fork.h"
 #include "soil_lakes.h"
 #include "soil_drain.h"
+#include "soil_spill.h"
 #include "soil_streams.h"
 #include "soil_strata.h"
 #include <algorithm>
@@ -477,6 +478,57 @@ struct StreamMarkFn {   // the scan's input: 1 where plane word g starts a segme
   const uint32_t* D;
   __host__ __device__ uint32_t operator()(uint32_t g) const { return stream_mark(D, g); }
 };
+
+// ---------------- spill analysis (smx_spill / smx_ensemble_spill; bodies: soil_spill.h) ----------------
+// The census's tiles and lanes. k_spill_pass holds the height and rank tiles with their halo of one (18 x 66 doubles and words, 14 KB
+// of LDS) and a table with a slot per cell of the tile (12 KB); k_spill_store's table holds 512 cells' worth of basins (14 KB).
+// k_spill_relax strides over a member's boundary cells with at most SPILL_RELAX_BLOCKS workgroups: the list's length is read on the device.
+constexpr int SPILL_PS = LAKE_TX * LAKE_TY;
+constexpr unsigned SPILL_RELAX_BLOCKS = 2048;
+struct SpillPlanes {   // the planes of one call (soil_spill.h)
+  uint32_t *T, *B, *R, *Q;
+  double* H;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_init(const LakeMember* __restrict__ tab, SpillAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  spill_init_group(m, g, blockIdx.x, acc);
+}
+template <int PHASE>
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_pass(const LakeMember* __restrict__ tab, SpillPlanes p, SpillAcc* acc) {
+  __shared__ double hs[(LAKE_TX + 2) * (LAKE_TY + 2)];
+  __shared__ uint32_t ls[(LAKE_TX + 2) * (LAKE_TY + 2)];
+  __shared__ SpillPassTable<SPILL_PS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if (blockIdx.x >= lake_tiles(m, LAKE_TX, LAKE_TY)) return;
+  ObsGroup g;
+  spill_pass_group<LAKE_TX, LAKE_TY, SPILL_PS, PHASE>(m, g, blockIdx.x, hs, ls, t, p.T, p.B, p.R, p.H, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_list(const LakeMember* __restrict__ tab, SpillPlanes p) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  spill_list_group(m, g, blockIdx.x, p.B, p.R, p.Q);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_point(const LakeMember* __restrict__ tab, SpillPlanes p, SpillAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  spill_point_group(m, g, blockIdx.x, p.T, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_relax(const LakeMember* __restrict__ tab, uint32_t sweep, SpillPlanes p, SpillAcc* acc, uint32_t* changed) {
+  const LakeMember m = tab[blockIdx.y];
+  ObsGroup g;
+  spill_relax_group(m, g, blockIdx.x, gridDim.x, sweep, p.T, p.B, p.R, p.Q, p.H, acc, changed);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_spill_store(const LakeMember* __restrict__ tab, SpillPlanes p, SpillAcc* acc, int filled) {
+  __shared__ SpillStoreTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  spill_store_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.T, p.H, acc, filled != 0);
+}
 
 // ---------------- reading the strata (smx_soil_totals / smx_soil_thickness / smx_cores; bodies: soil_strata.h) ----------------
 // One lane per column, pointer chasing: a workgroup is ONE wavefront (a deep column holds up nothing else) and strides over the map.
@@ -1873,6 +1925,18 @@ struct StreamScratch {
   char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
 };
 
+// smx_spill / smx_ensemble_spill: the drainage chain's three u32 planes, the list plane Q and the f64 plane H (soil_spill.h),
+// rocPRIM's temporary storage, the member tables with their pinned source, the counts and the change counts with their pinned
+// landing place, and the basins' table with its own. Its own, apart from the drainage's, the streams' and the census's: allocated
+// at first use, grown on demand, kept with the context or the ensemble. sweeps / batches: of the last call.
+struct SpillScratch {
+  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; uint32_t* Q = nullptr; double* H = nullptr; size_t words = 0;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t* d_cnt = nullptr; uint32_t* h_cnt = nullptr; uint32_t tab_cap = 0;
+  SpillAcc* d_acc = nullptr; SpillAcc* h_acc = nullptr; size_t acc_cap = 0;
+  uint32_t sweeps = 0, batches = 0;
+};
+
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
 // lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
 // pinned source of the table and landing place of the small results (h_buf). Allocated at first use, grown on demand, kept.
@@ -1951,6 +2015,7 @@ struct smx_ctx : EventTimer {
   LakeScratch lakes;                  // smx_lakes
   DrainScratch drain;                 // smx_drainage
   StreamScratch streams;              // smx_streams
+  SpillScratch spill;                 // smx_spill
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3523,6 +3588,7 @@ struct smx_ensemble : EventTimer {
   LakeScratch lakes;                      // smx_ensemble_lakes
   DrainScratch drain;                     // smx_ensemble_drainage
   StreamScratch streams;                  // smx_ensemble_streams
+  SpillScratch spill;                     // smx_ensemble_spill
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4367,6 +4433,191 @@ int smx_ensemble_streams(smx_ensemble* e, uint32_t threshold, smx_segment* out, 
   HIPCHK(e, hipSetDevice(e->device));
   return streams_run("smx_ensemble_streams", e->streams, e->mem, e->stream, e->members.data(), nm, threshold, out, struct_size, cap_per_member, nstreams, nullptr, nullptr,
                      nullptr, nullptr, e->err);
+}
+
+// ---------------- spill analysis (smx_spill / smx_ensemble_spill; kernels: soil_spill.h, soil_drain.h and the census's) ----------------
+// One path for both calls, on a scratch of its own. The drainage chain through k_drain_stats with no records (the tables' cap is 0:
+// T becomes the rank plane), the counts back: the FIRST synchronisation -- the basins' table is sized by them. Then k_spill_init,
+// k_spill_pass<0>, k_spill_pass<1>, rocPRIM's exclusive scan of the boundary marks, k_spill_list, k_spill_point; k_spill_relax in
+// batches of SPILL_BATCH sweeps, the change counts read once per batch (one synchronisation each) until a sweep changed nothing;
+// k_spill_store; the table and the plane back, the last synchronisation. smx_drainage's, smx_streams' and smx_lakes' scratch and
+// results are not touched.
+static_assert(sizeof(smx_spill_record) == 64 && sizeof(SpillRec) == sizeof(smx_spill_record) && offsetof(smx_spill_record, pour_height) == offsetof(SpillRec, pour_height) &&
+              offsetof(smx_spill_record, storage_q40) == offsetof(SpillRec, storage_q40) && offsetof(smx_spill_record, flags) == offsetof(SpillRec, flags), "smx_spill_record layout");
+static void spill_drop(SpillScratch& k, DevMem& mem) {
+  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.Q); mem.drop(k.H); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt);
+  mem.drop(k.d_acc); mem.drop(k.h_acc);
+  k = SpillScratch();
+}
+static int spill_run(const char* who, SpillScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_spill_record* out, uint64_t struct_size,
+                     uint32_t cap, uint32_t* nbasins, double* filled, std::string& err) {
+  std::vector<LakeMember> tab(nm);
+  uint64_t words = 0;
+  size_t tiles = 1, flat = 1, stat = 1;
+  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
+  k.sweeps = 0; k.batches = 0;
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = ms[i];
+    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
+    LakeMember& m = tab[i];
+    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;   // (the drainage chain touches no record)
+    words += (uint64_t)c->ncells;
+    if (words > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells in one call"; return -2; }
+    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
+    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
+    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
+  }
+  const size_t cnt_words = (((size_t)nm + 15) & ~(size_t)15) + 16;   // the counts, then SPILL_BATCH change counts
+  static_assert(SPILL_BATCH <= 16, "the change counts' room");
+  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
+  size_t tb = 0, tb2 = 0;
+  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess &&
+            rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)k.R, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  tb = std::max<size_t>(std::max(tb, tb2), 8);   // (a null temporary storage would make the scan a size query again)
+  auto oom = [&](uint64_t nrec) {
+    (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
+    spill_drop(k, mem);
+    err = std::string(who) + ": out of memory for the spill scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " basins)";
+    return -1;
+  };
+  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap)) {
+    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
+    if (ok && words > k.words) {
+      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.Q); mem.drop(k.H); k.words = 0;
+      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess &&
+           mem.dev(k.Q, (size_t)words) == hipSuccess && mem.dev(k.H, (size_t)words) == hipSuccess;
+      if (ok) k.words = (size_t)words;
+    }
+    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
+    if (ok && nm > k.tab_cap) {
+      mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt); k.tab_cap = 0;
+      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess && mem.dev(k.d_cnt, cnt_words) == hipSuccess &&
+           mem.pinned(k.h_cnt, cnt_words) == hipSuccess;
+      if (ok) k.tab_cap = nm;
+    }
+    if (!ok) return oom(0);
+  }
+  if (!ok) { err = std::string(who) + ": sizing the prefix sums failed"; return -1; }
+  const SpillPlanes p{k.T, k.B, k.R, k.Q, k.H};
+  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), gs((unsigned)stat, nm), wg(LAKE_LANES);
+  uint32_t* d_n = k.d_cnt;
+  uint32_t* d_chg = k.d_cnt + (cnt_words - 16);
+  const uint32_t* h_chg = k.h_cnt + (cnt_words - 16);
+  // the bare table (no records) for the drainage chain; behind it, once the counts are known, the table with the basins
+  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
+  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, k.d_tab, p.T, (LakeAcc*)nullptr);
+    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, k.d_tab, p.T);
+    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, k.d_tab, p.T);
+    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, k.d_tab, p.T, p.R, (BasinAcc*)nullptr);
+    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, k.d_tab, p.T);
+    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{p.T});
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, in, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_drain_stats, gs, wg, 0, st, k.d_tab, p.T, p.B, (BasinAcc*)nullptr, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = ok && hipMemcpyAsync(k.h_cnt, d_n, (size_t)nm * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the drainage chain failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  uint64_t nrec = 0;
+  uint32_t most = 0;
+  for (uint32_t i = 0; i < nm; i++) {
+    tab[i].cap = k.h_cnt[i]; tab[i].rec0 = (uint32_t)nrec;
+    nrec += tab[i].cap; most = std::max(most, tab[i].cap);
+  }
+  if (nrec > k.acc_cap) {   // (the stream is idle)
+    mem.drop(k.d_acc); mem.drop(k.h_acc); k.acc_cap = 0;
+    if (mem.dev(k.d_acc, (size_t)nrec) != hipSuccess || mem.pinned(k.h_acc, (size_t)nrec) != hipSuccess) return oom(nrec);
+    k.acc_cap = (size_t)nrec;
+  }
+  const LakeMember* full = k.d_tab + nm;
+  const dim3 gb((unsigned)(((size_t)most + LAKE_LANES - 1) / LAKE_LANES), nm), gr((unsigned)std::min<size_t>(flat, SPILL_RELAX_BLOCKS), nm);
+  memcpy(k.h_tab + nm, tab.data(), (size_t)nm * sizeof(LakeMember));
+  ok = hipMemcpyAsync(k.d_tab + nm, k.h_tab + nm, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_spill_init, gb, wg, 0, st, full, k.d_acc);
+    hipLaunchKernelGGL(k_spill_pass<0>, gt, wg, 0, st, full, p, k.d_acc);
+    hipLaunchKernelGGL(k_spill_pass<1>, gt, wg, 0, st, full, p, k.d_acc);
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, (const uint32_t*)p.R, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_spill_list, gf, wg, 0, st, full, p);
+    hipLaunchKernelGGL(k_spill_point, gb, wg, 0, st, full, p, k.d_acc);
+  }
+  // the sweeps: their number depends on the map, so this is where the call looks at the device more than once
+  for (bool done = false; ok && !done;) {
+    if ((uint64_t)k.sweeps >= (uint64_t)most + 2u) {   // (each sweep but the last settles a basin at least: cannot happen)
+      (void)hipStreamSynchronize(st);
+      err = std::string(who) + ": the fill levels did not settle within " + std::to_string(k.sweeps) + " sweeps (" + std::to_string(most) + " basins)";
+      return -1;
+    }
+    ok = hipMemsetAsync(d_chg, 0, 16 * 4, st) == hipSuccess;
+    for (uint32_t j = 0; ok && j < SPILL_BATCH; j++) hipLaunchKernelGGL(k_spill_relax, gr, wg, 0, st, full, k.sweeps + j + 1u, p, k.d_acc, d_chg + j);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(k.h_cnt + (cnt_words - 16), d_chg, 16 * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    se = hipStreamSynchronize(st);
+    if (!ok || se != hipSuccess) break;
+    k.sweeps += SPILL_BATCH; k.batches++;
+    for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || h_chg[j] == 0u;
+  }
+  if (ok && se == hipSuccess) {
+    hipLaunchKernelGGL(k_spill_store, gs, wg, 0, st, full, p, k.d_acc, filled ? 1 : 0);
+    ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(k.h_acc, k.d_acc, (size_t)nrec * sizeof(SpillAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
+    // (smx_spill only: one map, off = 0)
+    if (ok && filled) ok = hipMemcpyAsync(filled, p.H, (size_t)words * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+    se = hipStreamSynchronize(st);
+  }
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the spill analysis failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const size_t take = struct_size < sizeof(smx_spill_record) ? (size_t)struct_size : sizeof(smx_spill_record);
+  for (uint32_t i = 0; i < nm; i++) {
+    nbasins[i] = tab[i].cap;
+    const uint32_t w = std::min(tab[i].cap, cap);
+    for (uint32_t r = 0; r < w; r++) {
+      SpillRec rec;
+      spill_finish(k.h_acc[tab[i].rec0 + r], rec);
+      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
+    }
+  }
+  return 0;
+}
+
+int smx_spill(smx_ctx* ctx, smx_spill_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, double* filled) {
+  if (!ctx) return -2;
+  FULLMAP("smx_spill")
+  if (struct_size == 0) { ctx->err = "smx_spill: struct_size is 0 (pass sizeof(smx_spill_record) of the header you compiled against)"; return -2; }
+  if (!nbasins) { ctx->err = "smx_spill: nbasins is null"; return -2; }
+  if (!out && cap) { ctx->err = "smx_spill: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_spill: a context without a device"; return -3; }
+  roctx_range rr("soilmx:spill");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return spill_run("smx_spill", ctx->spill, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, filled, ctx->err);
+}
+int smx_ensemble_spill(smx_ensemble* e, smx_spill_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_spill: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_spill: struct_size is 0 (pass sizeof(smx_spill_record) of the header you compiled against)"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!nbasins) { e->err = "smx_ensemble_spill: nbasins is null (one count per member)"; return -2; }
+  if (!out && cap_per_member) { e->err = "smx_ensemble_spill: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  roctx_range rr("soilmx:ensemble_spill");
+  HIPCHK(e, hipSetDevice(e->device));
+  return spill_run("smx_ensemble_spill", e->spill, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, e->err);
+}
+int smx_get_spill_sweeps(smx_ctx* ctx, uint32_t* sweeps, uint32_t* batches) {
+  if (!ctx) return -2;
+  if (!sweeps || !batches) { ctx->err = "smx_get_spill_sweeps: a null argument"; return -2; }
+  *sweeps = ctx->spill.sweeps; *batches = ctx->spill.batches;
+  return 0;
+}
+int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* batches) {
+  if (!e) return -2;
+  if (!sweeps || !batches) { e->err = "smx_ensemble_get_spill_sweeps: a null argument"; return -2; }
+  *sweeps = e->spill.sweeps; *batches = e->spill.batches;
+  return 0;
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------

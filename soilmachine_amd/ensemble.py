@@ -296,6 +296,29 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, capi.ptr(counts)))
         return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
 
+    def spill(self, cap: int | None = None) -> list:
+        """The spill records of every member (``smx_ensemble_spill``: the same launches whatever the member count): one list of
+        dicts per member, in member order, each as ``Layermap.spill()`` gives it. ``cap`` None: two calls, the basin counts and the
+        fetch sized by the largest; else at most ``cap`` basins per member. Members may differ in size."""
+        self._check_members()
+        n = len(self.members)
+        if n == 0:
+            return []
+        counts = np.zeros(n, np.uint32)
+        if cap is None:
+            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
+            cap = int(counts.max())
+        cap = int(cap)
+        out = (capi.Spill * max(1, n * cap))()
+        self._chk(self.L.smx_ensemble_spill(self.h, out, C.sizeof(capi.Spill), cap, capi.ptr(counts)))
+        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
+    def spill_sweeps(self) -> tuple:
+        """(sweeps launched, batches) of the last ``spill()`` (``smx_ensemble_get_spill_sweeps``)."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_ensemble_get_spill_sweeps(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def soil_totals(self, ntypes: int, other: bool = False) -> list:
         """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
         one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,

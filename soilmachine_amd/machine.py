@@ -254,6 +254,34 @@ class Layermap:
         recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
         return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
 
+    def spill(self, filled: bool = False, cap: int | None = None):
+        """Where the basins overflow (``smx_spill``): one dict per basin in rank order, record k for basin k of ``drainage()`` --
+        ``first_cell``, ``pour_cell`` / ``pour_to`` (the pour point: the basin's lowest pass, a cell of the basin and its neighbour in
+        another basin, 0xFFFFFFFF: off the map), ``to_basin`` (``first_cell`` of the basin it pours into, 0xFFFFFFFF off the map),
+        ``flags`` (1: the terminal is a lake, 2: pours off the map, 4: nested in a larger depression -- the fill level is above the
+        pour height --, 8 / 16: ``storage_q40`` / ``fill_storage_q40`` unreliable), ``cells_below``, ``pour_height``, ``fill_height``
+        (how high water must rise before it leaves the map), ``storage_q40`` / ``fill_storage_q40`` (the exact integer sums of
+        floor((level - h) * 2^40) over the basin's cells below the pour height / the fill level) and ``storage`` / ``fill_storage``
+        (those as floats). ``filled``: the result is ``(records, plane)``, the (dimx, dimy) float64 plane max(h, fill level of the
+        cell's basin). ``cap`` None: two calls, a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it
+        and changes nothing; the number of relax sweeps depends on the map (``spill_sweeps()``)."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (capi.Spill * max(1, cap))()
+        plane = np.zeros(self.dimx * self.dimy, np.float64) if filled else None
+        self._chk(self.L.smx_spill(self.h, out, C.sizeof(capi.Spill), cap, C.byref(n), capi.ptr(plane)))
+        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
+        return (recs, plane.reshape(self.dimx, self.dimy)) if filled else recs
+
+    def spill_sweeps(self) -> tuple:
+        """(sweeps launched, batches) of the last ``spill()`` (``smx_get_spill_sweeps``)."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_get_spill_sweeps(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     # -- the strata read on the device --
     def soil_totals(self, ntypes: int | None = None, other: bool = False):
         """How much of each soil the map holds (``smx_soil_totals``): one dict per type 0..ntypes-1 -- ``sections`` (top sections

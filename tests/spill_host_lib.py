@@ -1,0 +1,96 @@
+"""ctypes wrapper of tests/spill_host (soil_spill.h compiled for the host -- TEST INFRASTRUCTURE ONLY)."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import drainage_host_lib as DH
+from soilmachine_amd import capi
+from soilmachine_amd.snapshot import Snapshot
+
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "spill_host")
+ROOT = os.path.dirname(os.path.dirname(HERE))
+LIB = os.path.join(HERE, "libspill_host.so")
+SRC = [os.path.join(HERE, "spill_host.cpp"), os.path.join(DH.HERE, "drainage_host.cpp")] + \
+      [os.path.join(ROOT, "soilmachine_amd", "csrc", f) for f in ("soil_core.h", "soil_lakes.h", "soil_drain.h", "soil_spill.h")]
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB) or any(os.path.getmtime(p) > os.path.getmtime(LIB) for p in SRC):
+            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", LIB, SRC[0]])
+        L = C.CDLL(LIB)
+        vp = C.c_void_p
+        L.dh_create.restype = vp
+        L.dh_create.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
+        L.dh_destroy.argtypes = [vp]; L.dh_destroy.restype = None
+        L.sh_variant.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4
+        L.sh_batch.restype = C.c_uint32
+        L.sh_spill.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib = L
+    return _lib
+
+
+def variants() -> dict:
+    """variant -> (tile columns, tile rows, slots of the pass table, slots of the store table)"""
+    L = lib()
+    out = {}
+    for v in range(L.sh_variants()):
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        assert L.sh_variant(v, C.byref(a), C.byref(b), C.byref(c), C.byref(d)) == 0
+        out[v] = (a.value, b.value, c.value, d.value)
+    return out
+
+
+def batch() -> int:
+    """G: the sweeps of one batch (SPILL_BATCH)."""
+    return int(lib().sh_batch())
+
+
+class HostMap:
+    """The top records of one snapshot's columns on the host (held by this library's copy of drainage_host)."""
+
+    def __init__(self, s: Snapshot):
+        self.L = lib()
+        self.dimx, self.dimy = int(s.dimx), int(s.dimy)
+        arr = [np.ascontiguousarray(a, dt) for a, dt in ((s.count, np.uint32), (s.type, np.uint32), (s.size, np.float64), (s.floor, np.float64))]
+        self.h = self.L.dh_create(self.dimx, self.dimy, *[capi.ptr(a) for a in arr])
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.dh_destroy(self.h); self.h = None
+
+
+def spill_many(maps, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True):
+    """The kernels' bodies over `maps` in one go (the ensemble path) -> ([(records, filled plane or None, nbasins) per map], (sweeps,
+    batches)); cap None: two calls, a count and the fetch. order: bit 0 the workgroups, bit 1 the lanes, last to first."""
+    L = lib()
+    n = len(maps)
+    hs = (C.c_void_p * n)(*[m.h for m in maps])
+    nb = np.zeros(n, np.uint32)
+    sw, ba = C.c_uint32(), C.c_uint32()
+    if cap is None:
+        assert L.sh_spill(hs, n, variant, lanes, order, 0, None, C.sizeof(capi.Spill), capi.ptr(nb), None, C.byref(sw), C.byref(ba)) == 0
+        cap = int(nb.max()) if n else 0
+    out = (capi.Spill * max(1, n * cap))()
+    words = sum(m.dimx * m.dimy for m in maps)
+    plane = np.zeros(words, np.float64) if filled else None
+    assert L.sh_spill(hs, n, variant, lanes, order, cap, out, C.sizeof(capi.Spill), capi.ptr(nb), capi.ptr(plane), C.byref(sw), C.byref(ba)) == 0
+    res, at = [], 0
+    for i, m in enumerate(maps):
+        k = min(cap, int(nb[i]))
+        cells = m.dimx * m.dimy
+        res.append(([out[i * cap + r].as_dict() for r in range(k)], plane[at:at + cells].reshape(m.dimx, m.dimy).copy() if filled else None, int(nb[i])))
+        at += cells
+    return res, (int(sw.value), int(ba.value))
+
+
+def spill(s: Snapshot, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True):
+    """((records, filled plane, nbasins), (sweeps, batches)) of one snapshot."""
+    res, sweeps = spill_many([HostMap(s)], variant, lanes, order, cap, filled)
+    return res[0], sweeps
