@@ -427,6 +427,62 @@ int smx_spill(smx_ctx* ctx, smx_spill_record* out, uint64_t struct_size, uint32_
 int smx_ensemble_spill(smx_ensemble* e, smx_spill_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
 int smx_get_spill_sweeps(smx_ctx* ctx, uint32_t* sweeps, uint32_t* batches);
 int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* batches);
+/* ---- through-drainage: when the pits and lakes are full, where does the water of a cell leave the map, and how much land drains
+ *      through a point -- one cycle-free outflow per basin, the forest of basins, catchments and the through area ----
+ * Cells, h(c), K, wet cells, basins, first_cell, the rank, the passes (c, n), w and the fill level L(a) are those of smx_drainage and
+ * smx_spill. Following smx_spill_record.to_basin from basin to basin does NOT lead to the edge of the map: two basins that share their
+ * lowest pass pour into each other. So:
+ * A pass (c, n) of basin a is TIGHT when K(max(w, L(basin(n)))) == K(L(a)); the off-map pass is tight when K(w) == K(L(a)). Every
+ * basin has one: the first pass of a minimax route is tight.
+ * hops(a) = 1 if a has a tight off-map pass, otherwise 1 + the smallest hops(basin(n)) over its tight in-map passes. It is finite for
+ * every basin: a tight step never raises (L, length of the shortest optimal route), and it lowers one of the two.
+ * The EXIT of a is the tight pass with the smallest (c, n) among those whose target has hops(a) - 1; the off-map side counts as 0, so a
+ * basin with hops == 1 exits off the map even where a tight in-map pass has a smaller (c, n). down(a) = basin(exit_to), or none. hops
+ * strictly falls along down: the basins form a forest whose roots all exit off the map. The exit may differ from smx_spill's pour
+ * point; flag 4 says so.
+ * through_cells(a) = cells(a) + the sum of through_cells(u) over down(u) == a; upstream_basins(a) is the number of basins strictly
+ * above a in the forest; outlet(a) is the root below a (a itself for a root), outlet_cell that root's exit_cell.
+ * through_area(c) = 1 + the sum of through_area over the donors of c (the cells whose receiver is c) + the sum of through_cells(b)
+ * over the basins b whose exit_to == c. Inside a basin the paths are smx_drainage's own; the filled part is a pool, so a basin's
+ * total arrives at its terminal and re-appears at the entry cell of the next basin, a wet entry cell included. For every basin the
+ * through_area over its sink or its wet cells sums to its through_cells; over the roots through_cells sums to dimx*dimy.
+ * outlets(c) is the RANK of outlet(basin(c)). Every figure is a comparison, an exact u32 / u64 integer or a copied double. */
+typedef struct smx_through_record {      /* 64 bytes; record k belongs to basin k of smx_drainage on the same state */
+  uint32_t first_cell;                   /* the basin's identity */
+  uint32_t exit_cell, exit_to;           /* c and n of the exit; exit_to 0xFFFFFFFF: off the map */
+  uint32_t down;                         /* first_cell of basin(exit_to), 0xFFFFFFFF off the map */
+  uint32_t outlet, outlet_cell;          /* first_cell of the root below the basin, and that root's exit_cell */
+  uint32_t hops;                         /* exits on the way off the map, this basin's included: 1 for a root */
+  uint32_t flags;                        /* 1 lake terminal  2 exits off the map  4 exit is not smx_spill's pour point  8 exit_to is a
+                                            wet cell */
+  uint32_t cells, through_cells, upstream_basins;
+  uint32_t reserved;                     /* written as 0 */
+  double   exit_height;                  /* w of the exit, copied */
+  double   fill_height;                  /* L, as smx_spill_record.fill_height */
+} smx_through_record;
+/* *nbasins, out, struct_size, cap and the ensemble call's layout are smx_spill's. through_area, outlets (NULL = skip): dimx*dimy u32 in
+ * cell order. Both calls run on the context's / the ensemble's stream (they see every tick queued before them) and change no map,
+ * flag, counter or generator; the scratch and the results of smx_lakes, smx_drainage, smx_streams and smx_spill are not touched. The
+ * launches, each one for all members: the drainage chain through k_drain_stats on the call's own scratch; smx_spill's k_spill_init,
+ * k_spill_pass twice, the prefix sum, k_spill_list, k_spill_point and the k_spill_relax sweeps in batches of 8 (their boundary marks
+ * in a plane of their own: the receivers stay); k_through_count (cells per basin); k_through_hops, ONE SWEEP per launch over the
+ * boundary cells, fetch_min(hops[a], hops[basin(n)] + 1) per tight pass in place, in batches of 8 as the level sweeps; k_through_exit
+ * (atomic min of (c << 32 | n) per basin); k_through_link twice (down, heights, flags, the pending counts; then the leaf marks);
+ * k_through_accumulate, the never-waiting walk of k_drain_area over the basins, which also adds every finished basin's through_cells
+ * to the area word of its exit_to; k_through_outlet; and where the planes are asked for k_drain_pending, k_through_plane and
+ * k_through_area -- k_drain_area's walk, except that a leaf cell starts from its own word: an entry cell may have no donor. No
+ * kernel waits for another lane or workgroup. The call SYNCHRONISES once behind the drainage chain, once per batch of level sweeps
+ * and of hop sweeps, once at the end; after more sweeps of either kind than the largest member has basins, plus 2, it gives up with
+ * -1 (that cannot happen). smx_get_through_sweeps gives the level sweeps, the hop sweeps and the batches (of both kinds together) of
+ * the context's / the ensemble's last call. A strip context, a null argument, struct_size == 0 and records asked for with out ==
+ * NULL return -2, a context without a device -3; an empty ensemble 0. The scratch -- five u32 planes and one f64 plane per cell
+ * and 128 bytes per basin -- is allocated at first use and kept; an allocation that fails returns < 0 and leaves the context / the
+ * ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_through(smx_ctx* ctx, smx_through_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* through_area,
+                uint32_t* outlets);
+int smx_ensemble_through(smx_ensemble* e, smx_through_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
+int smx_get_through_sweeps(smx_ctx* ctx, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches);
+int smx_ensemble_get_through_sweeps(smx_ensemble* e, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

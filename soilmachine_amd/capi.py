@@ -126,6 +126,17 @@ class Spill(C.Structure):
         return d
 
 
+class Through(C.Structure):
+    """smx_through_record: one basin's record of smx_through / smx_ensemble_through (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("exit_cell", C.c_uint32), ("exit_to", C.c_uint32), ("down", C.c_uint32),
+                ("outlet", C.c_uint32), ("outlet_cell", C.c_uint32), ("hops", C.c_uint32), ("flags", C.c_uint32),
+                ("cells", C.c_uint32), ("through_cells", C.c_uint32), ("upstream_basins", C.c_uint32), ("reserved", C.c_uint32),
+                ("exit_height", C.c_double), ("fill_height", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -152,6 +163,9 @@ STREAM_WET, STREAM_SINK, STREAM_HEAD, STREAM_BORDER = 1, 2, 4, 8       # smx_seg
 SPILL_NONE = 0xFFFFFFFF                # smx_spill_record.pour_to / to_basin: off the map
 SPILL_LAKE, SPILL_OFFMAP, SPILL_NESTED, SPILL_STORAGE_UNRELIABLE, SPILL_FILL_STORAGE_UNRELIABLE = 1, 2, 4, 8, 16   # smx_spill_record.flags
 
+THROUGH_NONE = 0xFFFFFFFF              # smx_through_record.exit_to / down: off the map
+THROUGH_LAKE, THROUGH_OFFMAP, THROUGH_NOT_POUR, THROUGH_WET_ENTRY = 1, 2, 4, 8   # smx_through_record.flags
+
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
 
@@ -174,6 +188,7 @@ SYMBOLS = [
     "smx_lakes", "smx_ensemble_lakes", "smx_drainage", "smx_ensemble_drainage",
     "smx_streams", "smx_ensemble_streams",
     "smx_spill", "smx_ensemble_spill", "smx_get_spill_sweeps", "smx_ensemble_get_spill_sweeps",
+    "smx_through", "smx_ensemble_through", "smx_get_through_sweeps", "smx_ensemble_get_through_sweeps",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -308,6 +323,10 @@ def load() -> C.CDLL:
     L.smx_ensemble_spill.argtypes = [vp, vp, u64, u32, vp]
     L.smx_get_spill_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.smx_ensemble_get_spill_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.smx_through.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp]
+    L.smx_ensemble_through.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_get_through_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.smx_ensemble_get_through_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

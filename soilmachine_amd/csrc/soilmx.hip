@@ -49,6 +49,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_lakes.h"
 #include "soil_drain.h"
 #include "soil_spill.h"
+#include "soil_through.h"
 #include "soil_streams.h"
 #include "soil_strata.h"
 #include <algorithm>
@@ -528,6 +529,69 @@ __global__ void __launch_bounds__(LAKE_LANES) k_spill_store(const LakeMember* __
   if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   spill_store_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.T, p.H, acc, filled != 0);
+}
+
+// ---------------- through-drainage (smx_through / smx_ensemble_through; bodies: soil_through.h) ----------------
+// The spill chain's kernels run on the call's own planes (the boundary marks in a plane of their own: R stays the receivers); behind
+// them, per basin or per boundary cell, the kernels below. k_through_count's table holds 512 cells' worth of basins (4 KB of LDS);
+// k_through_hops and k_through_exit stride over the boundary cells as k_spill_relax does.
+struct ThroughPlanes {   // the planes of one call (soil_through.h): M the boundary marks
+  uint32_t *T, *B, *M, *Q;
+  double* H;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_through_init(const LakeMember* __restrict__ tab, ThroughAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  through_init_group(m, g, blockIdx.x, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_count(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ T, ThroughAcc* acc) {
+  __shared__ ThroughCountTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  through_count_group<LAKE_SLOTS>(m, g, blockIdx.x, t, T, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_hops(const LakeMember* __restrict__ tab, ThroughPlanes p, const SpillAcc* sacc, ThroughAcc* acc, uint32_t* changed) {
+  const LakeMember m = tab[blockIdx.y];
+  ObsGroup g;
+  through_hops_group(m, g, blockIdx.x, gridDim.x, p.T, p.B, p.M, p.Q, p.H, sacc, acc, changed);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_exit(const LakeMember* __restrict__ tab, ThroughPlanes p, const SpillAcc* sacc, ThroughAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  ObsGroup g;
+  through_exit_group(m, g, blockIdx.x, gridDim.x, p.T, p.B, p.M, p.Q, p.H, sacc, acc);
+}
+template <int PHASE>
+__global__ void __launch_bounds__(LAKE_LANES) k_through_link(const LakeMember* __restrict__ tab, ThroughPlanes p, const SpillAcc* sacc, ThroughAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  through_link_group<PHASE>(m, g, blockIdx.x, p.T, p.H, sacc, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_accumulate(const LakeMember* __restrict__ tab, ThroughAcc* acc, uint32_t* AR) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  through_accumulate_group(m, g, blockIdx.x, acc, AR);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_outlet(const LakeMember* __restrict__ tab, const SpillAcc* sacc, ThroughAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= m.cap) return;
+  ObsGroup g;
+  through_outlet_group(m, g, blockIdx.x, sacc, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_plane(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ T, const ThroughAcc* acc, uint32_t* O) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  through_plane_group(m, g, blockIdx.x, T, acc, O);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_through_area(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ R, uint32_t* P, uint32_t* AR) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  through_area_group(m, g, blockIdx.x, R, P, AR);
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_soil_thickness / smx_cores; bodies: soil_strata.h) ----------------
@@ -1937,6 +2001,18 @@ struct SpillScratch {
   uint32_t sweeps = 0, batches = 0;
 };
 
+// smx_through / smx_ensemble_through: the spill scratch's planes and one more -- T, B, R (the receivers), M (the boundary marks, later
+// the pending words), Q (the boundary list, later the area), the f64 plane H --, rocPRIM's temporary storage, the member tables, the
+// counts and the change counts, and the two basins' tables with their pinned landing places. Its own: allocated at first use, grown
+// on demand, kept with the context or the ensemble. level_sweeps / hop_sweeps / batches: of the last call.
+struct ThroughScratch {
+  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; uint32_t* M = nullptr; uint32_t* Q = nullptr; double* H = nullptr; size_t words = 0;
+  void* temp = nullptr; size_t temp_bytes = 0;
+  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t* d_cnt = nullptr; uint32_t* h_cnt = nullptr; uint32_t tab_cap = 0;
+  SpillAcc* d_sacc = nullptr; SpillAcc* h_sacc = nullptr; ThroughAcc* d_acc = nullptr; ThroughAcc* h_acc = nullptr; size_t acc_cap = 0;
+  uint32_t level_sweeps = 0, hop_sweeps = 0, batches = 0;
+};
+
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
 // lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
 // pinned source of the table and landing place of the small results (h_buf). Allocated at first use, grown on demand, kept.
@@ -2016,6 +2092,7 @@ struct smx_ctx : EventTimer {
   DrainScratch drain;                 // smx_drainage
   StreamScratch streams;              // smx_streams
   SpillScratch spill;                 // smx_spill
+  ThroughScratch through;             // smx_through
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3589,6 +3666,7 @@ struct smx_ensemble : EventTimer {
   DrainScratch drain;                     // smx_ensemble_drainage
   StreamScratch streams;                  // smx_ensemble_streams
   SpillScratch spill;                     // smx_ensemble_spill
+  ThroughScratch through;                 // smx_ensemble_through
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4617,6 +4695,212 @@ int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* b
   if (!e) return -2;
   if (!sweeps || !batches) { e->err = "smx_ensemble_get_spill_sweeps: a null argument"; return -2; }
   *sweeps = e->spill.sweeps; *batches = e->spill.batches;
+  return 0;
+}
+
+// ---------------- through-drainage (smx_through / smx_ensemble_through; kernels: soil_through.h, soil_spill.h, soil_drain.h and the census's) ----------------
+// One path for both calls, shaped as spill_run, on a scratch of its own. The drainage chain through k_drain_stats with no records,
+// the counts back: the FIRST synchronisation. Then k_spill_init, k_through_init, k_spill_pass<0>, k_spill_pass<1> (their boundary
+// marks go to M: R stays the receivers), the scan, k_spill_list, k_spill_point, k_through_count; k_spill_relax in batches until a
+// sweep changed nothing, k_through_hops likewise (one synchronisation per batch); k_through_exit; k_drain_pending where the area is
+// asked for (P takes M's plane and AR takes Q's: the marks and the list are done with); k_through_link<0>, <1>,
+// k_through_accumulate, k_through_outlet, k_through_plane and k_through_area where their planes are asked for; the tables and the
+// planes back, the last synchronisation. The scratch and the results of the sibling calls are not touched.
+static_assert(sizeof(smx_through_record) == 64 && sizeof(ThroughRec) == sizeof(smx_through_record) && offsetof(smx_through_record, exit_height) == offsetof(ThroughRec, exit_height) &&
+              offsetof(smx_through_record, hops) == offsetof(ThroughRec, hops) && offsetof(smx_through_record, through_cells) == offsetof(ThroughRec, through_cells), "smx_through_record layout");
+static void through_drop(ThroughScratch& k, DevMem& mem) {
+  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.M); mem.drop(k.Q); mem.drop(k.H); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt);
+  mem.drop(k.h_cnt); mem.drop(k.d_sacc); mem.drop(k.h_sacc); mem.drop(k.d_acc); mem.drop(k.h_acc);
+  k = ThroughScratch();
+}
+static int through_run(const char* who, ThroughScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_through_record* out, uint64_t struct_size,
+                       uint32_t cap, uint32_t* nbasins, uint32_t* through_area, uint32_t* outlets, std::string& err) {
+  std::vector<LakeMember> tab(nm);
+  uint64_t words = 0;
+  size_t tiles = 1, flat = 1, stat = 1;
+  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
+  k.level_sweeps = 0; k.hop_sweeps = 0; k.batches = 0;
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* c = ms[i];
+    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
+    LakeMember& m = tab[i];
+    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;   // (the drainage chain touches no record)
+    words += (uint64_t)c->ncells;
+    if (words > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells in one call"; return -2; }
+    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
+    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
+    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
+  }
+  const size_t cnt_words = (((size_t)nm + 15) & ~(size_t)15) + 16;   // the counts, then SPILL_BATCH change counts
+  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
+  size_t tb = 0, tb2 = 0;
+  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess &&
+            rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)k.M, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+  tb = std::max<size_t>(std::max(tb, tb2), 8);   // (a null temporary storage would make the scan a size query again)
+  auto oom = [&](uint64_t nrec) {
+    (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
+    through_drop(k, mem);
+    err = std::string(who) + ": out of memory for the through-drainage scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " basins)";
+    return -1;
+  };
+  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap)) {
+    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
+    if (ok && words > k.words) {
+      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.M); mem.drop(k.Q); mem.drop(k.H); k.words = 0;
+      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess &&
+           mem.dev(k.M, (size_t)words) == hipSuccess && mem.dev(k.Q, (size_t)words) == hipSuccess && mem.dev(k.H, (size_t)words) == hipSuccess;
+      if (ok) k.words = (size_t)words;
+    }
+    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
+    if (ok && nm > k.tab_cap) {
+      mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt); k.tab_cap = 0;
+      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess && mem.dev(k.d_cnt, cnt_words) == hipSuccess &&
+           mem.pinned(k.h_cnt, cnt_words) == hipSuccess;
+      if (ok) k.tab_cap = nm;
+    }
+    if (!ok) return oom(0);
+  }
+  if (!ok) { err = std::string(who) + ": sizing the prefix sums failed"; return -1; }
+  const SpillPlanes sp{k.T, k.B, k.M, k.Q, k.H};     // what the spill chain's kernels see: their R is M
+  const ThroughPlanes p{k.T, k.B, k.M, k.Q, k.H};
+  uint32_t* const P = k.M;                           // behind k_through_exit
+  uint32_t* const AR = through_area ? k.Q : nullptr;
+  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), gs((unsigned)stat, nm), wg(LAKE_LANES);
+  uint32_t* d_n = k.d_cnt;
+  uint32_t* d_chg = k.d_cnt + (cnt_words - 16);
+  const uint32_t* h_chg = k.h_cnt + (cnt_words - 16);
+  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
+  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, k.d_tab, k.T, (LakeAcc*)nullptr);
+    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, k.d_tab, k.T);
+    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, k.d_tab, k.T);
+    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, k.d_tab, k.T, k.R, (BasinAcc*)nullptr);
+    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, k.d_tab, k.T);
+    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_drain_stats, gs, wg, 0, st, k.d_tab, k.T, k.B, (BasinAcc*)nullptr, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = ok && hipMemcpyAsync(k.h_cnt, d_n, (size_t)nm * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  hipError_t se = hipStreamSynchronize(st);
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the drainage chain failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  uint64_t nrec = 0;
+  uint32_t most = 0;
+  for (uint32_t i = 0; i < nm; i++) {
+    tab[i].cap = k.h_cnt[i]; tab[i].rec0 = (uint32_t)nrec;
+    nrec += tab[i].cap; most = std::max(most, tab[i].cap);
+  }
+  if (nrec > k.acc_cap) {   // (the stream is idle)
+    mem.drop(k.d_sacc); mem.drop(k.h_sacc); mem.drop(k.d_acc); mem.drop(k.h_acc); k.acc_cap = 0;
+    if (mem.dev(k.d_sacc, (size_t)nrec) != hipSuccess || mem.pinned(k.h_sacc, (size_t)nrec) != hipSuccess || mem.dev(k.d_acc, (size_t)nrec) != hipSuccess ||
+        mem.pinned(k.h_acc, (size_t)nrec) != hipSuccess)
+      return oom(nrec);
+    k.acc_cap = (size_t)nrec;
+  }
+  const LakeMember* full = k.d_tab + nm;
+  const dim3 gb((unsigned)(((size_t)most + LAKE_LANES - 1) / LAKE_LANES), nm), gr((unsigned)std::min<size_t>(flat, SPILL_RELAX_BLOCKS), nm);
+  memcpy(k.h_tab + nm, tab.data(), (size_t)nm * sizeof(LakeMember));
+  ok = hipMemcpyAsync(k.d_tab + nm, k.h_tab + nm, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_spill_init, gb, wg, 0, st, full, k.d_sacc);
+    hipLaunchKernelGGL(k_through_init, gb, wg, 0, st, full, k.d_acc);
+    hipLaunchKernelGGL(k_spill_pass<0>, gt, wg, 0, st, full, sp, k.d_sacc);
+    hipLaunchKernelGGL(k_spill_pass<1>, gt, wg, 0, st, full, sp, k.d_sacc);
+    size_t need = k.temp_bytes;
+    ok = rocprim::exclusive_scan(k.temp, need, (const uint32_t*)k.M, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+    hipLaunchKernelGGL(k_spill_list, gf, wg, 0, st, full, sp);
+    hipLaunchKernelGGL(k_spill_point, gb, wg, 0, st, full, sp, k.d_sacc);
+    hipLaunchKernelGGL(k_through_count, gs, wg, 0, st, full, k.T, k.d_acc);
+  }
+  // the sweeps, the fill levels first and the hop counts behind them: the host loop of spill_run, twice
+  for (int what = 0; what < 2 && ok && se == hipSuccess; what++) {
+    uint32_t& sweeps = what ? k.hop_sweeps : k.level_sweeps;
+    for (bool done = false; ok && !done;) {
+      if ((uint64_t)sweeps >= (uint64_t)most + 2u) {   // (each sweep but the last settles a basin at least: cannot happen)
+        (void)hipStreamSynchronize(st);
+        err = std::string(who) + ": the " + (what ? "hop counts" : "fill levels") + " did not settle within " + std::to_string(sweeps) + " sweeps (" + std::to_string(most) + " basins)";
+        return -1;
+      }
+      ok = hipMemsetAsync(d_chg, 0, 16 * 4, st) == hipSuccess;
+      for (uint32_t j = 0; ok && j < SPILL_BATCH; j++) {
+        if (what) hipLaunchKernelGGL(k_through_hops, gr, wg, 0, st, full, p, k.d_sacc, k.d_acc, d_chg + j);
+        else hipLaunchKernelGGL(k_spill_relax, gr, wg, 0, st, full, sweeps + j + 1u, sp, k.d_sacc, d_chg + j);
+      }
+      ok = ok && hipGetLastError() == hipSuccess;
+      ok = ok && hipMemcpyAsync(k.h_cnt + (cnt_words - 16), d_chg, 16 * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+      se = hipStreamSynchronize(st);
+      if (!ok || se != hipSuccess) break;
+      sweeps += SPILL_BATCH; k.batches++;
+      for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || h_chg[j] == 0u;
+    }
+  }
+  if (ok && se == hipSuccess) {
+    hipLaunchKernelGGL(k_through_exit, gr, wg, 0, st, full, p, k.d_sacc, k.d_acc);
+    if (AR) hipLaunchKernelGGL(k_drain_pending, gf, wg, 0, st, full, k.R, P, AR);
+    hipLaunchKernelGGL(k_through_link<0>, gb, wg, 0, st, full, p, k.d_sacc, k.d_acc);
+    hipLaunchKernelGGL(k_through_link<1>, gb, wg, 0, st, full, p, k.d_sacc, k.d_acc);
+    hipLaunchKernelGGL(k_through_accumulate, gb, wg, 0, st, full, k.d_acc, AR);
+    hipLaunchKernelGGL(k_through_outlet, gb, wg, 0, st, full, k.d_sacc, k.d_acc);
+    if (outlets) hipLaunchKernelGGL(k_through_plane, gf, wg, 0, st, full, k.T, k.d_acc, k.B);   // (B is done with)
+    if (AR) hipLaunchKernelGGL(k_through_area, gf, wg, 0, st, full, k.R, P, AR);
+    ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(k.h_sacc, k.d_sacc, (size_t)nrec * sizeof(SpillAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(k.h_acc, k.d_acc, (size_t)nrec * sizeof(ThroughAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
+    // (smx_through only: one map, off = 0)
+    if (ok && through_area) ok = hipMemcpyAsync(through_area, AR, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (ok && outlets) ok = hipMemcpyAsync(outlets, k.B, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    se = hipStreamSynchronize(st);
+  }
+  if (!ok || se != hipSuccess) { err = std::string(who) + ": the through-drainage failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
+  const size_t take = struct_size < sizeof(smx_through_record) ? (size_t)struct_size : sizeof(smx_through_record);
+  for (uint32_t i = 0; i < nm; i++) {
+    nbasins[i] = tab[i].cap;
+    const uint32_t w = std::min(tab[i].cap, cap);
+    for (uint32_t r = 0; r < w; r++) {
+      ThroughRec rec;
+      through_finish(k.h_sacc[tab[i].rec0 + r], k.h_acc[tab[i].rec0 + r], rec);
+      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
+    }
+  }
+  return 0;
+}
+
+int smx_through(smx_ctx* ctx, smx_through_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* through_area, uint32_t* outlets) {
+  if (!ctx) return -2;
+  FULLMAP("smx_through")
+  if (struct_size == 0) { ctx->err = "smx_through: struct_size is 0 (pass sizeof(smx_through_record) of the header you compiled against)"; return -2; }
+  if (!nbasins) { ctx->err = "smx_through: nbasins is null"; return -2; }
+  if (!out && cap) { ctx->err = "smx_through: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
+  if (!ctx->stream) { ctx->err = "smx_through: a context without a device"; return -3; }
+  roctx_range rr("soilmx:through");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return through_run("smx_through", ctx->through, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, through_area, outlets, ctx->err);
+}
+int smx_ensemble_through(smx_ensemble* e, smx_through_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
+  if (!e) return -2;
+  if (!e->stream) { e->err = "smx_ensemble_through: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
+  if (struct_size == 0) { e->err = "smx_ensemble_through: struct_size is 0 (pass sizeof(smx_through_record) of the header you compiled against)"; return -2; }
+  const uint32_t nm = (uint32_t)e->members.size();
+  if (nm == 0) return 0;
+  if (!nbasins) { e->err = "smx_ensemble_through: nbasins is null (one count per member)"; return -2; }
+  if (!out && cap_per_member) { e->err = "smx_ensemble_through: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  roctx_range rr("soilmx:ensemble_through");
+  HIPCHK(e, hipSetDevice(e->device));
+  return through_run("smx_ensemble_through", e->through, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, e->err);
+}
+int smx_get_through_sweeps(smx_ctx* ctx, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches) {
+  if (!ctx) return -2;
+  if (!level_sweeps || !hop_sweeps || !batches) { ctx->err = "smx_get_through_sweeps: a null argument"; return -2; }
+  *level_sweeps = ctx->through.level_sweeps; *hop_sweeps = ctx->through.hop_sweeps; *batches = ctx->through.batches;
+  return 0;
+}
+int smx_ensemble_get_through_sweeps(smx_ensemble* e, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches) {
+  if (!e) return -2;
+  if (!level_sweeps || !hop_sweeps || !batches) { e->err = "smx_ensemble_get_through_sweeps: a null argument"; return -2; }
+  *level_sweeps = e->through.level_sweeps; *hop_sweeps = e->through.hop_sweeps; *batches = e->through.batches;
   return 0;
 }
 

@@ -319,6 +319,29 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_get_spill_sweeps(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def through(self, cap: int | None = None) -> list:
+        """The through-drainage records of every member (``smx_ensemble_through``: the same launches whatever the member count): one
+        list of dicts per member, in member order, each as ``Layermap.through()`` gives it. ``cap`` None: two calls, the basin counts
+        and the fetch sized by the largest; else at most ``cap`` basins per member. Members may differ in size."""
+        self._check_members()
+        n = len(self.members)
+        if n == 0:
+            return []
+        counts = np.zeros(n, np.uint32)
+        if cap is None:
+            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
+            cap = int(counts.max())
+        cap = int(cap)
+        out = (capi.Through * max(1, n * cap))()
+        self._chk(self.L.smx_ensemble_through(self.h, out, C.sizeof(capi.Through), cap, capi.ptr(counts)))
+        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
+    def through_sweeps(self) -> tuple:
+        """(level sweeps, hop sweeps, batches) of the last ``through()`` (``smx_ensemble_get_through_sweeps``)."""
+        a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_ensemble_get_through_sweeps(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     def soil_totals(self, ntypes: int, other: bool = False) -> list:
         """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
         one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,

@@ -282,6 +282,35 @@ class Layermap:
         self._chk(self.L.smx_get_spill_sweeps(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def through(self, area: bool = False, outlets: bool = False, cap: int | None = None):
+        """Where the water goes once the pits and lakes are full (``smx_through``): one dict per basin in rank order, record k for basin
+        k of ``drainage()`` and ``spill()`` -- ``first_cell``, ``exit_cell`` / ``exit_to`` (the exit: the tight pass with the smallest
+        (c, n) among those that shorten the way off the map; 0xFFFFFFFF: off the map), ``down`` (``first_cell`` of the basin it exits
+        into, 0xFFFFFFFF off the map: the basins form a forest), ``outlet`` / ``outlet_cell`` (``first_cell`` of the root below the
+        basin and that root's exit cell), ``hops`` (exits on the way off the map, 1 for a root), ``flags`` (1: the terminal is a lake,
+        2: exits off the map, 4: the exit is not ``spill()``'s pour point, 8: ``exit_to`` is a wet cell), ``cells``, ``through_cells``
+        (the cells of the basin and of every basin above it), ``upstream_basins``, ``exit_height``, ``fill_height``. ``area`` /
+        ``outlets``: the result is ``(records, planes)``, the (dimx, dimy) uint32 planes ``through_area`` (the contributing area
+        routed through the overflows) and ``outlets`` (the rank of the root the cell's basin leaves through). ``cap`` None: two calls,
+        a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it and changes nothing; the number of
+        sweeps depends on the map (``through_sweeps()``)."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (capi.Through * max(1, cap))()
+        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, on in (("through_area", area), ("outlets", outlets)) if on}
+        self._chk(self.L.smx_through(self.h, out, C.sizeof(capi.Through), cap, C.byref(n), capi.ptr(planes.get("through_area")), capi.ptr(planes.get("outlets"))))
+        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
+        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+
+    def through_sweeps(self) -> tuple:
+        """(level sweeps, hop sweeps, batches) of the last ``through()`` (``smx_get_through_sweeps``)."""
+        a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_get_through_sweeps(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     # -- the strata read on the device --
     def soil_totals(self, ntypes: int | None = None, other: bool = False):
         """How much of each soil the map holds (``smx_soil_totals``): one dict per type 0..ntypes-1 -- ``sections`` (top sections

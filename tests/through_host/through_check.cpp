@@ -1,0 +1,134 @@
+// through_check -- a stand-alone run of the through-drainage bodies for the sanitizers:
+//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -o through_check through_check.cpp && ./through_check
+// Without arguments: random heights, random heights under a Bernoulli(0.2) wet mask, a plateau and a sawtooth at 33 x 47 and 96 x 80,
+// and three maps in one call: every tile shape, 64 and 256 lanes and the four launch orders must give the same records and the same
+// planes as the kernels' own shape in ascending order; hops strictly falls along down, the roots' through_cells sum to the map and
+// no through_area is 0.
+// With arguments: each names a dump written by tests/test_through_host.py -- an input of tests/through_ref.py with the restatement's
+// result: the columns' top records exactly as the snapshot holds them, then the count, the records and the two planes, all compared
+// bit by bit. Every tile shape, 64 and 256 lanes, workgroups and lanes first to last and last to first. Little-endian words:
+//   u32 magic 0x55524854, i32 dimx, i32 dimy, u32 nsec, u32 count[cells], u32 type[nsec], f64 size[nsec], f64 floor[nsec],
+//   u32 nbasins, 64-byte records[nbasins], u32 through_area[cells], u32 outlets[cells]
+// Exit status 0 = all equal.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+
+#include "through_host.cpp"
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
+
+static dh_map* make(const char* kind, int dx, int dy) {
+  const size_t n = (size_t)dx * dy;
+  std::vector<uint32_t> count(n), type;
+  std::vector<double> size, floor;
+  for (size_t c = 0; c < n; c++) {
+    double h = (double)(rnd() % 4096) * 0.0009765625;
+    if (!strcmp(kind, "plateau")) h = 1.0;
+    if (!strcmp(kind, "sawtooth")) h = (c % 2 ? 1.0 : 0.25) + (double)(c / dy) * 4.0;
+    const bool wet = !strcmp(kind, "lakes") && rnd() % 5 == 0;
+    count[c] = wet ? 2 : 1;
+    type.push_back(1); size.push_back(h); floor.push_back(0.0);
+    if (wet) { type.push_back(0); size.push_back(0.5); floor.push_back(h); }
+  }
+  return dh_create(dx, dy, count.data(), type.data(), size.data(), floor.data());
+}
+
+struct Result { std::vector<uint32_t> nb, area, outlets; std::vector<ThroughRec> recs; uint32_t sweeps[3] = {0, 0, 0}; };
+
+static bool run(const std::vector<dh_map*>& maps, int v, uint32_t lanes, int order, uint32_t cap, Result& r) {
+  size_t words = 0;
+  for (const dh_map* m : maps) words += m->cells.size();
+  r.nb.assign(maps.size(), 0); r.recs.assign(maps.size() * (size_t)cap + 1, ThroughRec()); r.area.assign(words, 0u); r.outlets.assign(words, 0u);
+  memset(r.recs.data(), 0, r.recs.size() * sizeof(ThroughRec));
+  return th_through(maps.data(), (uint32_t)maps.size(), v, lanes, order, cap, r.recs.data(), sizeof(ThroughRec), r.nb.data(), r.area.data(), r.outlets.data(), r.sweeps) == 0;
+}
+
+static int check(const char* name, const std::vector<dh_map*>& maps) {
+  uint32_t cap = 0;
+  for (const dh_map* m : maps) cap = std::max<uint32_t>(cap, (uint32_t)m->cells.size());
+  Result want;
+  int bad = run(maps, 0, 256, 0, cap, want) ? 0 : 1;
+  size_t at = 0;
+  for (size_t i = 0; i < maps.size() && !bad; i++) {
+    const dh_map* m = maps[i];
+    const ThroughRec* rec = want.recs.data() + i * (size_t)cap;
+    uint64_t roots = 0;
+    for (uint32_t k = 0; k < want.nb[i]; k++) {
+      const ThroughRec& s = rec[k];
+      if (s.first_cell >= m->cells.size() || s.exit_cell >= m->cells.size() || s.hops == 0u || s.hops > want.nb[i]) { bad++; continue; }
+      if (s.down == THROUGH_NONE) { roots += s.through_cells; if (s.hops != 1u || !(s.flags & THROUGH_F_OFFMAP)) bad++; continue; }
+      const ThroughRec* d = std::lower_bound(rec, rec + want.nb[i], s.down, [](const ThroughRec& a, uint32_t f) { return a.first_cell < f; });
+      if (d == rec + want.nb[i] || d->first_cell != s.down || d->hops + 1u != s.hops || lake_key(d->fill_height) > lake_key(s.fill_height)) bad++;
+    }
+    if (roots != m->cells.size()) bad++;
+    for (size_t c = 0; c < m->cells.size(); c++)
+      if (want.area[at + c] == 0u || want.outlets[at + c] >= want.nb[i]) bad++;
+    at += m->cells.size();
+  }
+  if (bad) printf("FAIL %s: the kernels' own shape\n", name);
+  for (int v = 0; v < th_variants(); v++)
+    for (uint32_t lanes : {64u, 256u})
+      for (int order = 0; order < 4; order++) {
+        Result got;
+        const bool same = run(maps, v, lanes, order, cap, got) && got.nb == want.nb &&
+                          memcmp(got.recs.data(), want.recs.data(), want.recs.size() * sizeof(ThroughRec)) == 0 && got.area == want.area && got.outlets == want.outlets;
+        if (!same) { printf("FAIL %s variant %d lanes %u order %d\n", name, v, lanes, order); bad++; }
+      }
+  printf("%-10s %zu map(s), %5u basins in the first, %3u + %3u sweeps  %s\n", name, maps.size(), want.nb.empty() ? 0u : want.nb[0], want.sweeps[0], want.sweeps[1],
+         bad ? "FAILED" : "ok");
+  return bad;
+}
+
+template <class T> static bool take(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
+
+static int check_dump(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { printf("FAIL cannot open %s\n", path); return 1; }
+  uint32_t head[4] = {0, 0, 0, 0}, nb = 0;
+  std::vector<uint32_t> count, type, area, outlets;
+  std::vector<double> size, floor;
+  std::vector<ThroughRec> recs;
+  bool ok = fread(head, 4, 4, f) == 4 && head[0] == 0x55524854u && (int32_t)head[1] > 0 && (int32_t)head[2] > 0 && head[1] <= 4096u && head[2] <= 4096u;
+  const size_t n = ok ? (size_t)head[1] * head[2] : 0;
+  ok = ok && take(f, count, n) && take(f, type, head[3]) && take(f, size, head[3]) && take(f, floor, head[3]);
+  uint64_t sum = 0;
+  for (uint32_t c : count) sum += c;
+  ok = ok && sum == head[3] && fread(&nb, 4, 1, f) == 1 && nb <= n && take(f, recs, nb) && take(f, area, n) && take(f, outlets, n);
+  fclose(f);
+  if (!ok) { printf("FAIL %s is not a dump\n", path); return 1; }
+  std::vector<dh_map*> maps{dh_create((int)head[1], (int)head[2], count.data(), type.data(), size.data(), floor.data())};
+  int bad = 0;
+  for (int v = 0; v < th_variants(); v++)
+    for (uint32_t lanes : {64u, 256u})
+      for (int order : {0, 3}) {
+        Result got;
+        const bool same = run(maps, v, lanes, order, nb + 2u, got) && got.nb[0] == nb && (nb == 0 || memcmp(got.recs.data(), recs.data(), (size_t)nb * sizeof(ThroughRec)) == 0) &&
+                          got.area == area && got.outlets == outlets;
+        if (!same) { printf("FAIL %s variant %d lanes %u order %d: %u basins, expected %u\n", path, v, lanes, order, got.nb[0], nb); bad++; }
+      }
+  dh_destroy(maps[0]);
+  const char* name = strrchr(path, '/');
+  printf("%-32s %4ux%-4u %6u basins  %s\n", name ? name + 1 : path, head[1], head[2], nb, bad ? "FAILED" : "ok");
+  return bad;
+}
+
+int main(int argc, char** argv) {
+  int bad = 0;
+  if (argc > 1) {
+    for (int i = 1; i < argc; i++) bad += check_dump(argv[i]);
+    return bad ? 1 : 0;
+  }
+  const int dims[2][2] = {{33, 47}, {96, 80}};
+  for (const auto& d : dims)
+    for (const char* kind : {"random", "lakes", "plateau", "sawtooth"}) {
+      std::vector<dh_map*> maps{make(kind, d[0], d[1])};
+      bad += check(kind, maps);
+      dh_destroy(maps[0]);
+    }
+  std::vector<dh_map*> three{make("lakes", 33, 47), make("sawtooth", 70, 1), make("random", 1, 70)};
+  bad += check("three maps", three);
+  for (dh_map* m : three) dh_destroy(m);
+  return bad ? 1 : 0;
+}
