@@ -553,6 +553,7 @@ int smx_fill_vertices_cut(smx_ctx* ctx, const float* colors4, int32_t ncolors, i
  * host-driven single edit; out = 44 bytes. */
 int smx_fill_vertex_cut(smx_ctx* ctx, const float* colors4, int32_t ncolors, int32_t mode, double cut, int32_t x, int32_t y, void* out_vertex44);
 int smx_heights_bilinear(smx_ctx* ctx, const float* pos2, int32_t n, double* out);      /* Layermap::height(vec2) (layermap.h:427) */
+/* (reads the four cells (px..px+1, py..py+1) as the reference does: every position must lie in [0, dimx-1) x [0, dimy-1), else -2 and nothing is read) */
 
 /* ---- observability ---- */
 /* The state digest of SURVEY.md Appendix E, computed from a device->host copy: sum of Layermap::height(ivec2) over the

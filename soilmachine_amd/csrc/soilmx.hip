@@ -2722,6 +2722,16 @@ int smx_fill_vertex_cut(smx_ctx* ctx, const float* colors4, int32_t ncolors, int
 
 int smx_heights_bilinear(smx_ctx* ctx, const float* pos2, int32_t n, double* out) {
   FULLMAP("smx_heights_bilinear")
+  if (n < 0 || (n > 0 && (!pos2 || !out))) { ctx->err = "smx_heights_bilinear: n < 0 or a null array"; return -2; }
+  if (n == 0) return 0;
+  // Layermap::height(vec2) reads the cells (px, py), (px + 1, py), (px, py + 1), (px + 1, py + 1) without a check (layermap.h:427-439): a position
+  // is defined only in [0, dimx - 1) x [0, dimy - 1) -- none on a map one cell wide. Anything else (NaN included) is refused before a lane reads.
+  for (int32_t i = 0; i < n; i++) {
+    const float fx = floorf(pos2[2 * i]), fy = floorf(pos2[2 * i + 1]);
+    if (!(fx >= 0.f && fx <= (float)(ctx->cfg.dimx - 2) && fy >= 0.f && fy <= (float)(ctx->cfg.dimy - 2))) {
+      ctx->err = "smx_heights_bilinear: position " + std::to_string(i) + " outside [0, dimx - 1) x [0, dimy - 1)"; return -2;
+    }
+  }
   float* dpos = nullptr; double* dout = nullptr;
   HIPCHK(ctx, ctx->mem.dev(dpos, (size_t)n * 2)); HIPCHK(ctx, ctx->mem.dev(dout, (size_t)n));
   HIPCHK(ctx, hipMemcpyAsync(dpos, pos2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));

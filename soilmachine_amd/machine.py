@@ -148,6 +148,8 @@ class Layermap:
         return out
 
     def heights_bilinear(self, pos: np.ndarray) -> np.ndarray:
+        """Layermap::height(vec2) at the (n, 2) float32 positions: the four cells around each are read, so every position must lie in
+        [0, dimx - 1) x [0, dimy - 1) -- a map one cell wide has none; anything else raises SoilmxError and reads nothing."""
         pos = np.ascontiguousarray(pos, np.float32)
         out = np.zeros(pos.shape[0])
         self._chk(self.L.smx_heights_bilinear(self.h, capi.ptr(pos), pos.shape[0], capi.ptr(out)))

@@ -83,3 +83,18 @@ RESTATEMENT_CASES = [
 
 def restatement_case_id(soil, size, seed, ticks, nwater, nwind) -> str:
     return f"{soil[:-5]}_{size}_s{seed}_t{ticks}_w{nwater}_d{nwind}"
+
+
+# the same on maps that no tile size divides (tests/oddmaps.py), from the initial terrain: soil, dimx, dimy, seed, ticks, nwater, nwind
+RESTATEMENT_ODD_CASES = [(soil, dx, dy, 3, 6, nw, nd)
+                         for soil, nw, nd in (("default.soil", 600, 0), ("rockgravelpebblessand.soil", 300, 80))
+                         for dx, dy in ((33, 47), (17, 19), (65, 63), (9, 7), (1, 70), (70, 1))]
+
+
+def restatement_odd_case_id(soil, dimx, dimy, seed, ticks, nwater, nwind) -> str:
+    return f"{soil[:-5]}_{dimx}x{dimy}_s{seed}_t{ticks}_w{nwater}_d{nwind}"
+
+
+def restatement_wet_case_id(workload, shape) -> str:
+    """the reference continued from the wet start state of tests/oddmaps.py"""
+    return f"oddmaps_{workload}_{shape[0]}x{shape[1]}_wet"
