@@ -52,6 +52,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_through.h"
 #include "soil_streams.h"
 #include "soil_strata.h"
+#include "soil_scratch.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
 
@@ -1959,59 +1960,9 @@ struct ForkScratch {
   ForkDst* tab = nullptr; uint32_t tab_cap = 0;
 };
 
-// smx_lakes / smx_ensemble_lakes: the two u32 planes, rocPRIM's temporary storage, the member table with its pinned source and the
-// results with their pinned landing place (allocated by the first census, grown on demand, kept with the context or the ensemble)
-struct LakeScratch {
-  uint32_t* A = nullptr; uint32_t* B = nullptr; size_t words = 0;
-  void* temp = nullptr; size_t temp_bytes = 0;
-  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
-  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
-};
-
-// smx_drainage / smx_ensemble_drainage: the u32 planes (T, B, R; P and AR once an area was asked for), rocPRIM's temporary storage, the
-// member table with its pinned source and the results with their pinned landing place. Its own, apart from the census's: allocated
-// by the first call, grown on demand, kept with the context or the ensemble.
-struct DrainScratch {
-  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; size_t words = 0;
-  uint32_t* P = nullptr; uint32_t* AR = nullptr; size_t area_words = 0;
-  void* temp = nullptr; size_t temp_bytes = 0;
-  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
-  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
-};
-
-// smx_streams / smx_ensemble_streams: ten u32 planes (the drainage chain's T, R, P and AR and the six of soil_streams.h), rocPRIM's
-// temporary storage, the member table with its pinned source and the results with their pinned landing place. Its own, apart from
-// the drainage's and the census's: allocated by the first call, grown on demand, kept with the context or the ensemble.
-struct StreamScratch {
-  uint32_t* plane[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t words = 0;
-  void* temp = nullptr; size_t temp_bytes = 0;
-  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t tab_cap = 0;
-  char* d_res = nullptr; char* h_res = nullptr; size_t res_cap = 0;
-};
-
-// smx_spill / smx_ensemble_spill: the drainage chain's three u32 planes, the list plane Q and the f64 plane H (soil_spill.h),
-// rocPRIM's temporary storage, the member tables with their pinned source, the counts and the change counts with their pinned
-// landing place, and the basins' table with its own. Its own, apart from the drainage's, the streams' and the census's: allocated
-// at first use, grown on demand, kept with the context or the ensemble. sweeps / batches: of the last call.
-struct SpillScratch {
-  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; uint32_t* Q = nullptr; double* H = nullptr; size_t words = 0;
-  void* temp = nullptr; size_t temp_bytes = 0;
-  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t* d_cnt = nullptr; uint32_t* h_cnt = nullptr; uint32_t tab_cap = 0;
-  SpillAcc* d_acc = nullptr; SpillAcc* h_acc = nullptr; size_t acc_cap = 0;
-  uint32_t sweeps = 0, batches = 0;
-};
-
-// smx_through / smx_ensemble_through: the spill scratch's planes and one more -- T, B, R (the receivers), M (the boundary marks, later
-// the pending words), Q (the boundary list, later the area), the f64 plane H --, rocPRIM's temporary storage, the member tables, the
-// counts and the change counts, and the two basins' tables with their pinned landing places. Its own: allocated at first use, grown
-// on demand, kept with the context or the ensemble. level_sweeps / hop_sweeps / batches: of the last call.
-struct ThroughScratch {
-  uint32_t* T = nullptr; uint32_t* B = nullptr; uint32_t* R = nullptr; uint32_t* M = nullptr; uint32_t* Q = nullptr; double* H = nullptr; size_t words = 0;
-  void* temp = nullptr; size_t temp_bytes = 0;
-  LakeMember* d_tab = nullptr; LakeMember* h_tab = nullptr; uint32_t* d_cnt = nullptr; uint32_t* h_cnt = nullptr; uint32_t tab_cap = 0;
-  SpillAcc* d_sacc = nullptr; SpillAcc* h_sacc = nullptr; ThroughAcc* d_acc = nullptr; ThroughAcc* h_acc = nullptr; size_t acc_cap = 0;
-  uint32_t level_sweeps = 0, hop_sweeps = 0, batches = 0;
-};
+// (the scratch of the five terrain analyses -- smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through -- is AnalysisScratch,
+// soil_scratch.h: one instance per analysis and owner)
+using AnalysisScratch = AnalysisScratchOf<LakeMember>;
 
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
 // lists with their counts and bases and rocPRIM's temporary storage (d_buf); the thickness planes or the section arrays (d_sec); the
@@ -2088,11 +2039,7 @@ struct smx_ctx : EventTimer {
   uint32_t* d_tdone = nullptr; uint32_t* d_tpend[2] = {nullptr, nullptr}; uint32_t* d_tcount = nullptr; uint32_t* h_tcount = nullptr; void* d_tsort = nullptr; size_t tsort_bytes = 0; uint32_t tsort_cap = 0;   // grid pass: tile states, pending lists
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
-  LakeScratch lakes;                  // smx_lakes
-  DrainScratch drain;                 // smx_drainage
-  StreamScratch streams;              // smx_streams
-  SpillScratch spill;                 // smx_spill
-  ThroughScratch through;             // smx_through
+  AnalysisScratch lakes, drain, streams, spill, through;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through: one each
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3672,11 +3619,7 @@ struct smx_ensemble : EventTimer {
   void* d_obs = nullptr; size_t d_obs_cap = 0;
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
-  LakeScratch lakes;                      // smx_ensemble_lakes
-  DrainScratch drain;                     // smx_ensemble_drainage
-  StreamScratch streams;                  // smx_ensemble_streams
-  SpillScratch spill;                     // smx_ensemble_spill
-  ThroughScratch through;                 // smx_ensemble_through
+  AnalysisScratch lakes, drain, streams, spill, through;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through: one each
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4133,785 +4076,544 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
   return 0;
 }
 
-// ---------------- the lake census (smx_lakes / smx_ensemble_lakes; kernels: soil_lakes.h) ----------------
-// One path for both calls: the maps ms[0..nm) share the two planes (member i at words [off_i, off_i + cells_i)), one table upload,
-// k_lake_tiles, k_lake_merge, k_lake_flatten, rocPRIM's exclusive scan of the root marks, k_lake_stats, the counts and the records
-// (and the label plane, where asked for) copied back, one synchronisation -- whatever the maps hold and however many there are.
-// (`mem`: the owner the scratch lives in -- the context's or the ensemble's)
-static_assert(sizeof(smx_lake) == 64 && sizeof(LakeRec) == sizeof(smx_lake) && offsetof(smx_lake, flags) == offsetof(LakeRec, flags), "smx_lake layout");
-static void lakes_drop(LakeScratch& k, DevMem& mem) {
-  mem.drop(k.A); mem.drop(k.B); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
-  k = LakeScratch();
+}  // extern "C"
+
+// ---------------- the five terrain analyses: the lake census, drainage, the stream network, spill, through-drainage ----------------
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through and their smx_ensemble_* twins; kernels: soil_lakes.h, soil_drain.h,
+// soil_streams.h, soil_spill.h, soil_through.h)
+// One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
+// cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
+// stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
+// the drainage chain, the sweep loop and the record cut. Each *_run below says what is particular to it: which planes, which kernels
+// behind the shared chain, which planes go back. Every analysis has a scratch of its own, so the results of the sibling calls are
+// not touched.
+struct AnalysisCall {   // who runs an analysis: a context (its one map) or an ensemble (its members)
+  const char* who; bool ensemble, partial;
+  DevMem& mem; hipStream_t st; smx_ctx* const* ms; uint32_t nm; std::string& err;
+};
+static AnalysisCall call_on(const char* who, smx_ctx*& ctx) { return {who, false, ctx->partial(), ctx->mem, ctx->stream, &ctx, 1u, ctx->err}; }
+static AnalysisCall call_on(const char* who, smx_ensemble* e) { return {who, true, false, e->mem, e->stream, e->members.data(), (uint32_t)e->members.size(), e->err}; }
+
+// The argument checks of the ten entry points, in the order they have always had -- an ensemble is asked for its device first, a
+// context last; an empty ensemble is done (rc 0) before its counts pointer is looked at. false: the
+// entry point returns rc. (record: the name of the public struct; threshold: smx_streams' only)
+static bool analysis_begin(const AnalysisCall& c, const char* record, const char* counts_name, uint64_t struct_size, const uint32_t* threshold, const void* counts,
+                           const void* out, uint32_t cap, int& rc) {
+  auto no = [&](int code, const std::string& why) { c.err = std::string(c.who) + ": " + why; rc = code; return false; };
+  if (c.ensemble && !c.st) return no(-3, "the ensemble has no device (smx_ensemble_create failed)");
+  if (c.partial) return no(-2, "not available on a strip context (smx_create_strip): it holds only a part of the map");
+  if (struct_size == 0) return no(-2, std::string("struct_size is 0 (pass sizeof(") + record + ") of the header you compiled against)");
+  if (threshold && *threshold == 0) return no(-2, "threshold is 0 (a channel cell has an area of at least threshold >= 1)");
+  if (c.ensemble && c.nm == 0) { rc = 0; return false; }
+  if (!counts) return no(-2, std::string(counts_name) + " is null (one count per map)");
+  if (!out && cap) return no(-2, "out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)");
+  if (!c.st) return no(-3, "a context without a device");
+  return true;
 }
-static int lakes_run(const char* who, LakeScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_lake* out, uint64_t struct_size,
-                     uint32_t cap, uint32_t* nlakes, uint32_t* labels, std::string& err) {
-  std::vector<LakeMember> tab(nm);
+
+// The member table of a call and what its launches share: the planes' length, the records' number, the grids. A map keeps min(cap,
+// the most it can hold) records: a lake per 2 x 2 block (its four cells are one lake); a basin or a segment per cell (a plateau);
+// none yet for spill and through, whose basins are counted by the chain first (plan_basins).
+enum CapRule { CAP_BLOCKS, CAP_CELLS, CAP_LATER };
+struct AnalysisPlan {
+  std::vector<LakeMember> tab;
   uint64_t words = 0, nrec = 0;
+  uint32_t most = 0;                // plan_basins: the largest basin count of a map
+  dim3 gt, gf, gs, gb, gr;          // tiles, LAKE_LANES cells a workgroup, the statistics' cells a workgroup; plan_basins: basins, relax sweeps
+  const dim3 wg{LAKE_LANES};
+};
+static int plan_members(const AnalysisCall& c, uint32_t cap, CapRule rule, AnalysisPlan& pl) {
+  pl.tab.resize(c.nm);
   size_t tiles = 1, flat = 1, stat = 1;
   const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
-  for (uint32_t i = 0; i < nm; i++) {
-    const smx_ctx* c = ms[i];
-    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side (the bounding boxes are 16-bit)"; return -2; }
-    LakeMember& m = tab[i];
-    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    const uint64_t most = (uint64_t)((m.dimx + 1) / 2) * (uint64_t)((m.dimy + 1) / 2);   // (the four cells of a 2 x 2 block are one lake)
+  for (uint32_t i = 0; i < c.nm; i++) {
+    const smx_ctx* x = c.ms[i];
+    if (x->cfg.dimx > 65536 || x->cfg.dimy > 65536) { c.err = std::string(c.who) + ": a map of more than 65536 cells a side (the bounding boxes are 16-bit)"; return -2; }
+    LakeMember& m = pl.tab[i];
+    m.cells = x->d.cells; m.dimx = x->cfg.dimx; m.dimy = x->cfg.dimy; m.pad = 0u;
+    m.off = (uint32_t)pl.words; m.rec0 = (uint32_t)pl.nrec;
+    const uint64_t most = rule == CAP_BLOCKS ? (uint64_t)((m.dimx + 1) / 2) * (uint64_t)((m.dimy + 1) / 2) : rule == CAP_CELLS ? (uint64_t)x->ncells : 0u;
     m.cap = (uint32_t)std::min<uint64_t>(cap, most);
-    words += (uint64_t)c->ncells; nrec += m.cap;
-    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one census"; return -2; }
+    pl.words += (uint64_t)x->ncells; pl.nrec += m.cap;
+    if (pl.words > 0xFFFFFFFEull || pl.nrec > 0xFFFFFFFEull) { c.err = std::string(c.who) + ": more than 2^32 - 2 cells (or records) in one call"; return -2; }
     tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
-    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
-    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
+    flat = std::max<size_t>(flat, (x->ncells + LAKE_LANES - 1) / LAKE_LANES);
+    stat = std::max<size_t>(stat, (x->ncells + per - 1) / per);
   }
-  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(LakeAcc);
-  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.A});
+  pl.gt = dim3((unsigned)tiles, c.nm); pl.gf = dim3((unsigned)flat, c.nm); pl.gs = dim3((unsigned)stat, c.nm);
+  return 0;
+}
+static void plan_basins(AnalysisPlan& pl, const uint32_t* counts) {   // spill and through, the chain's counts back: a record for every basin
+  pl.nrec = 0; pl.most = 0;
+  for (LakeMember& m : pl.tab) { m.cap = *counts++; m.rec0 = (uint32_t)pl.nrec; pl.nrec += m.cap; pl.most = std::max(pl.most, m.cap); }
+  pl.gb = dim3((unsigned)(((size_t)pl.most + LAKE_LANES - 1) / LAKE_LANES), pl.gt.y); pl.gr = dim3(std::min<unsigned>(pl.gf.x, SPILL_RELAX_BLOCKS), pl.gt.y);
+}
+// the plan's table into half `half` of the pinned tables (bare: every cap 0), and `halves` halves from `half` on to the device
+static void put_table(AnalysisScratch& k, const AnalysisPlan& pl, uint32_t half, bool bare) {
+  LakeMember* h = k.h_tab + (size_t)half * pl.tab.size();
+  memcpy(h, pl.tab.data(), pl.tab.size() * sizeof(LakeMember));
+  if (bare) for (size_t i = 0; i < pl.tab.size(); i++) h[i].cap = 0u;
+}
+static bool send_tables(const AnalysisCall& c, AnalysisScratch& k, uint32_t half, uint32_t halves) {
+  const size_t at = (size_t)half * c.nm;
+  return hipMemcpyAsync(k.d_tab + at, k.h_tab + at, (size_t)halves * c.nm * sizeof(LakeMember), hipMemcpyHostToDevice, c.st) == hipSuccess;
+}
+static size_t counts_pad(uint32_t nm) { return ((size_t)nm * 4 + 63) & ~(size_t)63; }   // the counts in front of the records: where the records start
+static size_t count_words(uint32_t nm) { return (((size_t)nm + 15) & ~(size_t)15) + 16; }   // spill and through: the counts, then SPILL_BATCH change counts
+static_assert(SPILL_BATCH <= 16, "the change counts' room");
+
+// rocPRIM's exclusive scan of one mark per plane word, and the temporary storage it asks for (folded into `most`)
+static auto lake_marks(const uint32_t* A) { return rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{A}); }
+static auto stream_marks(const uint32_t* D) { return rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), StreamMarkFn{D}); }
+template <class In> static bool scan_words(const AnalysisScratch& k, In in, uint32_t* out, uint64_t words, hipStream_t st) {
+  size_t bytes = k.temp_bytes;
+  return rocprim::exclusive_scan(k.temp, bytes, in, out, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
+}
+template <class In> static bool scan_bytes(const AnalysisCall& c, In in, uint64_t words, size_t& most) {
   size_t tb = 0;
-  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
-  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
-    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
-    if (ok && words > k.words) {
-      mem.drop(k.A); mem.drop(k.B); k.words = 0;
-      ok = mem.dev(k.A, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess;
-      if (ok) k.words = (size_t)words;
-    }
-    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
-    if (ok && nm > k.tab_cap) {
-      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
-      ok = mem.dev(k.d_tab, nm) == hipSuccess && mem.pinned(k.h_tab, nm) == hipSuccess;
-      if (ok) k.tab_cap = nm;
-    }
-    if (ok && res_bytes > k.res_cap) {
-      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
-      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
-      if (ok) k.res_cap = res_bytes;
-    }
-    if (!ok) {
-      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
-      lakes_drop(k, mem);
-      err = std::string(who) + ": out of memory for the census scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
+  if (rocprim::exclusive_scan(nullptr, tb, in, (uint32_t*)nullptr, 0u, (size_t)words, rocprim::plus<uint32_t>(), c.st) != hipSuccess) {
+    c.err = std::string(c.who) + ": sizing the prefix sum failed";
+    return false;
+  }
+  most = std::max(most, std::max<size_t>(tb, 8));   // (a null temporary storage would make the scan a size query again)
+  return true;
+}
+
+// Room for the call in its scratch. What has to grow is dropped and replaced group by group (soil_scratch.h) behind a synchronisation:
+// nothing queued still uses what is dropped. On failure nothing half-sized stays behind, and the failure does not surface in the
+// next launch check.
+static int analysis_reserve(const AnalysisCall& c, AnalysisScratch& k, const AnalysisScratch::Need& need, const char* what, uint64_t nrec) {
+  if (k.fits(need)) return 0;
+  if (hipStreamSynchronize(c.st) == hipSuccess && k.reserve(c.mem, need) == hipSuccess) return 0;
+  (void)hipGetLastError();
+  k.drop(c.mem);
+  c.err = std::string(c.who) + ": out of memory for the " + what + " scratch (" + std::to_string(need.words) + " cells, " + std::to_string(nrec) + " records)";
+  return -1;
+}
+// a plane, or the results, back to the host where `dst` is given, behind what is queued
+static bool copy_back(const AnalysisCall& c, bool ok, void* dst, const void* src, size_t bytes) {
+  return ok && (!dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.st) == hipSuccess);
+}
+// the end of a stretch of queued work: the stream synchronised, a failure of `what` said
+static int analysis_wait(const AnalysisCall& c, bool ok, const char* what) {
+  const hipError_t se = hipStreamSynchronize(c.st);
+  if (ok && se == hipSuccess) return 0;
+  c.err = std::string(c.who) + ": " + what + " failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")";
+  return -1;
+}
+
+// The census's labelling: A takes the root of every wet cell's lake (acc: the census's records, null for everybody else).
+static void launch_lake_labels(const AnalysisPlan& pl, hipStream_t st, const LakeMember* tab, uint32_t* A, LakeAcc* acc) {
+  hipLaunchKernelGGL(k_lake_tiles, pl.gt, pl.wg, 0, st, tab, A, acc);
+  hipLaunchKernelGGL(k_lake_merge, pl.gt, pl.wg, 0, st, tab, A);
+  hipLaunchKernelGGL(k_lake_flatten, pl.gf, pl.wg, 0, st, tab, A);
+}
+// The drainage chain on the planes T and R: the wet cells labelled through `bare` -- the members with cap 0, for k_lake_tiles writes
+// the identities of ITS records for ranks below cap: none here --, then k_drain_recv and k_drain_resolve through `tab`, the members
+// as the drainage kernels see them (acc: the basins' records or null). d_n given, with statistics: the scan of the terminal marks
+// into B and k_drain_stats, T becomes the rank plane and the counts go to d_n. P given, with area: k_drain_pending and k_drain_area
+// on P and AR.
+static bool launch_drain_chain(const AnalysisPlan& pl, hipStream_t st, const AnalysisScratch& k, const LakeMember* bare, const LakeMember* tab, uint32_t* T, uint32_t* B,
+                               uint32_t* R, BasinAcc* acc, uint32_t* d_n, uint32_t* P, uint32_t* AR) {
+  bool ok = true;
+  launch_lake_labels(pl, st, bare, T, nullptr);
+  hipLaunchKernelGGL(k_drain_recv, pl.gt, pl.wg, 0, st, tab, T, R, acc);
+  hipLaunchKernelGGL(k_drain_resolve, pl.gf, pl.wg, 0, st, tab, T);
+  if (d_n) {
+    ok = scan_words(k, lake_marks(T), B, pl.words, st);
+    hipLaunchKernelGGL(k_drain_stats, pl.gs, pl.wg, 0, st, tab, T, B, acc, d_n);
+  }
+  if (P) {
+    hipLaunchKernelGGL(k_drain_pending, pl.gf, pl.wg, 0, st, tab, R, P, AR);
+    hipLaunchKernelGGL(k_drain_area, pl.gf, pl.wg, 0, st, tab, R, P, AR);
+  }
+  return ok;
+}
+
+// The sweeps whose number depends on the map: this is where a call looks at the device more than once. launch(n, chg) queues sweep
+// number n (counted from 1), which counts what it changed into *chg. SPILL_BATCH sweeps go between two looks at the change counts
+// (one synchronisation each), until the batch with a sweep that changed nothing. Each sweep but the last settles a basin at least,
+// so giving up after most + 2 cannot happen. (`settling`: what the sweeps settle, for that message)
+template <class Launch> static int sweep_until_settled(const AnalysisCall& c, AnalysisScratch& k, const AnalysisPlan& pl, uint32_t& sweeps, const char* what,
+                                                       const char* settling, Launch launch) {
+  uint32_t* const d_chg = k.d_cnt + (count_words(c.nm) - 16);
+  uint32_t* const h_chg = k.h_cnt + (count_words(c.nm) - 16);
+  for (bool done = false; !done;) {
+    if ((uint64_t)sweeps >= (uint64_t)pl.most + 2u) {
+      (void)hipStreamSynchronize(c.st);
+      c.err = std::string(c.who) + ": the " + settling + " did not settle within " + std::to_string(sweeps) + " sweeps (" + std::to_string(pl.most) + " basins)";
       return -1;
     }
-  }
-  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
-  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
-  LakeAcc* acc = reinterpret_cast<LakeAcc*>(k.d_res + rec_at);
-  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
-  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_lake_tiles, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A, acc);
-    hipLaunchKernelGGL(k_lake_merge, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A);
-    hipLaunchKernelGGL(k_lake_flatten, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A);
-    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.A});
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_lake_stats, dim3((unsigned)stat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.A, k.B, acc, d_n);
-  }
-  ok = ok && hipGetLastError() == hipSuccess;
-  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && labels) ok = hipMemcpyAsync(labels, k.A, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;   // (smx_lakes only: one map, off = 0)
-  const hipError_t se = hipStreamSynchronize(st);
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the census failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
-  const LakeAcc* a = reinterpret_cast<const LakeAcc*>(k.h_res + rec_at);
-  const size_t take = struct_size < sizeof(smx_lake) ? (size_t)struct_size : sizeof(smx_lake);
-  for (uint32_t i = 0; i < nm; i++) {
-    nlakes[i] = n[i];
-    const uint32_t w = std::min(n[i], tab[i].cap);   // (= min(cap, n): a map holds at most tab[i].cap lakes where cap was cut)
-    for (uint32_t r = 0; r < w; r++) {
-      LakeRec rec;
-      lake_finish(a[tab[i].rec0 + r], rec);
-      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
-    }
+    bool ok = hipMemsetAsync(d_chg, 0, 16 * 4, c.st) == hipSuccess;
+    for (uint32_t j = 0; ok && j < SPILL_BATCH; j++) launch(sweeps + j + 1u, d_chg + j);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = copy_back(c, ok, h_chg, d_chg, 16 * 4);
+    if (analysis_wait(c, ok, what)) return -1;
+    sweeps += SPILL_BATCH; k.batches++;
+    for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || h_chg[j] == 0u;
   }
   return 0;
 }
 
+// The counts and the records into the caller's arrays: map i's records at out[i * cap ...], each cut to the caller's struct_size (a
+// header older than the library has the shorter record). finish(j, rec) hands out record j of the call's table, made in rec where it
+// has to be made (the streams' records are finished on the device: no second copy of what may be millions of them).
+template <class Rec, class Finish> static void cut_records(const AnalysisPlan& pl, const uint32_t* n, void* out, uint64_t struct_size, uint32_t cap, uint32_t* counts,
+                                                           Finish finish) {
+  const size_t take = struct_size < sizeof(Rec) ? (size_t)struct_size : sizeof(Rec);
+  for (size_t i = 0; i < pl.tab.size(); i++) {
+    counts[i] = n[i];
+    const uint32_t w = std::min(n[i], std::min(pl.tab[i].cap, cap));   // (a map holds at most tab[i].cap records where cap was cut)
+    for (uint32_t r = 0; r < w; r++) {
+      Rec rec;
+      const Rec& done = finish((size_t)pl.tab[i].rec0 + r, rec);
+      memcpy(static_cast<char*>(out) + (i * cap + r) * (size_t)struct_size, &done, take);
+    }
+  }
+}
+
+// ---- the lake census: planes A (labels) and B (ranks); the labelling, the scan of the root marks, k_lake_stats; the counts and the
+// records (and the label plane, where asked for) copied back, one synchronisation
+static_assert(sizeof(smx_lake) == 64 && sizeof(LakeRec) == sizeof(smx_lake) && offsetof(smx_lake, flags) == offsetof(LakeRec, flags), "smx_lake layout");
+static int lakes_run(const AnalysisCall& c, AnalysisScratch& k, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_BLOCKS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm);
+  need.words = (size_t)pl.words; need.planes = 2; need.members = c.nm; need.res_bytes = rec_at + (size_t)pl.nrec * sizeof(LakeAcc);
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "census", pl.nrec)) return rc;
+  uint32_t* const A = k.plane[0]; uint32_t* const B = k.plane[1];
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  LakeAcc* acc = reinterpret_cast<LakeAcc*>(k.d_res + rec_at);
+  put_table(k, pl, 0, false);
+  bool ok = send_tables(c, k, 0, 1);
+  if (ok) {
+    launch_lake_labels(pl, c.st, k.d_tab, A, acc);
+    ok = scan_words(k, lake_marks(A), B, pl.words, c.st);
+    hipLaunchKernelGGL(k_lake_stats, pl.gs, pl.wg, 0, c.st, k.d_tab, A, B, acc, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  ok = copy_back(c, ok, labels, A, (size_t)pl.words * 4);   // (smx_lakes only: one map, off = 0)
+  if (analysis_wait(c, ok, "the census")) return -1;
+  const LakeAcc* a = reinterpret_cast<const LakeAcc*>(k.h_res + rec_at);
+  cut_records<LakeRec>(pl, reinterpret_cast<const uint32_t*>(k.h_res), out, struct_size, cap, nlakes, [a](size_t j, LakeRec& rec) -> const LakeRec& { lake_finish(a[j], rec); return rec; });
+  return 0;
+}
+
+// ---- drainage: planes T, B, R, and P and AR once an area is asked for; the chain with its statistics, and with the area where asked
+// for; the counts, the records and the planes asked for copied back, one synchronisation
+static_assert(sizeof(smx_basin) == 48 && sizeof(BasinRec) == sizeof(smx_basin) && offsetof(smx_basin, height_min) == offsetof(BasinRec, height_min) &&
+              offsetof(smx_basin, x0) == offsetof(BasinRec, x0), "smx_basin layout");
+static int drain_run(const AnalysisCall& c, AnalysisScratch& k, smx_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* receivers,
+                     uint32_t* labels, uint32_t* area) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_CELLS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm);
+  need.words = (size_t)pl.words; need.planes = 3; need.more = area ? 2 : 0; need.members = c.nm; need.res_bytes = rec_at + (size_t)pl.nrec * sizeof(BasinAcc);
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "drainage", pl.nrec)) return rc;
+  uint32_t* const T = k.plane[0]; uint32_t* const B = k.plane[1]; uint32_t* const R = k.plane[2]; uint32_t* const P = k.plane[3]; uint32_t* const AR = k.plane[4];
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  BasinAcc* acc = reinterpret_cast<BasinAcc*>(k.d_res + rec_at);
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  if (ok) ok = launch_drain_chain(pl, c.st, k, k.d_tab + c.nm, k.d_tab, T, B, R, acc, d_n, area ? P : nullptr, AR);
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_drainage only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, receivers, R, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, labels, T, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, area, AR, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "drainage")) return -1;
+  const BasinAcc* a = reinterpret_cast<const BasinAcc*>(k.h_res + rec_at);
+  cut_records<BasinRec>(pl, reinterpret_cast<const uint32_t*>(k.h_res), out, struct_size, cap, nbasins, [a](size_t j, BasinRec& rec) -> const BasinRec& { drain_finish(a[j], rec); return rec; });
+  return 0;
+}
+
+// ---- the stream network: the ten planes of StreamPlanes; the chain without statistics (the basins' ranks are not needed, T stays the
+// terminal plane) and with the area, all of it through the bare table; k_stream_mark, k_stream_order, the scan of the start marks,
+// k_stream_segments through the table with the record caps; the counts, the records and the planes asked for copied back, one
+// synchronisation
+static_assert(sizeof(smx_segment) == 64 && sizeof(StreamRec) == sizeof(smx_segment) && offsetof(smx_segment, down) == offsetof(StreamRec, down) &&
+              offsetof(smx_segment, straight) == offsetof(StreamRec, straight) && offsetof(smx_segment, height_first) == offsetof(StreamRec, height_first), "smx_segment layout");
+static int streams_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap, uint32_t* nstreams,
+                       uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_CELLS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm);
+  need.words = (size_t)pl.words; need.planes = 10; need.members = c.nm; need.res_bytes = rec_at + (size_t)pl.nrec * sizeof(StreamRec);
+  if (!scan_bytes(c, stream_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "stream", pl.nrec)) return rc;
+  const StreamPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.plane[4], k.plane[5], k.plane[6], k.plane[7], k.plane[8], k.plane[9]};
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  StreamRec* recs = reinterpret_cast<StreamRec*>(k.d_res + rec_at);
+  const LakeMember* bare = k.d_tab + c.nm;
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  if (ok) {
+    launch_drain_chain(pl, c.st, k, bare, bare, p.T, nullptr, p.R, nullptr, nullptr, p.P, p.AR);
+    hipLaunchKernelGGL(k_stream_mark, pl.gf, pl.wg, 0, c.st, bare, threshold, p);
+    hipLaunchKernelGGL(k_stream_order, pl.gf, pl.wg, 0, c.st, bare, threshold, p);
+    ok = scan_words(k, stream_marks(p.D), p.B, pl.words, c.st);
+    hipLaunchKernelGGL(k_stream_segments, pl.gf, pl.wg, 0, c.st, k.d_tab, segments ? 1 : 0, p, recs, d_n);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_streams only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, order, p.O, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, segments, p.SG, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, reach, p.RE, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, heads, p.H, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "the stream network")) return -1;
+  const StreamRec* a = reinterpret_cast<const StreamRec*>(k.h_res + rec_at);   // (finished on the device: handed out as they are)
+  cut_records<StreamRec>(pl, reinterpret_cast<const uint32_t*>(k.h_res), out, struct_size, cap, nstreams, [a](size_t j, StreamRec&) -> const StreamRec& { return a[j]; });
+  return 0;
+}
+
+// ---- spill: planes T, B, R, the list plane Q and the f64 plane H. The chain with its statistics and no records (T becomes the rank
+// plane), the counts back: the FIRST synchronisation -- the basins' table, the result region, is sized by them. Then k_spill_init,
+// k_spill_pass<0>, k_spill_pass<1>, the scan of the boundary marks, k_spill_list, k_spill_point; k_spill_relax in the sweep loop;
+// k_spill_store; the table and the plane back, the last synchronisation.
+static_assert(sizeof(smx_spill_record) == 64 && sizeof(SpillRec) == sizeof(smx_spill_record) && offsetof(smx_spill_record, pour_height) == offsetof(SpillRec, pour_height) &&
+              offsetof(smx_spill_record, storage_q40) == offsetof(SpillRec, storage_q40) && offsetof(smx_spill_record, flags) == offsetof(SpillRec, flags), "smx_spill_record layout");
+static int spill_run(const AnalysisCall& c, AnalysisScratch& k, smx_spill_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, double* filled) {
+  k.sweeps[0] = 0; k.batches = 0;
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_LATER, pl)) return rc;
+  AnalysisScratch::Need need;
+  need.words = (size_t)pl.words; need.planes = 4; need.f64 = true; need.members = c.nm; need.count_words = count_words(c.nm);
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes) || !scan_bytes(c, (const uint32_t*)nullptr, pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "spill", 0)) return rc;
+  const SpillPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.h64};
+  // the bare table (no records) for the drainage chain; behind it, once the counts are known, the table with the basins
+  put_table(k, pl, 0, false);
+  bool ok = send_tables(c, k, 0, 1);
+  if (ok) ok = launch_drain_chain(pl, c.st, k, k.d_tab, k.d_tab, p.T, p.B, p.R, nullptr, k.d_cnt, nullptr, nullptr);
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_cnt, k.d_cnt, (size_t)c.nm * 4);
+  if (analysis_wait(c, ok, "the drainage chain")) return -1;
+  plan_basins(pl, k.h_cnt);
+  need.res_bytes = (size_t)pl.nrec * sizeof(SpillAcc);
+  if (int rc = analysis_reserve(c, k, need, "spill", pl.nrec)) return rc;   // (the stream is idle)
+  SpillAcc* acc = reinterpret_cast<SpillAcc*>(k.d_res);
+  const LakeMember* full = k.d_tab + c.nm;
+  put_table(k, pl, 1, false);
+  ok = send_tables(c, k, 1, 1);
+  if (ok) {
+    hipLaunchKernelGGL(k_spill_init, pl.gb, pl.wg, 0, c.st, full, acc);
+    hipLaunchKernelGGL(k_spill_pass<0>, pl.gt, pl.wg, 0, c.st, full, p, acc);
+    hipLaunchKernelGGL(k_spill_pass<1>, pl.gt, pl.wg, 0, c.st, full, p, acc);
+    ok = scan_words(k, (const uint32_t*)p.R, p.B, pl.words, c.st);
+    hipLaunchKernelGGL(k_spill_list, pl.gf, pl.wg, 0, c.st, full, p);
+    hipLaunchKernelGGL(k_spill_point, pl.gb, pl.wg, 0, c.st, full, p, acc);
+  }
+  if (!ok) return analysis_wait(c, false, "the spill analysis");
+  if (sweep_until_settled(c, k, pl, k.sweeps[0], "the spill analysis", "fill levels",
+                          [&](uint32_t n, uint32_t* chg) { hipLaunchKernelGGL(k_spill_relax, pl.gr, pl.wg, 0, c.st, full, n, p, acc, chg); }))
+    return -1;
+  hipLaunchKernelGGL(k_spill_store, pl.gs, pl.wg, 0, c.st, full, p, acc, filled ? 1 : 0);
+  ok = hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  ok = copy_back(c, ok, filled, p.H, (size_t)pl.words * 8);   // (smx_spill only: one map, off = 0)
+  if (analysis_wait(c, ok, "the spill analysis")) return -1;
+  const SpillAcc* a = reinterpret_cast<const SpillAcc*>(k.h_res);
+  cut_records<SpillRec>(pl, k.h_cnt, out, struct_size, cap, nbasins, [a](size_t j, SpillRec& rec) -> const SpillRec& { spill_finish(a[j], rec); return rec; });
+  return 0;
+}
+
+// ---- through-drainage: spill's planes and one more -- T, B, R (the receivers), M (the boundary marks, later the pending words), Q (the
+// boundary list, later the area), the f64 plane H. The chain with its statistics and no records, the counts back: the FIRST
+// synchronisation; the result region holds the two basins' tables, spill's in front. Then k_spill_init, k_through_init,
+// k_spill_pass<0>, k_spill_pass<1> (their boundary marks go to M: R stays the receivers), the scan, k_spill_list, k_spill_point,
+// k_through_count; k_spill_relax in the sweep loop, k_through_hops likewise; k_through_exit; k_drain_pending where the area is asked
+// for (P takes M's plane and AR takes Q's: the marks and the list are done with); k_through_link<0>, <1>, k_through_accumulate,
+// k_through_outlet, k_through_plane and k_through_area where their planes are asked for; the tables and the planes back, the last
+// synchronisation.
+static_assert(sizeof(smx_through_record) == 64 && sizeof(ThroughRec) == sizeof(smx_through_record) && offsetof(smx_through_record, exit_height) == offsetof(ThroughRec, exit_height) &&
+              offsetof(smx_through_record, hops) == offsetof(ThroughRec, hops) && offsetof(smx_through_record, through_cells) == offsetof(ThroughRec, through_cells), "smx_through_record layout");
+static_assert(sizeof(SpillAcc) % alignof(ThroughAcc) == 0, "the second table of the result region is aligned");
+static int through_run(const AnalysisCall& c, AnalysisScratch& k, smx_through_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* through_area,
+                       uint32_t* outlets) {
+  k.sweeps[0] = k.sweeps[1] = 0; k.batches = 0;
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_LATER, pl)) return rc;
+  AnalysisScratch::Need need;
+  need.words = (size_t)pl.words; need.planes = 5; need.f64 = true; need.members = c.nm; need.count_words = count_words(c.nm);
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes) || !scan_bytes(c, (const uint32_t*)nullptr, pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "through-drainage", 0)) return rc;
+  uint32_t* const T = k.plane[0]; uint32_t* const B = k.plane[1]; uint32_t* const R = k.plane[2]; uint32_t* const M = k.plane[3]; uint32_t* const Q = k.plane[4];
+  const SpillPlanes sp{T, B, M, Q, k.h64};     // what the spill chain's kernels see: their R is M
+  const ThroughPlanes p{T, B, M, Q, k.h64};
+  uint32_t* const P = M;                       // behind k_through_exit
+  uint32_t* const AR = through_area ? Q : nullptr;
+  put_table(k, pl, 0, false);
+  bool ok = send_tables(c, k, 0, 1);
+  if (ok) ok = launch_drain_chain(pl, c.st, k, k.d_tab, k.d_tab, T, B, R, nullptr, k.d_cnt, nullptr, nullptr);
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_cnt, k.d_cnt, (size_t)c.nm * 4);
+  if (analysis_wait(c, ok, "the drainage chain")) return -1;
+  plan_basins(pl, k.h_cnt);
+  need.res_bytes = (size_t)pl.nrec * (sizeof(SpillAcc) + sizeof(ThroughAcc));
+  if (int rc = analysis_reserve(c, k, need, "through-drainage", pl.nrec)) return rc;   // (the stream is idle)
+  const size_t acc_at = (size_t)pl.nrec * sizeof(SpillAcc);
+  SpillAcc* sacc = reinterpret_cast<SpillAcc*>(k.d_res);
+  ThroughAcc* acc = reinterpret_cast<ThroughAcc*>(k.d_res + acc_at);
+  const LakeMember* full = k.d_tab + c.nm;
+  put_table(k, pl, 1, false);
+  ok = send_tables(c, k, 1, 1);
+  if (ok) {
+    hipLaunchKernelGGL(k_spill_init, pl.gb, pl.wg, 0, c.st, full, sacc);
+    hipLaunchKernelGGL(k_through_init, pl.gb, pl.wg, 0, c.st, full, acc);
+    hipLaunchKernelGGL(k_spill_pass<0>, pl.gt, pl.wg, 0, c.st, full, sp, sacc);
+    hipLaunchKernelGGL(k_spill_pass<1>, pl.gt, pl.wg, 0, c.st, full, sp, sacc);
+    ok = scan_words(k, (const uint32_t*)M, B, pl.words, c.st);
+    hipLaunchKernelGGL(k_spill_list, pl.gf, pl.wg, 0, c.st, full, sp);
+    hipLaunchKernelGGL(k_spill_point, pl.gb, pl.wg, 0, c.st, full, sp, sacc);
+    hipLaunchKernelGGL(k_through_count, pl.gs, pl.wg, 0, c.st, full, T, acc);
+  }
+  if (!ok) return analysis_wait(c, false, "the through-drainage");
+  // the fill levels first and the hop counts behind them
+  if (sweep_until_settled(c, k, pl, k.sweeps[0], "the through-drainage", "fill levels",
+                          [&](uint32_t n, uint32_t* chg) { hipLaunchKernelGGL(k_spill_relax, pl.gr, pl.wg, 0, c.st, full, n, sp, sacc, chg); }))
+    return -1;
+  if (sweep_until_settled(c, k, pl, k.sweeps[1], "the through-drainage", "hop counts",
+                          [&](uint32_t, uint32_t* chg) { hipLaunchKernelGGL(k_through_hops, pl.gr, pl.wg, 0, c.st, full, p, sacc, acc, chg); }))
+    return -1;
+  hipLaunchKernelGGL(k_through_exit, pl.gr, pl.wg, 0, c.st, full, p, sacc, acc);
+  if (AR) hipLaunchKernelGGL(k_drain_pending, pl.gf, pl.wg, 0, c.st, full, R, P, AR);
+  hipLaunchKernelGGL(k_through_link<0>, pl.gb, pl.wg, 0, c.st, full, p, sacc, acc);
+  hipLaunchKernelGGL(k_through_link<1>, pl.gb, pl.wg, 0, c.st, full, p, sacc, acc);
+  hipLaunchKernelGGL(k_through_accumulate, pl.gb, pl.wg, 0, c.st, full, acc, AR);
+  hipLaunchKernelGGL(k_through_outlet, pl.gb, pl.wg, 0, c.st, full, sacc, acc);
+  if (outlets) hipLaunchKernelGGL(k_through_plane, pl.gf, pl.wg, 0, c.st, full, T, acc, B);   // (B is done with)
+  if (AR) hipLaunchKernelGGL(k_through_area, pl.gf, pl.wg, 0, c.st, full, R, P, AR);
+  ok = hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_through only: one map, off = 0)
+  ok = copy_back(c, ok, through_area, AR, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, outlets, B, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "the through-drainage")) return -1;
+  const SpillAcc* sa = reinterpret_cast<const SpillAcc*>(k.h_res);
+  const ThroughAcc* a = reinterpret_cast<const ThroughAcc*>(k.h_res + acc_at);
+  cut_records<ThroughRec>(pl, k.h_cnt, out, struct_size, cap, nbasins, [sa, a](size_t j, ThroughRec& rec) -> const ThroughRec& { through_finish(sa[j], a[j], rec); return rec; });
+  return 0;
+}
+
+extern "C" {
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
   if (!ctx) return -2;
-  FULLMAP("smx_lakes")
-  if (struct_size == 0) { ctx->err = "smx_lakes: struct_size is 0 (pass sizeof(smx_lake) of the header you compiled against)"; return -2; }
-  if (!nlakes) { ctx->err = "smx_lakes: nlakes is null"; return -2; }
-  if (!out && cap) { ctx->err = "smx_lakes: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
-  if (!ctx->stream) { ctx->err = "smx_lakes: a context without a device"; return -3; }
+  const AnalysisCall c = call_on("smx_lakes", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_lake", "nlakes", struct_size, nullptr, nlakes, out, cap, rc)) return rc;
   roctx_range rr("soilmx:lakes");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return lakes_run("smx_lakes", ctx->lakes, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nlakes, labels, ctx->err);
+  return lakes_run(c, ctx->lakes, out, struct_size, cap, nlakes, labels);
 }
 int smx_ensemble_lakes(smx_ensemble* e, smx_lake* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nlakes) {
   if (!e) return -2;
-  if (!e->stream) { e->err = "smx_ensemble_lakes: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
-  if (struct_size == 0) { e->err = "smx_ensemble_lakes: struct_size is 0 (pass sizeof(smx_lake) of the header you compiled against)"; return -2; }
-  const uint32_t nm = (uint32_t)e->members.size();
-  if (nm == 0) return 0;
-  if (!nlakes) { e->err = "smx_ensemble_lakes: nlakes is null (one count per member)"; return -2; }
-  if (!out && cap_per_member) { e->err = "smx_ensemble_lakes: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_lakes", e);
+  int rc;
+  if (!analysis_begin(c, "smx_lake", "nlakes", struct_size, nullptr, nlakes, out, cap_per_member, rc)) return rc;
   roctx_range rr("soilmx:ensemble_lakes");
   HIPCHK(e, hipSetDevice(e->device));
-  return lakes_run("smx_ensemble_lakes", e->lakes, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nlakes, nullptr, e->err);
+  return lakes_run(c, e->lakes, out, struct_size, cap_per_member, nlakes, nullptr);
 }
-
-// ---------------- drainage (smx_drainage / smx_ensemble_drainage; kernels: soil_drain.h and the census's) ----------------
-// One path for both calls, shaped as lakes_run: one table upload; k_lake_tiles, k_lake_merge and k_lake_flatten label the wet cells on
-// the drainage scratch (the table's cap is 0 for them: they touch no record); k_drain_recv, k_drain_resolve, rocPRIM's exclusive scan
-// of the terminal marks, k_drain_stats; k_drain_pending and k_drain_area where the area plane is asked for; the counts, the records and
-// the planes asked for copied back, one synchronisation -- whatever the maps hold and however many there are.
-static_assert(sizeof(smx_basin) == 48 && sizeof(BasinRec) == sizeof(smx_basin) && offsetof(smx_basin, height_min) == offsetof(BasinRec, height_min) &&
-              offsetof(smx_basin, x0) == offsetof(BasinRec, x0), "smx_basin layout");
-static void drain_drop(DrainScratch& k, DevMem& mem) {
-  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.P); mem.drop(k.AR); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
-  k = DrainScratch();
-}
-static int drain_run(const char* who, DrainScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_basin* out, uint64_t struct_size,
-                     uint32_t cap, uint32_t* nbasins, uint32_t* receivers, uint32_t* labels, uint32_t* area, std::string& err) {
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0;
-  size_t tiles = 1, flat = 1, stat = 1;
-  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
-  for (uint32_t i = 0; i < nm; i++) {
-    const smx_ctx* c = ms[i];
-    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side (the bounding boxes are 16-bit)"; return -2; }
-    LakeMember& m = tab[i];
-    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    m.cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)c->ncells);   // (every cell of a plateau is a basin)
-    words += (uint64_t)c->ncells; nrec += m.cap;
-    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one call"; return -2; }
-    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
-    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
-    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
-  }
-  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(BasinAcc);
-  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
-  size_t tb = 0;
-  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
-  if (ok && (words > k.words || (area && words > k.area_words) || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
-    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
-    if (ok && words > k.words) {
-      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); k.words = 0;
-      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess;
-      if (ok) k.words = (size_t)words;
-    }
-    if (ok && area && words > k.area_words) {
-      mem.drop(k.P); mem.drop(k.AR); k.area_words = 0;
-      ok = mem.dev(k.P, (size_t)words) == hipSuccess && mem.dev(k.AR, (size_t)words) == hipSuccess;
-      if (ok) k.area_words = (size_t)words;
-    }
-    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
-    if (ok && nm > k.tab_cap) {
-      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
-      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess;
-      if (ok) k.tab_cap = nm;
-    }
-    if (ok && res_bytes > k.res_cap) {
-      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
-      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
-      if (ok) k.res_cap = res_bytes;
-    }
-    if (!ok) {
-      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
-      drain_drop(k, mem);
-      err = std::string(who) + ": out of memory for the drainage scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
-      return -1;
-    }
-  }
-  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
-  // two tables: the members as the drainage kernels see them, and, behind them, the same members with cap 0 for the census's kernels
-  // (k_lake_tiles writes the identities of ITS records for ranks below cap: none here)
-  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
-  for (uint32_t i = 0; i < nm; i++) { k.h_tab[nm + i] = tab[i]; k.h_tab[nm + i].cap = 0u; }
-  const LakeMember* wet_tab = k.d_tab + nm;
-  BasinAcc* acc = reinterpret_cast<BasinAcc*>(k.d_res + rec_at);
-  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
-  ok = hipMemcpyAsync(k.d_tab, k.h_tab, 2 * (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_lake_tiles, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T, (LakeAcc*)nullptr);
-    hipLaunchKernelGGL(k_lake_merge, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T);
-    hipLaunchKernelGGL(k_lake_flatten, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, wet_tab, k.T);
-    hipLaunchKernelGGL(k_drain_recv, dim3((unsigned)tiles, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T, k.R, acc);
-    hipLaunchKernelGGL(k_drain_resolve, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T);
-    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_drain_stats, dim3((unsigned)stat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.T, k.B, acc, d_n);
-    if (area) {
-      hipLaunchKernelGGL(k_drain_pending, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.R, k.P, k.AR);
-      hipLaunchKernelGGL(k_drain_area, dim3((unsigned)flat, nm), dim3(LAKE_LANES), 0, st, k.d_tab, k.R, k.P, k.AR);
-    }
-  }
-  ok = ok && hipGetLastError() == hipSuccess;
-  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  // (smx_drainage only: one map, off = 0, so a plane index is a cell index)
-  if (ok && receivers) ok = hipMemcpyAsync(receivers, k.R, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && labels) ok = hipMemcpyAsync(labels, k.T, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && area) ok = hipMemcpyAsync(area, k.AR, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  const hipError_t se = hipStreamSynchronize(st);
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": drainage failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
-  const BasinAcc* a = reinterpret_cast<const BasinAcc*>(k.h_res + rec_at);
-  const size_t take = struct_size < sizeof(smx_basin) ? (size_t)struct_size : sizeof(smx_basin);
-  for (uint32_t i = 0; i < nm; i++) {
-    nbasins[i] = n[i];
-    const uint32_t w = std::min(n[i], tab[i].cap);
-    for (uint32_t r = 0; r < w; r++) {
-      BasinRec rec;
-      drain_finish(a[tab[i].rec0 + r], rec);
-      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
-    }
-  }
-  return 0;
-}
-
 int smx_drainage(smx_ctx* ctx, smx_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* receivers, uint32_t* labels, uint32_t* area) {
   if (!ctx) return -2;
-  FULLMAP("smx_drainage")
-  if (struct_size == 0) { ctx->err = "smx_drainage: struct_size is 0 (pass sizeof(smx_basin) of the header you compiled against)"; return -2; }
-  if (!nbasins) { ctx->err = "smx_drainage: nbasins is null"; return -2; }
-  if (!out && cap) { ctx->err = "smx_drainage: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
-  if (!ctx->stream) { ctx->err = "smx_drainage: a context without a device"; return -3; }
+  const AnalysisCall c = call_on("smx_drainage", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_basin", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
   roctx_range rr("soilmx:drainage");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return drain_run("smx_drainage", ctx->drain, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, receivers, labels, area, ctx->err);
+  return drain_run(c, ctx->drain, out, struct_size, cap, nbasins, receivers, labels, area);
 }
 int smx_ensemble_drainage(smx_ensemble* e, smx_basin* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
   if (!e) return -2;
-  if (!e->stream) { e->err = "smx_ensemble_drainage: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
-  if (struct_size == 0) { e->err = "smx_ensemble_drainage: struct_size is 0 (pass sizeof(smx_basin) of the header you compiled against)"; return -2; }
-  const uint32_t nm = (uint32_t)e->members.size();
-  if (nm == 0) return 0;
-  if (!nbasins) { e->err = "smx_ensemble_drainage: nbasins is null (one count per member)"; return -2; }
-  if (!out && cap_per_member) { e->err = "smx_ensemble_drainage: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_drainage", e);
+  int rc;
+  if (!analysis_begin(c, "smx_basin", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
   roctx_range rr("soilmx:ensemble_drainage");
   HIPCHK(e, hipSetDevice(e->device));
-  return drain_run("smx_ensemble_drainage", e->drain, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, e->err);
+  return drain_run(c, e->drain, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr);
 }
-
-// ---------------- the stream network (smx_streams / smx_ensemble_streams; kernels: soil_streams.h, soil_drain.h and the census's) ----------------
-// One path for both calls, shaped as drain_run, on a scratch of its own: one table upload; k_lake_tiles, k_lake_merge, k_lake_flatten,
-// k_drain_recv, k_drain_resolve, k_drain_pending and k_drain_area (the table's cap is 0 for them: they touch no record; the basins'
-// scan and statistics are not needed, T stays the terminal plane); k_stream_mark, k_stream_order, rocPRIM's exclusive scan of the
-// start marks, k_stream_segments; the counts, the records and the planes asked for copied back, one synchronisation -- whatever the
-// maps hold and however many there are. smx_drainage's scratch and results are not touched.
-static_assert(sizeof(smx_segment) == 64 && sizeof(StreamRec) == sizeof(smx_segment) && offsetof(smx_segment, down) == offsetof(StreamRec, down) &&
-              offsetof(smx_segment, straight) == offsetof(StreamRec, straight) && offsetof(smx_segment, height_first) == offsetof(StreamRec, height_first), "smx_segment layout");
-static void streams_drop(StreamScratch& k, DevMem& mem) {
-  for (uint32_t*& q : k.plane) mem.drop(q);
-  mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_res); mem.drop(k.h_res);
-  k = StreamScratch();
-}
-static int streams_run(const char* who, StreamScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, uint32_t threshold, smx_segment* out,
-                       uint64_t struct_size, uint32_t cap, uint32_t* nstreams, uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads, std::string& err) {
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0;
-  size_t tiles = 1, flat = 1;
-  for (uint32_t i = 0; i < nm; i++) {
-    const smx_ctx* c = ms[i];
-    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
-    LakeMember& m = tab[i];
-    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    m.cap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)c->ncells);   // (threshold 1 on a plateau: every cell is a segment)
-    words += (uint64_t)c->ncells; nrec += m.cap;
-    if (words > 0xFFFFFFFEull || nrec > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells (or records) in one call"; return -2; }
-    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
-    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
-  }
-  const size_t rec_at = ((size_t)nm * 4 + 63) & ~(size_t)63, res_bytes = rec_at + (size_t)nrec * sizeof(StreamRec);
-  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), StreamMarkFn{k.plane[4]});
-  size_t tb = 0;
-  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.plane[8], 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-  if (tb == 0) tb = 8;   // (a null temporary storage would make the scan a size query again)
-  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap || res_bytes > k.res_cap)) {
-    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
-    if (ok && words > k.words) {
-      for (uint32_t*& q : k.plane) mem.drop(q);
-      k.words = 0;
-      for (uint32_t*& q : k.plane) ok = ok && mem.dev(q, (size_t)words) == hipSuccess;
-      if (ok) k.words = (size_t)words;
-    }
-    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
-    if (ok && nm > k.tab_cap) {
-      mem.drop(k.d_tab); mem.drop(k.h_tab); k.tab_cap = 0;
-      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess;
-      if (ok) k.tab_cap = nm;
-    }
-    if (ok && res_bytes > k.res_cap) {
-      mem.drop(k.d_res); mem.drop(k.h_res); k.res_cap = 0;
-      ok = mem.dev(k.d_res, res_bytes) == hipSuccess && mem.pinned(k.h_res, res_bytes) == hipSuccess;
-      if (ok) k.res_cap = res_bytes;
-    }
-    if (!ok) {
-      (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
-      streams_drop(k, mem);
-      err = std::string(who) + ": out of memory for the stream scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " records)";
-      return -1;
-    }
-  }
-  if (!ok) { err = std::string(who) + ": sizing the prefix sum failed"; return -1; }
-  // two tables: the members with their record caps for k_stream_segments, and, behind them, the same members with cap 0 for the
-  // census's and the drainage's kernels (they write the identities of THEIR records for ranks below cap: none here)
-  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
-  for (uint32_t i = 0; i < nm; i++) { k.h_tab[nm + i] = tab[i]; k.h_tab[nm + i].cap = 0u; }
-  const LakeMember* bare = k.d_tab + nm;
-  const StreamPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.plane[4], k.plane[5], k.plane[6], k.plane[7], k.plane[8], k.plane[9]};
-  StreamRec* recs = reinterpret_cast<StreamRec*>(k.d_res + rec_at);
-  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
-  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), wg(LAKE_LANES);
-  ok = hipMemcpyAsync(k.d_tab, k.h_tab, 2 * (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, bare, p.T, (LakeAcc*)nullptr);
-    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, bare, p.T);
-    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, bare, p.T);
-    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, bare, p.T, p.R, (BasinAcc*)nullptr);
-    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, bare, p.T);
-    hipLaunchKernelGGL(k_drain_pending, gf, wg, 0, st, bare, p.R, p.P, p.AR);
-    hipLaunchKernelGGL(k_drain_area, gf, wg, 0, st, bare, p.R, p.P, p.AR);
-    hipLaunchKernelGGL(k_stream_mark, gf, wg, 0, st, bare, threshold, p);
-    hipLaunchKernelGGL(k_stream_order, gf, wg, 0, st, bare, threshold, p);
-    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), StreamMarkFn{p.D});
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, in, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_stream_segments, gf, wg, 0, st, k.d_tab, segments ? 1 : 0, p, recs, d_n);
-  }
-  ok = ok && hipGetLastError() == hipSuccess;
-  ok = ok && hipMemcpyAsync(k.h_res, k.d_res, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  // (smx_streams only: one map, off = 0, so a plane index is a cell index)
-  if (ok && order) ok = hipMemcpyAsync(order, p.O, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && segments) ok = hipMemcpyAsync(segments, p.SG, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && reach) ok = hipMemcpyAsync(reach, p.RE, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && heads) ok = hipMemcpyAsync(heads, p.H, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  const hipError_t se = hipStreamSynchronize(st);
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the stream network failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
-  const char* a = k.h_res + rec_at;
-  const size_t take = struct_size < sizeof(smx_segment) ? (size_t)struct_size : sizeof(smx_segment);
-  for (uint32_t i = 0; i < nm; i++) {
-    nstreams[i] = n[i];
-    const uint32_t w = std::min(n[i], tab[i].cap);
-    for (uint32_t r = 0; r < w; r++)
-      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, a + ((size_t)tab[i].rec0 + r) * sizeof(StreamRec), take);
-  }
-  return 0;
-}
-
 int smx_streams(smx_ctx* ctx, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap, uint32_t* nstreams, uint32_t* order, uint32_t* segments,
                 uint32_t* reach, uint32_t* heads) {
   if (!ctx) return -2;
-  FULLMAP("smx_streams")
-  if (struct_size == 0) { ctx->err = "smx_streams: struct_size is 0 (pass sizeof(smx_segment) of the header you compiled against)"; return -2; }
-  if (threshold == 0) { ctx->err = "smx_streams: threshold is 0 (a channel cell has an area of at least threshold >= 1)"; return -2; }
-  if (!nstreams) { ctx->err = "smx_streams: nstreams is null"; return -2; }
-  if (!out && cap) { ctx->err = "smx_streams: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
-  if (!ctx->stream) { ctx->err = "smx_streams: a context without a device"; return -3; }
+  const AnalysisCall c = call_on("smx_streams", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_segment", "nstreams", struct_size, &threshold, nstreams, out, cap, rc)) return rc;
   roctx_range rr("soilmx:streams");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return streams_run("smx_streams", ctx->streams, ctx->mem, ctx->stream, &ctx, 1u, threshold, out, struct_size, cap, nstreams, order, segments, reach, heads, ctx->err);
+  return streams_run(c, ctx->streams, threshold, out, struct_size, cap, nstreams, order, segments, reach, heads);
 }
 int smx_ensemble_streams(smx_ensemble* e, uint32_t threshold, smx_segment* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nstreams) {
   if (!e) return -2;
-  if (!e->stream) { e->err = "smx_ensemble_streams: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
-  if (struct_size == 0) { e->err = "smx_ensemble_streams: struct_size is 0 (pass sizeof(smx_segment) of the header you compiled against)"; return -2; }
-  if (threshold == 0) { e->err = "smx_ensemble_streams: threshold is 0 (a channel cell has an area of at least threshold >= 1)"; return -2; }
-  const uint32_t nm = (uint32_t)e->members.size();
-  if (nm == 0) return 0;
-  if (!nstreams) { e->err = "smx_ensemble_streams: nstreams is null (one count per member)"; return -2; }
-  if (!out && cap_per_member) { e->err = "smx_ensemble_streams: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_streams", e);
+  int rc;
+  if (!analysis_begin(c, "smx_segment", "nstreams", struct_size, &threshold, nstreams, out, cap_per_member, rc)) return rc;
   roctx_range rr("soilmx:ensemble_streams");
   HIPCHK(e, hipSetDevice(e->device));
-  return streams_run("smx_ensemble_streams", e->streams, e->mem, e->stream, e->members.data(), nm, threshold, out, struct_size, cap_per_member, nstreams, nullptr, nullptr,
-                     nullptr, nullptr, e->err);
+  return streams_run(c, e->streams, threshold, out, struct_size, cap_per_member, nstreams, nullptr, nullptr, nullptr, nullptr);
 }
-
-// ---------------- spill analysis (smx_spill / smx_ensemble_spill; kernels: soil_spill.h, soil_drain.h and the census's) ----------------
-// One path for both calls, on a scratch of its own. The drainage chain through k_drain_stats with no records (the tables' cap is 0:
-// T becomes the rank plane), the counts back: the FIRST synchronisation -- the basins' table is sized by them. Then k_spill_init,
-// k_spill_pass<0>, k_spill_pass<1>, rocPRIM's exclusive scan of the boundary marks, k_spill_list, k_spill_point; k_spill_relax in
-// batches of SPILL_BATCH sweeps, the change counts read once per batch (one synchronisation each) until a sweep changed nothing;
-// k_spill_store; the table and the plane back, the last synchronisation. smx_drainage's, smx_streams' and smx_lakes' scratch and
-// results are not touched.
-static_assert(sizeof(smx_spill_record) == 64 && sizeof(SpillRec) == sizeof(smx_spill_record) && offsetof(smx_spill_record, pour_height) == offsetof(SpillRec, pour_height) &&
-              offsetof(smx_spill_record, storage_q40) == offsetof(SpillRec, storage_q40) && offsetof(smx_spill_record, flags) == offsetof(SpillRec, flags), "smx_spill_record layout");
-static void spill_drop(SpillScratch& k, DevMem& mem) {
-  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.Q); mem.drop(k.H); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt);
-  mem.drop(k.d_acc); mem.drop(k.h_acc);
-  k = SpillScratch();
-}
-static int spill_run(const char* who, SpillScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_spill_record* out, uint64_t struct_size,
-                     uint32_t cap, uint32_t* nbasins, double* filled, std::string& err) {
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0;
-  size_t tiles = 1, flat = 1, stat = 1;
-  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
-  k.sweeps = 0; k.batches = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    const smx_ctx* c = ms[i];
-    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
-    LakeMember& m = tab[i];
-    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
-    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;   // (the drainage chain touches no record)
-    words += (uint64_t)c->ncells;
-    if (words > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells in one call"; return -2; }
-    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
-    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
-    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
-  }
-  const size_t cnt_words = (((size_t)nm + 15) & ~(size_t)15) + 16;   // the counts, then SPILL_BATCH change counts
-  static_assert(SPILL_BATCH <= 16, "the change counts' room");
-  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
-  size_t tb = 0, tb2 = 0;
-  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess &&
-            rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)k.R, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-  tb = std::max<size_t>(std::max(tb, tb2), 8);   // (a null temporary storage would make the scan a size query again)
-  auto oom = [&](uint64_t nrec) {
-    (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
-    spill_drop(k, mem);
-    err = std::string(who) + ": out of memory for the spill scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " basins)";
-    return -1;
-  };
-  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap)) {
-    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
-    if (ok && words > k.words) {
-      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.Q); mem.drop(k.H); k.words = 0;
-      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess &&
-           mem.dev(k.Q, (size_t)words) == hipSuccess && mem.dev(k.H, (size_t)words) == hipSuccess;
-      if (ok) k.words = (size_t)words;
-    }
-    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
-    if (ok && nm > k.tab_cap) {
-      mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt); k.tab_cap = 0;
-      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess && mem.dev(k.d_cnt, cnt_words) == hipSuccess &&
-           mem.pinned(k.h_cnt, cnt_words) == hipSuccess;
-      if (ok) k.tab_cap = nm;
-    }
-    if (!ok) return oom(0);
-  }
-  if (!ok) { err = std::string(who) + ": sizing the prefix sums failed"; return -1; }
-  const SpillPlanes p{k.T, k.B, k.R, k.Q, k.H};
-  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), gs((unsigned)stat, nm), wg(LAKE_LANES);
-  uint32_t* d_n = k.d_cnt;
-  uint32_t* d_chg = k.d_cnt + (cnt_words - 16);
-  const uint32_t* h_chg = k.h_cnt + (cnt_words - 16);
-  // the bare table (no records) for the drainage chain; behind it, once the counts are known, the table with the basins
-  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
-  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, k.d_tab, p.T, (LakeAcc*)nullptr);
-    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, k.d_tab, p.T);
-    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, k.d_tab, p.T);
-    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, k.d_tab, p.T, p.R, (BasinAcc*)nullptr);
-    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, k.d_tab, p.T);
-    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{p.T});
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, in, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_drain_stats, gs, wg, 0, st, k.d_tab, p.T, p.B, (BasinAcc*)nullptr, d_n);
-  }
-  ok = ok && hipGetLastError() == hipSuccess;
-  ok = ok && hipMemcpyAsync(k.h_cnt, d_n, (size_t)nm * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  hipError_t se = hipStreamSynchronize(st);
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the drainage chain failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  uint64_t nrec = 0;
-  uint32_t most = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    tab[i].cap = k.h_cnt[i]; tab[i].rec0 = (uint32_t)nrec;
-    nrec += tab[i].cap; most = std::max(most, tab[i].cap);
-  }
-  if (nrec > k.acc_cap) {   // (the stream is idle)
-    mem.drop(k.d_acc); mem.drop(k.h_acc); k.acc_cap = 0;
-    if (mem.dev(k.d_acc, (size_t)nrec) != hipSuccess || mem.pinned(k.h_acc, (size_t)nrec) != hipSuccess) return oom(nrec);
-    k.acc_cap = (size_t)nrec;
-  }
-  const LakeMember* full = k.d_tab + nm;
-  const dim3 gb((unsigned)(((size_t)most + LAKE_LANES - 1) / LAKE_LANES), nm), gr((unsigned)std::min<size_t>(flat, SPILL_RELAX_BLOCKS), nm);
-  memcpy(k.h_tab + nm, tab.data(), (size_t)nm * sizeof(LakeMember));
-  ok = hipMemcpyAsync(k.d_tab + nm, k.h_tab + nm, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_spill_init, gb, wg, 0, st, full, k.d_acc);
-    hipLaunchKernelGGL(k_spill_pass<0>, gt, wg, 0, st, full, p, k.d_acc);
-    hipLaunchKernelGGL(k_spill_pass<1>, gt, wg, 0, st, full, p, k.d_acc);
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, (const uint32_t*)p.R, p.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_spill_list, gf, wg, 0, st, full, p);
-    hipLaunchKernelGGL(k_spill_point, gb, wg, 0, st, full, p, k.d_acc);
-  }
-  // the sweeps: their number depends on the map, so this is where the call looks at the device more than once
-  for (bool done = false; ok && !done;) {
-    if ((uint64_t)k.sweeps >= (uint64_t)most + 2u) {   // (each sweep but the last settles a basin at least: cannot happen)
-      (void)hipStreamSynchronize(st);
-      err = std::string(who) + ": the fill levels did not settle within " + std::to_string(k.sweeps) + " sweeps (" + std::to_string(most) + " basins)";
-      return -1;
-    }
-    ok = hipMemsetAsync(d_chg, 0, 16 * 4, st) == hipSuccess;
-    for (uint32_t j = 0; ok && j < SPILL_BATCH; j++) hipLaunchKernelGGL(k_spill_relax, gr, wg, 0, st, full, k.sweeps + j + 1u, p, k.d_acc, d_chg + j);
-    ok = ok && hipGetLastError() == hipSuccess;
-    ok = ok && hipMemcpyAsync(k.h_cnt + (cnt_words - 16), d_chg, 16 * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-    se = hipStreamSynchronize(st);
-    if (!ok || se != hipSuccess) break;
-    k.sweeps += SPILL_BATCH; k.batches++;
-    for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || h_chg[j] == 0u;
-  }
-  if (ok && se == hipSuccess) {
-    hipLaunchKernelGGL(k_spill_store, gs, wg, 0, st, full, p, k.d_acc, filled ? 1 : 0);
-    ok = hipGetLastError() == hipSuccess;
-    ok = ok && hipMemcpyAsync(k.h_acc, k.d_acc, (size_t)nrec * sizeof(SpillAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
-    // (smx_spill only: one map, off = 0)
-    if (ok && filled) ok = hipMemcpyAsync(filled, p.H, (size_t)words * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-    se = hipStreamSynchronize(st);
-  }
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the spill analysis failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  const size_t take = struct_size < sizeof(smx_spill_record) ? (size_t)struct_size : sizeof(smx_spill_record);
-  for (uint32_t i = 0; i < nm; i++) {
-    nbasins[i] = tab[i].cap;
-    const uint32_t w = std::min(tab[i].cap, cap);
-    for (uint32_t r = 0; r < w; r++) {
-      SpillRec rec;
-      spill_finish(k.h_acc[tab[i].rec0 + r], rec);
-      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
-    }
-  }
-  return 0;
-}
-
 int smx_spill(smx_ctx* ctx, smx_spill_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, double* filled) {
   if (!ctx) return -2;
-  FULLMAP("smx_spill")
-  if (struct_size == 0) { ctx->err = "smx_spill: struct_size is 0 (pass sizeof(smx_spill_record) of the header you compiled against)"; return -2; }
-  if (!nbasins) { ctx->err = "smx_spill: nbasins is null"; return -2; }
-  if (!out && cap) { ctx->err = "smx_spill: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
-  if (!ctx->stream) { ctx->err = "smx_spill: a context without a device"; return -3; }
+  const AnalysisCall c = call_on("smx_spill", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_spill_record", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
   roctx_range rr("soilmx:spill");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return spill_run("smx_spill", ctx->spill, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, filled, ctx->err);
+  return spill_run(c, ctx->spill, out, struct_size, cap, nbasins, filled);
 }
 int smx_ensemble_spill(smx_ensemble* e, smx_spill_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
   if (!e) return -2;
-  if (!e->stream) { e->err = "smx_ensemble_spill: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
-  if (struct_size == 0) { e->err = "smx_ensemble_spill: struct_size is 0 (pass sizeof(smx_spill_record) of the header you compiled against)"; return -2; }
-  const uint32_t nm = (uint32_t)e->members.size();
-  if (nm == 0) return 0;
-  if (!nbasins) { e->err = "smx_ensemble_spill: nbasins is null (one count per member)"; return -2; }
-  if (!out && cap_per_member) { e->err = "smx_ensemble_spill: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_spill", e);
+  int rc;
+  if (!analysis_begin(c, "smx_spill_record", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
   roctx_range rr("soilmx:ensemble_spill");
   HIPCHK(e, hipSetDevice(e->device));
-  return spill_run("smx_ensemble_spill", e->spill, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, e->err);
+  return spill_run(c, e->spill, out, struct_size, cap_per_member, nbasins, nullptr);
 }
-int smx_get_spill_sweeps(smx_ctx* ctx, uint32_t* sweeps, uint32_t* batches) {
-  if (!ctx) return -2;
-  if (!sweeps || !batches) { ctx->err = "smx_get_spill_sweeps: a null argument"; return -2; }
-  *sweeps = ctx->spill.sweeps; *batches = ctx->spill.batches;
-  return 0;
-}
-int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* batches) {
-  if (!e) return -2;
-  if (!sweeps || !batches) { e->err = "smx_ensemble_get_spill_sweeps: a null argument"; return -2; }
-  *sweeps = e->spill.sweeps; *batches = e->spill.batches;
-  return 0;
-}
-
-// ---------------- through-drainage (smx_through / smx_ensemble_through; kernels: soil_through.h, soil_spill.h, soil_drain.h and the census's) ----------------
-// One path for both calls, shaped as spill_run, on a scratch of its own. The drainage chain through k_drain_stats with no records,
-// the counts back: the FIRST synchronisation. Then k_spill_init, k_through_init, k_spill_pass<0>, k_spill_pass<1> (their boundary
-// marks go to M: R stays the receivers), the scan, k_spill_list, k_spill_point, k_through_count; k_spill_relax in batches until a
-// sweep changed nothing, k_through_hops likewise (one synchronisation per batch); k_through_exit; k_drain_pending where the area is
-// asked for (P takes M's plane and AR takes Q's: the marks and the list are done with); k_through_link<0>, <1>,
-// k_through_accumulate, k_through_outlet, k_through_plane and k_through_area where their planes are asked for; the tables and the
-// planes back, the last synchronisation. The scratch and the results of the sibling calls are not touched.
-static_assert(sizeof(smx_through_record) == 64 && sizeof(ThroughRec) == sizeof(smx_through_record) && offsetof(smx_through_record, exit_height) == offsetof(ThroughRec, exit_height) &&
-              offsetof(smx_through_record, hops) == offsetof(ThroughRec, hops) && offsetof(smx_through_record, through_cells) == offsetof(ThroughRec, through_cells), "smx_through_record layout");
-static void through_drop(ThroughScratch& k, DevMem& mem) {
-  mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.M); mem.drop(k.Q); mem.drop(k.H); mem.drop(k.temp); mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt);
-  mem.drop(k.h_cnt); mem.drop(k.d_sacc); mem.drop(k.h_sacc); mem.drop(k.d_acc); mem.drop(k.h_acc);
-  k = ThroughScratch();
-}
-static int through_run(const char* who, ThroughScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, smx_through_record* out, uint64_t struct_size,
-                       uint32_t cap, uint32_t* nbasins, uint32_t* through_area, uint32_t* outlets, std::string& err) {
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0;
-  size_t tiles = 1, flat = 1, stat = 1;
-  const size_t per = lake_stats_cells(LAKE_SLOTS, LAKE_LANES);
-  k.level_sweeps = 0; k.hop_sweeps = 0; k.batches = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    const smx_ctx* c = ms[i];
-    if (c->cfg.dimx > 65536 || c->cfg.dimy > 65536) { err = std::string(who) + ": a map of more than 65536 cells a side"; return -2; }
-    LakeMember& m = tab[i];
-    m.cells = c->d.cells; m.dimx = c->cfg.dimx; m.dimy = c->cfg.dimy; m.pad = 0u;
-    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;   // (the drainage chain touches no record)
-    words += (uint64_t)c->ncells;
-    if (words > 0xFFFFFFFEull) { err = std::string(who) + ": more than 2^32 - 2 cells in one call"; return -2; }
-    tiles = std::max<size_t>(tiles, lake_tiles(m, LAKE_TX, LAKE_TY));
-    flat = std::max<size_t>(flat, (c->ncells + LAKE_LANES - 1) / LAKE_LANES);
-    stat = std::max<size_t>(stat, (c->ncells + per - 1) / per);
-  }
-  const size_t cnt_words = (((size_t)nm + 15) & ~(size_t)15) + 16;   // the counts, then SPILL_BATCH change counts
-  const auto marks = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
-  size_t tb = 0, tb2 = 0;
-  bool ok = rocprim::exclusive_scan(nullptr, tb, marks, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess &&
-            rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)k.M, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-  tb = std::max<size_t>(std::max(tb, tb2), 8);   // (a null temporary storage would make the scan a size query again)
-  auto oom = [&](uint64_t nrec) {
-    (void)hipGetLastError();   // nothing half-sized stays behind, and the failure does not surface in the next launch check
-    through_drop(k, mem);
-    err = std::string(who) + ": out of memory for the through-drainage scratch (" + std::to_string(words) + " cells, " + std::to_string(nrec) + " basins)";
-    return -1;
-  };
-  if (ok && (words > k.words || tb > k.temp_bytes || nm > k.tab_cap)) {
-    ok = hipStreamSynchronize(st) == hipSuccess;   // (nothing queued still uses what is dropped)
-    if (ok && words > k.words) {
-      mem.drop(k.T); mem.drop(k.B); mem.drop(k.R); mem.drop(k.M); mem.drop(k.Q); mem.drop(k.H); k.words = 0;
-      ok = mem.dev(k.T, (size_t)words) == hipSuccess && mem.dev(k.B, (size_t)words) == hipSuccess && mem.dev(k.R, (size_t)words) == hipSuccess &&
-           mem.dev(k.M, (size_t)words) == hipSuccess && mem.dev(k.Q, (size_t)words) == hipSuccess && mem.dev(k.H, (size_t)words) == hipSuccess;
-      if (ok) k.words = (size_t)words;
-    }
-    ok = ok && mem.grow(k.temp, k.temp_bytes, tb, tb) == hipSuccess;
-    if (ok && nm > k.tab_cap) {
-      mem.drop(k.d_tab); mem.drop(k.h_tab); mem.drop(k.d_cnt); mem.drop(k.h_cnt); k.tab_cap = 0;
-      ok = mem.dev(k.d_tab, 2 * (size_t)nm) == hipSuccess && mem.pinned(k.h_tab, 2 * (size_t)nm) == hipSuccess && mem.dev(k.d_cnt, cnt_words) == hipSuccess &&
-           mem.pinned(k.h_cnt, cnt_words) == hipSuccess;
-      if (ok) k.tab_cap = nm;
-    }
-    if (!ok) return oom(0);
-  }
-  if (!ok) { err = std::string(who) + ": sizing the prefix sums failed"; return -1; }
-  const SpillPlanes sp{k.T, k.B, k.M, k.Q, k.H};     // what the spill chain's kernels see: their R is M
-  const ThroughPlanes p{k.T, k.B, k.M, k.Q, k.H};
-  uint32_t* const P = k.M;                           // behind k_through_exit
-  uint32_t* const AR = through_area ? k.Q : nullptr;
-  const dim3 gt((unsigned)tiles, nm), gf((unsigned)flat, nm), gs((unsigned)stat, nm), wg(LAKE_LANES);
-  uint32_t* d_n = k.d_cnt;
-  uint32_t* d_chg = k.d_cnt + (cnt_words - 16);
-  const uint32_t* h_chg = k.h_cnt + (cnt_words - 16);
-  memcpy(k.h_tab, tab.data(), (size_t)nm * sizeof(LakeMember));
-  ok = hipMemcpyAsync(k.d_tab, k.h_tab, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_lake_tiles, gt, wg, 0, st, k.d_tab, k.T, (LakeAcc*)nullptr);
-    hipLaunchKernelGGL(k_lake_merge, gt, wg, 0, st, k.d_tab, k.T);
-    hipLaunchKernelGGL(k_lake_flatten, gf, wg, 0, st, k.d_tab, k.T);
-    hipLaunchKernelGGL(k_drain_recv, gt, wg, 0, st, k.d_tab, k.T, k.R, (BasinAcc*)nullptr);
-    hipLaunchKernelGGL(k_drain_resolve, gf, wg, 0, st, k.d_tab, k.T);
-    const auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LakeMarkFn{k.T});
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, in, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_drain_stats, gs, wg, 0, st, k.d_tab, k.T, k.B, (BasinAcc*)nullptr, d_n);
-  }
-  ok = ok && hipGetLastError() == hipSuccess;
-  ok = ok && hipMemcpyAsync(k.h_cnt, d_n, (size_t)nm * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-  hipError_t se = hipStreamSynchronize(st);
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the drainage chain failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  uint64_t nrec = 0;
-  uint32_t most = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    tab[i].cap = k.h_cnt[i]; tab[i].rec0 = (uint32_t)nrec;
-    nrec += tab[i].cap; most = std::max(most, tab[i].cap);
-  }
-  if (nrec > k.acc_cap) {   // (the stream is idle)
-    mem.drop(k.d_sacc); mem.drop(k.h_sacc); mem.drop(k.d_acc); mem.drop(k.h_acc); k.acc_cap = 0;
-    if (mem.dev(k.d_sacc, (size_t)nrec) != hipSuccess || mem.pinned(k.h_sacc, (size_t)nrec) != hipSuccess || mem.dev(k.d_acc, (size_t)nrec) != hipSuccess ||
-        mem.pinned(k.h_acc, (size_t)nrec) != hipSuccess)
-      return oom(nrec);
-    k.acc_cap = (size_t)nrec;
-  }
-  const LakeMember* full = k.d_tab + nm;
-  const dim3 gb((unsigned)(((size_t)most + LAKE_LANES - 1) / LAKE_LANES), nm), gr((unsigned)std::min<size_t>(flat, SPILL_RELAX_BLOCKS), nm);
-  memcpy(k.h_tab + nm, tab.data(), (size_t)nm * sizeof(LakeMember));
-  ok = hipMemcpyAsync(k.d_tab + nm, k.h_tab + nm, (size_t)nm * sizeof(LakeMember), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_spill_init, gb, wg, 0, st, full, k.d_sacc);
-    hipLaunchKernelGGL(k_through_init, gb, wg, 0, st, full, k.d_acc);
-    hipLaunchKernelGGL(k_spill_pass<0>, gt, wg, 0, st, full, sp, k.d_sacc);
-    hipLaunchKernelGGL(k_spill_pass<1>, gt, wg, 0, st, full, sp, k.d_sacc);
-    size_t need = k.temp_bytes;
-    ok = rocprim::exclusive_scan(k.temp, need, (const uint32_t*)k.M, k.B, 0u, (size_t)words, rocprim::plus<uint32_t>(), st) == hipSuccess;
-    hipLaunchKernelGGL(k_spill_list, gf, wg, 0, st, full, sp);
-    hipLaunchKernelGGL(k_spill_point, gb, wg, 0, st, full, sp, k.d_sacc);
-    hipLaunchKernelGGL(k_through_count, gs, wg, 0, st, full, k.T, k.d_acc);
-  }
-  // the sweeps, the fill levels first and the hop counts behind them: the host loop of spill_run, twice
-  for (int what = 0; what < 2 && ok && se == hipSuccess; what++) {
-    uint32_t& sweeps = what ? k.hop_sweeps : k.level_sweeps;
-    for (bool done = false; ok && !done;) {
-      if ((uint64_t)sweeps >= (uint64_t)most + 2u) {   // (each sweep but the last settles a basin at least: cannot happen)
-        (void)hipStreamSynchronize(st);
-        err = std::string(who) + ": the " + (what ? "hop counts" : "fill levels") + " did not settle within " + std::to_string(sweeps) + " sweeps (" + std::to_string(most) + " basins)";
-        return -1;
-      }
-      ok = hipMemsetAsync(d_chg, 0, 16 * 4, st) == hipSuccess;
-      for (uint32_t j = 0; ok && j < SPILL_BATCH; j++) {
-        if (what) hipLaunchKernelGGL(k_through_hops, gr, wg, 0, st, full, p, k.d_sacc, k.d_acc, d_chg + j);
-        else hipLaunchKernelGGL(k_spill_relax, gr, wg, 0, st, full, sweeps + j + 1u, sp, k.d_sacc, d_chg + j);
-      }
-      ok = ok && hipGetLastError() == hipSuccess;
-      ok = ok && hipMemcpyAsync(k.h_cnt + (cnt_words - 16), d_chg, 16 * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-      se = hipStreamSynchronize(st);
-      if (!ok || se != hipSuccess) break;
-      sweeps += SPILL_BATCH; k.batches++;
-      for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || h_chg[j] == 0u;
-    }
-  }
-  if (ok && se == hipSuccess) {
-    hipLaunchKernelGGL(k_through_exit, gr, wg, 0, st, full, p, k.d_sacc, k.d_acc);
-    if (AR) hipLaunchKernelGGL(k_drain_pending, gf, wg, 0, st, full, k.R, P, AR);
-    hipLaunchKernelGGL(k_through_link<0>, gb, wg, 0, st, full, p, k.d_sacc, k.d_acc);
-    hipLaunchKernelGGL(k_through_link<1>, gb, wg, 0, st, full, p, k.d_sacc, k.d_acc);
-    hipLaunchKernelGGL(k_through_accumulate, gb, wg, 0, st, full, k.d_acc, AR);
-    hipLaunchKernelGGL(k_through_outlet, gb, wg, 0, st, full, k.d_sacc, k.d_acc);
-    if (outlets) hipLaunchKernelGGL(k_through_plane, gf, wg, 0, st, full, k.T, k.d_acc, k.B);   // (B is done with)
-    if (AR) hipLaunchKernelGGL(k_through_area, gf, wg, 0, st, full, k.R, P, AR);
-    ok = hipGetLastError() == hipSuccess;
-    ok = ok && hipMemcpyAsync(k.h_sacc, k.d_sacc, (size_t)nrec * sizeof(SpillAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
-    ok = ok && hipMemcpyAsync(k.h_acc, k.d_acc, (size_t)nrec * sizeof(ThroughAcc), hipMemcpyDeviceToHost, st) == hipSuccess;
-    // (smx_through only: one map, off = 0)
-    if (ok && through_area) ok = hipMemcpyAsync(through_area, AR, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (ok && outlets) ok = hipMemcpyAsync(outlets, k.B, (size_t)words * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-    se = hipStreamSynchronize(st);
-  }
-  if (!ok || se != hipSuccess) { err = std::string(who) + ": the through-drainage failed on the device (" + hipGetErrorString(se != hipSuccess ? se : hipGetLastError()) + ")"; return -1; }
-  const size_t take = struct_size < sizeof(smx_through_record) ? (size_t)struct_size : sizeof(smx_through_record);
-  for (uint32_t i = 0; i < nm; i++) {
-    nbasins[i] = tab[i].cap;
-    const uint32_t w = std::min(tab[i].cap, cap);
-    for (uint32_t r = 0; r < w; r++) {
-      ThroughRec rec;
-      through_finish(k.h_sacc[tab[i].rec0 + r], k.h_acc[tab[i].rec0 + r], rec);
-      memcpy(reinterpret_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, take);
-    }
-  }
-  return 0;
-}
-
 int smx_through(smx_ctx* ctx, smx_through_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* through_area, uint32_t* outlets) {
   if (!ctx) return -2;
-  FULLMAP("smx_through")
-  if (struct_size == 0) { ctx->err = "smx_through: struct_size is 0 (pass sizeof(smx_through_record) of the header you compiled against)"; return -2; }
-  if (!nbasins) { ctx->err = "smx_through: nbasins is null"; return -2; }
-  if (!out && cap) { ctx->err = "smx_through: out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)"; return -2; }
-  if (!ctx->stream) { ctx->err = "smx_through: a context without a device"; return -3; }
+  const AnalysisCall c = call_on("smx_through", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_through_record", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
   roctx_range rr("soilmx:through");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return through_run("smx_through", ctx->through, ctx->mem, ctx->stream, &ctx, 1u, out, struct_size, cap, nbasins, through_area, outlets, ctx->err);
+  return through_run(c, ctx->through, out, struct_size, cap, nbasins, through_area, outlets);
 }
 int smx_ensemble_through(smx_ensemble* e, smx_through_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
   if (!e) return -2;
-  if (!e->stream) { e->err = "smx_ensemble_through: the ensemble has no device (smx_ensemble_create failed)"; return -3; }
-  if (struct_size == 0) { e->err = "smx_ensemble_through: struct_size is 0 (pass sizeof(smx_through_record) of the header you compiled against)"; return -2; }
-  const uint32_t nm = (uint32_t)e->members.size();
-  if (nm == 0) return 0;
-  if (!nbasins) { e->err = "smx_ensemble_through: nbasins is null (one count per member)"; return -2; }
-  if (!out && cap_per_member) { e->err = "smx_ensemble_through: out is null while cap_per_member is " + std::to_string(cap_per_member); return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_through", e);
+  int rc;
+  if (!analysis_begin(c, "smx_through_record", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
   roctx_range rr("soilmx:ensemble_through");
   HIPCHK(e, hipSetDevice(e->device));
-  return through_run("smx_ensemble_through", e->through, e->mem, e->stream, e->members.data(), nm, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, e->err);
+  return through_run(c, e->through, out, struct_size, cap_per_member, nbasins, nullptr, nullptr);
+}
+// (sweeps launched, batches) of the last spill call; (level sweeps, hop sweeps, batches) of the last through call
+static int sweeps_of(const AnalysisScratch& k, std::string& err, const char* who, uint32_t* a, uint32_t* b, uint32_t* batches) {
+  if (!a || !b || !batches) { err = std::string(who) + ": a null argument"; return -2; }
+  *a = k.sweeps[0]; *b = k.sweeps[1]; *batches = k.batches;
+  return 0;
+}
+int smx_get_spill_sweeps(smx_ctx* ctx, uint32_t* sweeps, uint32_t* batches) {
+  uint32_t none;
+  return ctx ? sweeps_of(ctx->spill, ctx->err, "smx_get_spill_sweeps", sweeps, &none, batches) : -2;
+}
+int smx_ensemble_get_spill_sweeps(smx_ensemble* e, uint32_t* sweeps, uint32_t* batches) {
+  uint32_t none;
+  return e ? sweeps_of(e->spill, e->err, "smx_ensemble_get_spill_sweeps", sweeps, &none, batches) : -2;
 }
 int smx_get_through_sweeps(smx_ctx* ctx, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches) {
-  if (!ctx) return -2;
-  if (!level_sweeps || !hop_sweeps || !batches) { ctx->err = "smx_get_through_sweeps: a null argument"; return -2; }
-  *level_sweeps = ctx->through.level_sweeps; *hop_sweeps = ctx->through.hop_sweeps; *batches = ctx->through.batches;
-  return 0;
+  return ctx ? sweeps_of(ctx->through, ctx->err, "smx_get_through_sweeps", level_sweeps, hop_sweeps, batches) : -2;
 }
 int smx_ensemble_get_through_sweeps(smx_ensemble* e, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches) {
-  if (!e) return -2;
-  if (!level_sweeps || !hop_sweeps || !batches) { e->err = "smx_ensemble_get_through_sweeps: a null argument"; return -2; }
-  *level_sweeps = e->through.level_sweeps; *hop_sweeps = e->through.hop_sweeps; *batches = e->through.batches;
-  return 0;
+  return e ? sweeps_of(e->through, e->err, "smx_ensemble_get_through_sweeps", level_sweeps, hop_sweeps, batches) : -2;
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------

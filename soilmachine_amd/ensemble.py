@@ -230,22 +230,31 @@ class Ensemble:
                                                   capi.ptr(out.get("vmin")), capi.ptr(out.get("vmax")), capi.ptr(out.get("nonzero"))))
         return out
 
-    def lakes(self, cap: int | None = None) -> list:
-        """The lake census of every member (``smx_ensemble_lakes``: the same launches whatever the member count): one list of lake
-        dicts per member, in member order, each as ``Layermap.lakes()`` gives it. ``cap`` None: two calls, a count with no records
-        and the fetch sized by the largest count; else at most ``cap`` lakes per member. Members may differ in size."""
+    def _analysis(self, call, rec, cap, count=None):
+        """What the five terrain analyses share: the count call where ``cap`` is None (``count``, or ``call`` with no records), the
+        array sized by the largest count, the fetch ``call(out, cap, counts)`` and one list of dicts per member."""
         self._check_members()
         n = len(self.members)
         if n == 0:
             return []
         counts = np.zeros(n, np.uint32)
         if cap is None:
-            self._chk(self.L.smx_ensemble_lakes(self.h, None, C.sizeof(capi.Lake), 0, capi.ptr(counts)))
+            self._chk(count(capi.ptr(counts)) if count else call(None, 0, capi.ptr(counts)))
             cap = int(counts.max())
         cap = int(cap)
-        out = (capi.Lake * max(1, n * cap))()
-        self._chk(self.L.smx_ensemble_lakes(self.h, out, C.sizeof(capi.Lake), cap, capi.ptr(counts)))
+        out = (rec * max(1, n * cap))()
+        self._chk(call(out, cap, capi.ptr(counts)))
         return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+
+    def _basin_counts(self, counts):
+        """``spill`` and ``through`` take their counts from the drainage call: record k is basin k of ``drainage()``."""
+        return self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, counts)
+
+    def lakes(self, cap: int | None = None) -> list:
+        """The lake census of every member (``smx_ensemble_lakes``: the same launches whatever the member count): one list of lake
+        dicts per member, in member order, each as ``Layermap.lakes()`` gives it. ``cap`` None: two calls, a count with no records
+        and the fetch sized by the largest count; else at most ``cap`` lakes per member. Members may differ in size."""
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_lakes(self.h, out, C.sizeof(capi.Lake), cap, counts), capi.Lake, cap)
 
     def lake_counts(self) -> list:
         """The number of lakes of every member (``smx_ensemble_lakes`` with no records)."""
@@ -258,18 +267,7 @@ class Ensemble:
         """The basins of every member (``smx_ensemble_drainage``: the same launches whatever the member count): one list of basin
         dicts per member, in member order, each as ``Layermap.drainage()`` gives it. ``cap`` None: two calls, a count with no records
         and the fetch sized by the largest count; else at most ``cap`` basins per member. Members may differ in size."""
-        self._check_members()
-        n = len(self.members)
-        if n == 0:
-            return []
-        counts = np.zeros(n, np.uint32)
-        if cap is None:
-            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
-            cap = int(counts.max())
-        cap = int(cap)
-        out = (capi.Basin * max(1, n * cap))()
-        self._chk(self.L.smx_ensemble_drainage(self.h, out, C.sizeof(capi.Basin), cap, capi.ptr(counts)))
-        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_drainage(self.h, out, C.sizeof(capi.Basin), cap, counts), capi.Basin, cap)
 
     def basin_counts(self) -> list:
         """The number of basins of every member (``smx_ensemble_drainage`` with no records)."""
@@ -282,36 +280,14 @@ class Ensemble:
         """The channel segments of every member (``smx_ensemble_streams``: the same launches whatever the member count): one list of
         segment dicts per member, in member order, each as ``Layermap.streams(threshold)`` gives it. ``cap`` None: two calls, a count
         with no records and the fetch sized by the largest count; else at most ``cap`` segments per member. Members may differ in size."""
-        self._check_members()
-        n = len(self.members)
-        if n == 0:
-            return []
         threshold = int(threshold)
-        counts = np.zeros(n, np.uint32)
-        if cap is None:
-            self._chk(self.L.smx_ensemble_streams(self.h, threshold, None, C.sizeof(capi.Stream), 0, capi.ptr(counts)))
-            cap = int(counts.max())
-        cap = int(cap)
-        out = (capi.Stream * max(1, n * cap))()
-        self._chk(self.L.smx_ensemble_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, capi.ptr(counts)))
-        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, counts), capi.Stream, cap)
 
     def spill(self, cap: int | None = None) -> list:
         """The spill records of every member (``smx_ensemble_spill``: the same launches whatever the member count): one list of
         dicts per member, in member order, each as ``Layermap.spill()`` gives it. ``cap`` None: two calls, the basin counts and the
         fetch sized by the largest; else at most ``cap`` basins per member. Members may differ in size."""
-        self._check_members()
-        n = len(self.members)
-        if n == 0:
-            return []
-        counts = np.zeros(n, np.uint32)
-        if cap is None:
-            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
-            cap = int(counts.max())
-        cap = int(cap)
-        out = (capi.Spill * max(1, n * cap))()
-        self._chk(self.L.smx_ensemble_spill(self.h, out, C.sizeof(capi.Spill), cap, capi.ptr(counts)))
-        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_spill(self.h, out, C.sizeof(capi.Spill), cap, counts), capi.Spill, cap, count=self._basin_counts)
 
     def spill_sweeps(self) -> tuple:
         """(sweeps launched, batches) of the last ``spill()`` (``smx_ensemble_get_spill_sweeps``)."""
@@ -323,18 +299,7 @@ class Ensemble:
         """The through-drainage records of every member (``smx_ensemble_through``: the same launches whatever the member count): one
         list of dicts per member, in member order, each as ``Layermap.through()`` gives it. ``cap`` None: two calls, the basin counts
         and the fetch sized by the largest; else at most ``cap`` basins per member. Members may differ in size."""
-        self._check_members()
-        n = len(self.members)
-        if n == 0:
-            return []
-        counts = np.zeros(n, np.uint32)
-        if cap is None:
-            self._chk(self.L.smx_ensemble_drainage(self.h, None, C.sizeof(capi.Basin), 0, capi.ptr(counts)))
-            cap = int(counts.max())
-        cap = int(cap)
-        out = (capi.Through * max(1, n * cap))()
-        self._chk(self.L.smx_ensemble_through(self.h, out, C.sizeof(capi.Through), cap, capi.ptr(counts)))
-        return [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(n)]
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_through(self.h, out, C.sizeof(capi.Through), cap, counts), capi.Through, cap, count=self._basin_counts)
 
     def through_sweeps(self) -> tuple:
         """(level sweeps, hop sweeps, batches) of the last ``through()`` (``smx_ensemble_get_through_sweeps``)."""

@@ -191,6 +191,24 @@ class Layermap:
         return {"sumh": sh.value, "nsec": int(ns.value), "typehash": f"{th.value:016x}",
                 "rand_calls": self.counters()["rand_calls"]}
 
+    def _analysis(self, call, rec, cap, planes, dtype=np.uint32, count=None):
+        """What the five terrain analyses share: the count call where ``cap`` is None (``count``, or ``call`` with no records and
+        no planes), the array sized by it, the fetch, the dicts -- and the (dimx, dimy) planes asked for, ``planes`` listing
+        (name, wanted) in the order of the plane arguments of ``call(out, cap, byref(n), *plane_pointers)``."""
+        n = C.c_uint32()
+        if cap is None:
+            self._chk(count(C.byref(n)) if count else call(None, 0, C.byref(n), *[None] * len(planes)))
+            cap = int(n.value)
+        cap = int(cap)
+        out = (rec * max(1, cap))()
+        got = {k: np.zeros(self.dimx * self.dimy, dtype) for k, want in planes if want}
+        self._chk(call(out, cap, C.byref(n), *[capi.ptr(got.get(k)) for k, _ in planes]))
+        return [out[k].as_dict() for k in range(min(cap, int(n.value)))], {k: v.reshape(self.dimx, self.dimy) for k, v in got.items()}
+
+    def _basin_count(self, n):
+        """``spill`` and ``through`` take their count from the drainage call: record k is basin k of ``drainage()``."""
+        return self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, n, None, None, None)
+
     def lakes(self, labels: bool = False, cap: int | None = None):
         """The lake census (``smx_lakes``): one dict per lake in rank order -- ``first_cell`` (the lake's smallest cell index
         x*dimy+y, its identity), ``cells``, ``volume_q40`` (the exact integer sum of floor(size * 2^40)) and ``volume`` (that as a
@@ -199,16 +217,8 @@ class Layermap:
         section Air -- connected through the eight neighbours. ``labels``: also the (dimx, dimy) uint32 plane of ranks, 0xFFFFFFFF
         for a dry cell. ``cap`` None: two calls, a count and the fetch; else at most ``cap`` lakes. Sees every tick queued before
         it and changes nothing."""
-        n = C.c_uint32()
-        if cap is None:
-            self._chk(self.L.smx_lakes(self.h, None, C.sizeof(capi.Lake), 0, C.byref(n), None))
-            cap = int(n.value)
-        cap = int(cap)
-        out = (capi.Lake * max(1, cap))()
-        plane = np.zeros(self.dimx * self.dimy, np.uint32) if labels else None
-        self._chk(self.L.smx_lakes(self.h, out, C.sizeof(capi.Lake), cap, C.byref(n), capi.ptr(plane)))
-        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
-        return (recs, plane.reshape(self.dimx, self.dimy)) if labels else recs
+        recs, planes = self._analysis(lambda out, cap, n, lab: self.L.smx_lakes(self.h, out, C.sizeof(capi.Lake), cap, n, lab), capi.Lake, cap, [("labels", labels)])
+        return (recs, planes["labels"]) if labels else recs
 
     def drainage(self, receivers: bool = False, labels: bool = False, area: bool = False, cap: int | None = None):
         """Where the water goes (``smx_drainage``): one dict per basin in rank order -- ``first_cell`` (the sink's cell index
@@ -220,17 +230,9 @@ class Layermap:
         0xFFFFFFFF for a sink and a wet cell), ``labels`` (the basin's rank) and ``area`` (1 + the areas of the cells draining into
         the cell). ``cap`` None: two calls, a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it and
         changes nothing."""
-        n = C.c_uint32()
-        if cap is None:
-            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
-            cap = int(n.value)
-        cap = int(cap)
-        out = (capi.Basin * max(1, cap))()
-        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, want in (("receivers", receivers), ("labels", labels), ("area", area)) if want}
-        self._chk(self.L.smx_drainage(self.h, out, C.sizeof(capi.Basin), cap, C.byref(n), capi.ptr(planes.get("receivers")), capi.ptr(planes.get("labels")),
-                                      capi.ptr(planes.get("area"))))
-        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
-        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_drainage(self.h, out, C.sizeof(capi.Basin), cap, n, *pl), capi.Basin, cap,
+                                      [("receivers", receivers), ("labels", labels), ("area", area)])
+        return (recs, planes) if planes else recs
 
     def streams(self, threshold: int, order: bool = False, segments: bool = False, reach: bool = False, heads: bool = False, cap: int | None = None):
         """The channel network (``smx_streams``): one dict per segment in rank order (ascending ``first_cell``) -- ``first_cell``,
@@ -243,18 +245,10 @@ class Layermap:
         (dimx, dimy) uint32 arrays: ``order``, ``reach`` (cells on the longest channel path down to the cell) and ``heads`` (0 off
         the channels) and ``segments`` (the segment's rank, 0xFFFFFFFF off the channels). ``cap`` None: two calls, a count and the
         fetch; else at most ``cap`` segments. Sees every tick queued before it and changes nothing."""
-        n = C.c_uint32()
         threshold = int(threshold)
-        if cap is None:
-            self._chk(self.L.smx_streams(self.h, threshold, None, C.sizeof(capi.Stream), 0, C.byref(n), None, None, None, None))
-            cap = int(n.value)
-        cap = int(cap)
-        out = (capi.Stream * max(1, cap))()
-        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, want in (("order", order), ("segments", segments), ("reach", reach), ("heads", heads)) if want}
-        self._chk(self.L.smx_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, C.byref(n), capi.ptr(planes.get("order")), capi.ptr(planes.get("segments")),
-                                     capi.ptr(planes.get("reach")), capi.ptr(planes.get("heads"))))
-        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
-        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, n, *pl), capi.Stream, cap,
+                                      [("order", order), ("segments", segments), ("reach", reach), ("heads", heads)])
+        return (recs, planes) if planes else recs
 
     def spill(self, filled: bool = False, cap: int | None = None):
         """Where the basins overflow (``smx_spill``): one dict per basin in rank order, record k for basin k of ``drainage()`` --
@@ -267,16 +261,9 @@ class Layermap:
         (those as floats). ``filled``: the result is ``(records, plane)``, the (dimx, dimy) float64 plane max(h, fill level of the
         cell's basin). ``cap`` None: two calls, a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it
         and changes nothing; the number of relax sweeps depends on the map (``spill_sweeps()``)."""
-        n = C.c_uint32()
-        if cap is None:
-            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
-            cap = int(n.value)
-        cap = int(cap)
-        out = (capi.Spill * max(1, cap))()
-        plane = np.zeros(self.dimx * self.dimy, np.float64) if filled else None
-        self._chk(self.L.smx_spill(self.h, out, C.sizeof(capi.Spill), cap, C.byref(n), capi.ptr(plane)))
-        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
-        return (recs, plane.reshape(self.dimx, self.dimy)) if filled else recs
+        recs, planes = self._analysis(lambda out, cap, n, pl: self.L.smx_spill(self.h, out, C.sizeof(capi.Spill), cap, n, pl), capi.Spill, cap, [("filled", filled)],
+                                      dtype=np.float64, count=self._basin_count)
+        return (recs, planes["filled"]) if filled else recs
 
     def spill_sweeps(self) -> tuple:
         """(sweeps launched, batches) of the last ``spill()`` (``smx_get_spill_sweeps``)."""
@@ -296,16 +283,9 @@ class Layermap:
         routed through the overflows) and ``outlets`` (the rank of the root the cell's basin leaves through). ``cap`` None: two calls,
         a count and the fetch; else at most ``cap`` basins. Sees every tick queued before it and changes nothing; the number of
         sweeps depends on the map (``through_sweeps()``)."""
-        n = C.c_uint32()
-        if cap is None:
-            self._chk(self.L.smx_drainage(self.h, None, C.sizeof(capi.Basin), 0, C.byref(n), None, None, None))
-            cap = int(n.value)
-        cap = int(cap)
-        out = (capi.Through * max(1, cap))()
-        planes = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, on in (("through_area", area), ("outlets", outlets)) if on}
-        self._chk(self.L.smx_through(self.h, out, C.sizeof(capi.Through), cap, C.byref(n), capi.ptr(planes.get("through_area")), capi.ptr(planes.get("outlets"))))
-        recs = [out[k].as_dict() for k in range(min(cap, int(n.value)))]
-        return (recs, {k: v.reshape(self.dimx, self.dimy) for k, v in planes.items()}) if planes else recs
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_through(self.h, out, C.sizeof(capi.Through), cap, n, *pl), capi.Through, cap,
+                                      [("through_area", area), ("outlets", outlets)], count=self._basin_count)
+        return (recs, planes) if planes else recs
 
     def through_sweeps(self) -> tuple:
         """(level sweeps, hop sweeps, batches) of the last ``through()`` (``smx_get_through_sweeps``)."""

@@ -43,10 +43,15 @@ hipError_t hipFree(void* p) { return release(p, false); }
 hipError_t hipHostFree(void* p) { return release(p, true); }
 
 #include "../../soilmachine_amd/csrc/soil_devmem.h"
+struct LakeMember { uint64_t w[4]; };   // a stand-in of soil_lakes.h's, of its size: the scratch only allocates tables of them
+#include "../../soilmachine_amd/csrc/soil_scratch.h"
+using AnalysisScratch = AnalysisScratchOf<LakeMember>;
 
-// slots 0 .. 7 hold uint32_t* (count = elements of 4 bytes), slots 8 .. 15 hold void* (count = bytes)
+// slots 0 .. 7 hold uint32_t* (count = elements of 4 bytes), slots 8 .. 15 hold void* (count = bytes); `a`: the scratch of one terrain
+// analysis on the same owner (as_*)
 struct Rig {
   uint32_t* w[8] = {}; void* v[8] = {}; uint32_t wcap[8] = {}; size_t vcap[8] = {};
+  AnalysisScratch a;
   DevMem* m = new DevMem();   // (declared last and deleted by hand: dm_delete measures what the destructor frees)
 };
 
@@ -58,6 +63,7 @@ uint64_t dm_live_bytes() { uint64_t b = 0; for (auto& kv : g_live) b += kv.secon
 uint64_t dm_wrong_free() { return g_wrong_free; }
 uint64_t dm_unknown_free() { return g_unknown_free; }
 uint64_t dm_calls() { return g_log.size(); }
+uint64_t dm_block_id(uint64_t p) { auto it = g_live.find((void*)(uintptr_t)p); return it == g_live.end() ? 0 : it->second.id; }   // (an address may come again, a serial number does not)
 void dm_call(uint64_t i, int* op, uint64_t* id, uint64_t* bytes, int* ok) { const Call& c = g_log[i]; *op = c.op; *id = c.id; *bytes = c.bytes; *ok = c.ok; }
 
 Rig* dm_new() { return new Rig(); }
@@ -85,5 +91,30 @@ int dm_swap_pair(Rig* r, int d, int h, uint64_t count) {
   r->m->drop(r->w[d]); r->m->drop(r->w[h]);
   r->w[d] = nd; r->w[h] = nh; r->wcap[d] = r->wcap[h] = (uint32_t)count;
   return 0;
+}
+
+// AnalysisScratch (soil_scratch.h) on the rig's owner. as_ptr: 0 .. 9 the u32 planes, 10 the f64 plane, 11 temp, 12 / 13 the device /
+// pinned tables, 14 / 15 the count words, 16 / 17 the result region. as_cap: 0 words, 1 more_words, 2 temp_bytes, 3 tab_cap, 4 res_cap.
+static AnalysisScratch::Need as_need(uint64_t words, int planes, int more, int f64, uint64_t temp_bytes, uint32_t members, uint64_t count_words, uint64_t res_bytes) {
+  AnalysisScratch::Need n;
+  n.words = words; n.planes = planes; n.more = more; n.f64 = f64 != 0; n.temp_bytes = temp_bytes; n.members = members; n.count_words = count_words; n.res_bytes = res_bytes;
+  return n;
+}
+int as_reserve(Rig* r, uint64_t words, int planes, int more, int f64, uint64_t temp_bytes, uint32_t members, uint64_t count_words, uint64_t res_bytes) {
+  return r->a.reserve(*r->m, as_need(words, planes, more, f64, temp_bytes, members, count_words, res_bytes));
+}
+int as_fits(Rig* r, uint64_t words, int planes, int more, int f64, uint64_t temp_bytes, uint32_t members, uint64_t count_words, uint64_t res_bytes) {
+  return r->a.fits(as_need(words, planes, more, f64, temp_bytes, members, count_words, res_bytes)) ? 1 : 0;
+}
+void as_drop(Rig* r) { r->a.drop(*r->m); }
+uint64_t as_ptr(Rig* r, int i) {
+  const AnalysisScratch& a = r->a;
+  const void* p[18] = {a.plane[0], a.plane[1], a.plane[2], a.plane[3], a.plane[4], a.plane[5], a.plane[6], a.plane[7], a.plane[8], a.plane[9], a.h64, a.temp,
+                       a.d_tab, a.h_tab, a.d_cnt, a.h_cnt, a.d_res, a.h_res};
+  return (uint64_t)(uintptr_t)p[i];
+}
+uint64_t as_cap(Rig* r, int i) {
+  const uint64_t c[5] = {r->a.words, r->a.more_words, r->a.temp_bytes, r->a.tab_cap, r->a.res_cap};
+  return c[i];
 }
 }
