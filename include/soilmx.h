@@ -483,6 +483,51 @@ int smx_through(smx_ctx* ctx, smx_through_record* out, uint64_t struct_size, uin
 int smx_ensemble_through(smx_ensemble* e, smx_through_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
 int smx_get_through_sweeps(smx_ctx* ctx, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches);
 int smx_ensemble_get_through_sweeps(smx_ensemble* e, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches);
+/* ---- hillslopes: where the land enters the channel network, how far it is from there, how high it stands above it (HAND), and one
+ *      record per segment of the land that drains into it from the side ----
+ * Cells, h(c), wet cells, receivers R and sinks are those of smx_drainage; channel cells, segments and their ranks are those of
+ * smx_streams on the same state with the same threshold, a u32 >= 1. For a dry cell c follow c, R(c), R(R(c)), ...: its ENTRY e(c) is
+ * the first cell on that path, c itself included, that is a channel cell, a sink or a wet cell. A wet cell has no entry.
+ * straight(c) / diagonal(c) are the numbers of straight and diagonal steps from c to e(c): the flow length is straight + diagonal *
+ * sqrt(2), as in smx_segment. hand(c) = h(c) - h(e(c)) is one f64 subtraction, the height above the nearest drainage: the cells with
+ * hand < stage are the ones under water at that stage. hillslope(c) is the rank of the segment that e(c) lies on, 0xFFFFFFFF where
+ * e(c) is no channel cell: that land is unchannelled, it drains into a pit or a lake directly. A wet cell gets entry = hillslope =
+ * 0xFFFFFFFF, straight = diagonal = 0 and hand = +0.0; a channel cell, and a sink off the channels, is its own entry with 0 steps
+ * and hand = +0.0. A path has at most min(threshold, cells) - 1 steps: every dry cell before the entry is off the channels, so its
+ * area is below threshold, and the area is at least the number of cells upstream. Every figure of a record is an integer add or an
+ * order-free extreme: a host restatement reproduces each bit, whatever the launch shape and the order of arrival. */
+typedef struct smx_hillslope {            /* 64 bytes; record k belongs to segment k of smx_streams on the same state with the same threshold */
+  uint32_t first_cell;                   /* the segment's identity: join on it with smx_segment */
+  uint32_t cells;                        /* dry cells off the channels whose entry lies on the segment */
+  uint32_t steps_max;                    /* the largest straight + diagonal among them */
+  uint32_t farthest_cell;                /* the cell that has steps_max, the smallest cell index among equals; 0xFFFFFFFF when cells == 0 */
+  uint64_t straight_sum, diagonal_sum;   /* exact sums over those cells */
+  double   hand_max;                     /* the largest hand by the ordered image K of smx_spill; +0.0 when cells == 0 */
+  uint64_t hand_sum_q40;                 /* the sum of floor(hand * 2^40) as u64, as smx_lake.volume_q40: a term that is not finite, is
+                                            negative or is >= 2^24 contributes 0 and sets flag 1; a wrapped sum sets it too */
+  uint32_t bank_cells;                   /* those with exactly one step */
+  uint32_t head_cells;                   /* those whose entry is the segment's first_cell */
+  uint32_t flags;                        /* 1: hand_sum_q40 unreliable */
+  uint32_t reserved;                     /* written as 0 */
+} smx_hillslope;
+/* *nsegments = the number of segments, whatever cap is; the first min(cap, *nsegments) records are written in rank order, record k at
+ * byte k * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each record); out may be NULL when cap is 0
+ * (counting only). The planes (NULL = skip) hold dimx*dimy words -- hand: doubles -- in cell order, as defined above, entry as a cell
+ * index. In the ensemble call member i's records start at out + i * cap_per_member records and nsegments holds one count per member;
+ * an empty ensemble: 0, nothing written. Both calls run on the context's / the ensemble's stream (they see every tick queued before
+ * them), launch the same kernels whatever the map holds and however many members there are (one table upload; the streams chain on
+ * the call's own scratch with k_stream_segments writing its plane and no record; k_hill_init; k rounds of k_hill_jump, pointer
+ * doubling between two sets of planes, k the smallest number with 2^k >= min(threshold, cells of the largest map) - 1, known before
+ * the launch; k_hill_fold; the RESULTS copied back), synchronise once and change no map, flag, counter or generator; the results
+ * and the scratch of the sibling analyses are not touched. No kernel waits for another lane or workgroup. A strip context, a null
+ * argument, struct_size == 0, threshold == 0 and records asked for with out == NULL return -2, a context without a device -3. The
+ * scratch -- ten u32 planes and one f64 plane per cell and the records asked for -- is allocated at first use and kept; an
+ * allocation that fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells
+ * per call. */
+int smx_hillslopes(smx_ctx* ctx, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap, uint32_t* nsegments,
+                   uint32_t* entry, uint32_t* hillslope, uint32_t* straight, uint32_t* diagonal, double* hand);
+int smx_ensemble_hillslopes(smx_ensemble* e, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap_per_member,
+                            uint32_t* nsegments);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

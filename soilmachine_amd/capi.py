@@ -137,6 +137,18 @@ class Through(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class Hillslope(C.Structure):
+    """smx_hillslope: one segment's record of smx_hillslopes / smx_ensemble_hillslopes (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("steps_max", C.c_uint32), ("farthest_cell", C.c_uint32),
+                ("straight_sum", C.c_uint64), ("diagonal_sum", C.c_uint64), ("hand_max", C.c_double), ("hand_sum_q40", C.c_uint64),
+                ("bank_cells", C.c_uint32), ("head_cells", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        d["hand_sum"] = int(self.hand_sum_q40) * 2.0 ** -40    # below the exact sum of the hands by less than cells * 2^-40
+        return d
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -165,6 +177,8 @@ SPILL_LAKE, SPILL_OFFMAP, SPILL_NESTED, SPILL_STORAGE_UNRELIABLE, SPILL_FILL_STO
 
 THROUGH_NONE = 0xFFFFFFFF              # smx_through_record.exit_to / down: off the map
 THROUGH_LAKE, THROUGH_OFFMAP, THROUGH_NOT_POUR, THROUGH_WET_ENTRY = 1, 2, 4, 8   # smx_through_record.flags
+HILL_NONE = 0xFFFFFFFF                 # the entry / hillslope planes: a wet cell; hillslope: unchannelled land; smx_hillslope.farthest_cell: no cell
+HILL_HAND_UNRELIABLE = 1                # smx_hillslope.flags
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
@@ -189,6 +203,7 @@ SYMBOLS = [
     "smx_streams", "smx_ensemble_streams",
     "smx_spill", "smx_ensemble_spill", "smx_get_spill_sweeps", "smx_ensemble_get_spill_sweeps",
     "smx_through", "smx_ensemble_through", "smx_get_through_sweeps", "smx_ensemble_get_through_sweeps",
+    "smx_hillslopes", "smx_ensemble_hillslopes",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -327,6 +342,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_through.argtypes = [vp, vp, u64, u32, vp]
     L.smx_get_through_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.smx_ensemble_get_through_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.smx_hillslopes.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp, vp]
+    L.smx_ensemble_hillslopes.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -51,6 +51,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_spill.h"
 #include "soil_through.h"
 #include "soil_streams.h"
+#include "soil_hills.h"
 #include "soil_strata.h"
 #include "soil_scratch.h"
 #include <algorithm>
@@ -480,6 +481,35 @@ struct StreamMarkFn {   // the scan's input: 1 where plane word g starts a segme
   const uint32_t* D;
   __host__ __device__ uint32_t operator()(uint32_t g) const { return stream_mark(D, g); }
 };
+
+// ---------------- the hillslopes (smx_hillslopes / smx_ensemble_hillslopes; bodies: soil_hills.h) ----------------
+// Behind the streams chain, on its planes. k_hill_init and k_hill_jump take one lane per cell and stream: a round of k_hill_jump reads
+// three words, gathers three and writes three per cell. k_hill_fold's table holds 512 cells' worth of segments (30 KB of LDS).
+struct HillSet {   // one of the two sets k_hill_jump writes in turns: the jump pointer and the steps to it
+  uint32_t *J, *S, *G;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_hill_init(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ SG, HillSet s, HillAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  const uint64_t n = (uint64_t)m.dimx * (uint64_t)m.dimy;
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= n) return;
+  ObsGroup g;
+  hill_init_group(m, g, blockIdx.x, (uint32_t)((n + LAKE_LANES - 1) / LAKE_LANES), SG, s.J, s.S, s.G, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_hill_jump(const LakeMember* __restrict__ tab, HillSet from, HillSet to) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  hill_jump_group(m, g, blockIdx.x, from.J, from.S, from.G, to.J, to.S, to.G);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_hill_fold(const LakeMember* __restrict__ tab, HillSet s, const uint32_t* __restrict__ SG, const uint32_t* __restrict__ D,
+                                                          const uint32_t* __restrict__ B, HillAcc* acc, uint32_t* nsegments, uint32_t* entry, uint32_t* hillslope,
+                                                          double* hand) {
+  __shared__ HillTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  hill_fold_group<LAKE_SLOTS>(m, g, blockIdx.x, t, s.J, s.S, s.G, SG, D, B, acc, nsegments + blockIdx.y, entry, hillslope, hand);
+}
 
 // ---------------- spill analysis (smx_spill / smx_ensemble_spill; bodies: soil_spill.h) ----------------
 // The census's tiles and lanes. k_spill_pass holds the height and rank tiles with their halo of one (18 x 66 doubles and words, 14 KB
@@ -1960,8 +1990,8 @@ struct ForkScratch {
   ForkDst* tab = nullptr; uint32_t tab_cap = 0;
 };
 
-// (the scratch of the five terrain analyses -- smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through -- is AnalysisScratch,
-// soil_scratch.h: one instance per analysis and owner)
+// (the scratch of the terrain analyses -- smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes -- is
+// AnalysisScratch, soil_scratch.h: one instance per analysis and owner)
 using AnalysisScratch = AnalysisScratchOf<LakeMember>;
 
 // smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores: the member table, the error words, the records, the core
@@ -2039,7 +2069,7 @@ struct smx_ctx : EventTimer {
   uint32_t* d_tdone = nullptr; uint32_t* d_tpend[2] = {nullptr, nullptr}; uint32_t* d_tcount = nullptr; uint32_t* h_tcount = nullptr; void* d_tsort = nullptr; size_t tsort_bytes = 0; uint32_t tsort_cap = 0;   // grid pass: tile states, pending lists
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
-  AnalysisScratch lakes, drain, streams, spill, through;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through: one each
+  AnalysisScratch lakes, drain, streams, spill, through, hills;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes: one each
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3619,7 +3649,7 @@ struct smx_ensemble : EventTimer {
   void* d_obs = nullptr; size_t d_obs_cap = 0;
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
-  AnalysisScratch lakes, drain, streams, spill, through;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through: one each
+  AnalysisScratch lakes, drain, streams, spill, through, hills;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes: one each
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4078,9 +4108,9 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 
 }  // extern "C"
 
-// ---------------- the five terrain analyses: the lake census, drainage, the stream network, spill, through-drainage ----------------
-// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through and their smx_ensemble_* twins; kernels: soil_lakes.h, soil_drain.h,
-// soil_streams.h, soil_spill.h, soil_through.h)
+// ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes ----------------
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes and their smx_ensemble_* twins; kernels: soil_lakes.h,
+// soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h)
 // One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
 // cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
 // stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
@@ -4503,6 +4533,61 @@ static int through_run(const AnalysisCall& c, AnalysisScratch& k, smx_through_re
   return 0;
 }
 
+// ---- the hillslopes: the ten planes of StreamPlanes and the f64 plane. The streams chain through the bare table, k_stream_segments
+// with its plane and no record: SG is complete. Then k_hill_init through the table with the record caps (J takes R's plane, S and G
+// take P's and AR's), k rounds of k_hill_jump between that set and (T, O, H) -- k is known before the launch from the path bound
+// min(threshold, the largest map's cells) - 1 --, k_hill_fold on the set the last round wrote; entry goes to RE's plane, hillslope to
+// the other set's J, hand to the f64 plane, the steps are the settled set itself. The counts, the records and the planes asked for
+// copied back, one synchronisation.
+static_assert(sizeof(smx_hillslope) == 64 && sizeof(HillRec) == sizeof(smx_hillslope) && offsetof(smx_hillslope, straight_sum) == offsetof(HillRec, straight_sum) &&
+              offsetof(smx_hillslope, hand_max) == offsetof(HillRec, hand_max) && offsetof(smx_hillslope, bank_cells) == offsetof(HillRec, bank_cells) &&
+              offsetof(smx_hillslope, farthest_cell) == offsetof(HillRec, farthest_cell), "smx_hillslope layout");
+static int hills_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap, uint32_t* nsegments,
+                     uint32_t* entry, uint32_t* hillslope, uint32_t* straight, uint32_t* diagonal, double* hand) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_CELLS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm);
+  need.words = (size_t)pl.words; need.planes = 10; need.f64 = true; need.members = c.nm; need.res_bytes = rec_at + (size_t)pl.nrec * sizeof(HillAcc);
+  if (!scan_bytes(c, stream_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "hillslope", pl.nrec)) return rc;
+  const StreamPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.plane[4], k.plane[5], k.plane[6], k.plane[7], k.plane[8], k.plane[9]};
+  const HillSet set[2] = {{p.R, p.P, p.AR}, {p.T, p.O, p.H}};
+  uint64_t largest = 0;
+  for (uint32_t i = 0; i < c.nm; i++) largest = std::max<uint64_t>(largest, c.ms[i]->ncells);
+  const uint32_t rounds = hill_rounds(hill_bound(threshold, largest));
+  const HillSet& last = set[rounds & 1u];
+  uint32_t* const d_entry = p.RE; uint32_t* const d_hill = set[(rounds + 1u) & 1u].J;
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  HillAcc* acc = reinterpret_cast<HillAcc*>(k.d_res + rec_at);
+  const LakeMember* bare = k.d_tab + c.nm;
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  if (ok) {
+    launch_drain_chain(pl, c.st, k, bare, bare, p.T, nullptr, p.R, nullptr, nullptr, p.P, p.AR);
+    hipLaunchKernelGGL(k_stream_mark, pl.gf, pl.wg, 0, c.st, bare, threshold, p);
+    hipLaunchKernelGGL(k_stream_order, pl.gf, pl.wg, 0, c.st, bare, threshold, p);
+    ok = scan_words(k, stream_marks(p.D), p.B, pl.words, c.st);
+    hipLaunchKernelGGL(k_stream_segments, pl.gf, pl.wg, 0, c.st, bare, 1, p, (StreamRec*)nullptr, d_n);   // (cap 0: no record is written)
+    hipLaunchKernelGGL(k_hill_init, pl.gf, pl.wg, 0, c.st, k.d_tab, p.SG, set[0], acc);
+    for (uint32_t r = 0; r < rounds; r++) hipLaunchKernelGGL(k_hill_jump, pl.gf, pl.wg, 0, c.st, bare, set[r & 1u], set[(r + 1u) & 1u]);
+    hipLaunchKernelGGL(k_hill_fold, pl.gs, pl.wg, 0, c.st, k.d_tab, last, p.SG, p.D, p.B, acc, d_n, entry ? d_entry : nullptr, hillslope ? d_hill : nullptr,
+                       hand ? k.h64 : nullptr);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_hillslopes only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, entry, d_entry, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, hillslope, d_hill, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, straight, last.S, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, diagonal, last.G, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, hand, k.h64, (size_t)pl.words * 8);
+  if (analysis_wait(c, ok, "the hillslopes")) return -1;
+  const HillAcc* a = reinterpret_cast<const HillAcc*>(k.h_res + rec_at);
+  cut_records<HillRec>(pl, reinterpret_cast<const uint32_t*>(k.h_res), out, struct_size, cap, nsegments, [a](size_t j, HillRec& rec) -> const HillRec& { hill_finish(a[j], rec); return rec; });
+  return 0;
+}
+
 extern "C" {
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
   if (!ctx) return -2;
@@ -4594,6 +4679,25 @@ int smx_ensemble_through(smx_ensemble* e, smx_through_record* out, uint64_t stru
   roctx_range rr("soilmx:ensemble_through");
   HIPCHK(e, hipSetDevice(e->device));
   return through_run(c, e->through, out, struct_size, cap_per_member, nbasins, nullptr, nullptr);
+}
+int smx_hillslopes(smx_ctx* ctx, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap, uint32_t* nsegments, uint32_t* entry,
+                   uint32_t* hillslope, uint32_t* straight, uint32_t* diagonal, double* hand) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_hillslopes", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_hillslope", "nsegments", struct_size, &threshold, nsegments, out, cap, rc)) return rc;
+  roctx_range rr("soilmx:hillslopes");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return hills_run(c, ctx->hills, threshold, out, struct_size, cap, nsegments, entry, hillslope, straight, diagonal, hand);
+}
+int smx_ensemble_hillslopes(smx_ensemble* e, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nsegments) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_hillslopes", e);
+  int rc;
+  if (!analysis_begin(c, "smx_hillslope", "nsegments", struct_size, &threshold, nsegments, out, cap_per_member, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_hillslopes");
+  HIPCHK(e, hipSetDevice(e->device));
+  return hills_run(c, e->hills, threshold, out, struct_size, cap_per_member, nsegments, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 // (sweeps launched, batches) of the last spill call; (level sweeps, hop sweeps, batches) of the last through call
 static int sweeps_of(const AnalysisScratch& k, std::string& err, const char* who, uint32_t* a, uint32_t* b, uint32_t* batches) {

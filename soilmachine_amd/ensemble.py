@@ -283,6 +283,15 @@ class Ensemble:
         threshold = int(threshold)
         return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_streams(self.h, threshold, out, C.sizeof(capi.Stream), cap, counts), capi.Stream, cap)
 
+    def hillslopes(self, threshold: int, cap: int | None = None) -> list:
+        """The hillslope records of every member (``smx_ensemble_hillslopes``: the same launches whatever the member count): one list
+        of dicts per member, in member order, each as ``Layermap.hillslopes(threshold)`` gives it, record k for segment k of
+        ``streams(threshold)``. ``cap`` None: two calls, a count with no records and the fetch sized by the largest count; else at
+        most ``cap`` segments per member. Members may differ in size."""
+        threshold = int(threshold)
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_hillslopes(self.h, threshold, out, C.sizeof(capi.Hillslope), cap, counts),
+                              capi.Hillslope, cap)
+
     def spill(self, cap: int | None = None) -> list:
         """The spill records of every member (``smx_ensemble_spill``: the same launches whatever the member count): one list of
         dicts per member, in member order, each as ``Layermap.spill()`` gives it. ``cap`` None: two calls, the basin counts and the

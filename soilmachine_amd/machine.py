@@ -192,16 +192,18 @@ class Layermap:
                 "rand_calls": self.counters()["rand_calls"]}
 
     def _analysis(self, call, rec, cap, planes, dtype=np.uint32, count=None):
-        """What the five terrain analyses share: the count call where ``cap`` is None (``count``, or ``call`` with no records and
+        """What the terrain analyses share: the count call where ``cap`` is None (``count``, or ``call`` with no records and
         no planes), the array sized by it, the fetch, the dicts -- and the (dimx, dimy) planes asked for, ``planes`` listing
-        (name, wanted) in the order of the plane arguments of ``call(out, cap, byref(n), *plane_pointers)``."""
+        (name, wanted) in the order of the plane arguments of ``call(out, cap, byref(n), *plane_pointers)``. ``dtype``: of every
+        plane, or a dict name -> dtype for the planes that are not uint32."""
         n = C.c_uint32()
         if cap is None:
             self._chk(count(C.byref(n)) if count else call(None, 0, C.byref(n), *[None] * len(planes)))
             cap = int(n.value)
         cap = int(cap)
         out = (rec * max(1, cap))()
-        got = {k: np.zeros(self.dimx * self.dimy, dtype) for k, want in planes if want}
+        each = dtype if isinstance(dtype, dict) else {k: dtype for k, _ in planes}
+        got = {k: np.zeros(self.dimx * self.dimy, each.get(k, np.uint32)) for k, want in planes if want}
         self._chk(call(out, cap, C.byref(n), *[capi.ptr(got.get(k)) for k, _ in planes]))
         return [out[k].as_dict() for k in range(min(cap, int(n.value)))], {k: v.reshape(self.dimx, self.dimy) for k, v in got.items()}
 
@@ -292,6 +294,26 @@ class Layermap:
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._chk(self.L.smx_get_through_sweeps(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    def hillslopes(self, threshold: int, entry: bool = False, hillslope: bool = False, straight: bool = False, diagonal: bool = False, hand: bool = False,
+                   cap: int | None = None):
+        """The land beside the channels (``smx_hillslopes``): one dict per segment, record k for segment k of ``streams(threshold)``
+        -- ``first_cell`` (join on it with ``streams()``), ``cells`` (the dry cells off the channels whose entry lies on the
+        segment), ``steps_max`` / ``farthest_cell`` (the longest way to the segment and the cell it starts at, 0xFFFFFFFF without a
+        cell), ``straight_sum`` / ``diagonal_sum`` (flow length = straight + diagonal * sqrt(2)), ``hand_max``, ``hand_sum_q40`` (the
+        exact integer sum of floor(hand * 2^40)) and ``hand_sum`` (that as a float), ``bank_cells`` (one step from the segment),
+        ``head_cells`` (entering at the segment's first cell) and ``flags`` (1: ``hand_sum_q40`` unreliable). A dry cell's entry is
+        the first channel cell, sink or wet cell on its way down, the cell itself included; ``hand`` is the cell's height above its
+        entry. With a plane asked for the result is ``(records, planes)``, ``planes`` a dict of (dimx, dimy) arrays: ``entry`` (the
+        entry's cell index), ``hillslope`` (the rank of the entry's segment, 0xFFFFFFFF for unchannelled land), ``straight`` /
+        ``diagonal`` (steps to the entry), all uint32 and 0xFFFFFFFF / 0 for a wet cell, and ``hand`` (float64: the cells with
+        ``hand < stage`` are under water at that stage). ``cap`` None: two calls, a count and the fetch; else at most ``cap``
+        segments. Sees every tick queued before it and changes nothing."""
+        threshold = int(threshold)
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_hillslopes(self.h, threshold, out, C.sizeof(capi.Hillslope), cap, n, *pl), capi.Hillslope,
+                                      cap, [("entry", entry), ("hillslope", hillslope), ("straight", straight), ("diagonal", diagonal), ("hand", hand)],
+                                      dtype={"hand": np.float64})
+        return (recs, planes) if planes else recs
 
     # -- the strata read on the device --
     def soil_totals(self, ntypes: int | None = None, other: bool = False):
