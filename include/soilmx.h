@@ -528,6 +528,54 @@ int smx_hillslopes(smx_ctx* ctx, uint32_t threshold, smx_hillslope* out, uint64_
                    uint32_t* entry, uint32_t* hillslope, uint32_t* straight, uint32_t* diagonal, double* hand);
 int smx_ensemble_hillslopes(smx_ensemble* e, uint32_t threshold, smx_hillslope* out, uint64_t struct_size, uint32_t cap_per_member,
                             uint32_t* nsegments);
+/* ---- flow paths: how far every cell is from where its water ends up and how far it falls on the way, the longest path that arrives
+ *      at every cell, and per basin the main stem with the ordered list of its cells, the long profile ----
+ * Cells, h(c), wet cells, lakes, receivers R, sinks, basins, first_cell and the rank are those of smx_drainage, the ordered image K
+ * that of smx_spill. The TERMINAL t(c) of a dry cell is the last cell of the path c, R(c), R(R(c)), ...: a sink (c itself where c is
+ * a sink) or the first wet cell the path meets. A wet cell is its own terminal. straight(c) / diagonal(c) count the steps from c to
+ * t(c), the step into a wet cell included, split as in smx_segment; steps = straight + diagonal. drop(c) = h(c) - h(t(c)) is one f64
+ * subtraction, +0.0 where t(c) == c: a NaN cell, always a sink, has drop +0.0.
+ * key(c) = (steps(c) << 32) | (0xFFFFFFFF - c). up(c) is the largest key(u) over the cells u whose path passes through c, c
+ * included. upstream(c) = (up(c) >> 32) - steps(c) is the number of steps of the longest flow path that arrives at c,
+ * source(c) = 0xFFFFFFFF - (u32)up(c) the cell it starts at: among equally long paths the smallest cell index.
+ * For a basin b, far(b) is the largest key over its cells: it gives steps_max and source_cell. The MAIN STEM of b is the set of cells
+ * with up(c) == far(b). Keys are unique, so it is exactly the path from source_cell to t(source_cell), steps_max + 1 cells; in a
+ * lake's basin with several entry cells only one path qualifies. stem(c) = steps_max(b) - steps(c) on the stem, the position counted
+ * from the source, and 0xFFFFFFFF off the stems. The PROFILE is the stems of all basins in rank order, each from source to terminal:
+ * profile_at(b) is the sum of steps_max + 1 over the basins of lower rank, profile[profile_at(b) + stem(c)] = c, and nprofile, the
+ * total, is at most the number of cells. A lake without dry land has a stem of one cell, its first_cell. Every figure is a
+ * comparison, an exact integer, an order-free extreme or a copied / once-subtracted double: a host restatement reproduces each bit. */
+typedef struct smx_flowpath {             /* 64 bytes; record k belongs to basin k of smx_drainage on the same state */
+  uint32_t first_cell, cells;            /* the basin's identity and size */
+  uint32_t source_cell, terminal_cell;   /* the two ends of the main stem */
+  uint32_t steps_max, diagonal;          /* its steps, and how many of them are diagonal */
+  uint32_t profile_at;                   /* index of source_cell in the profile (the ensemble call: within the member) */
+  uint32_t flags;                        /* 1: terminal_cell is wet */
+  uint64_t straight_sum, diagonal_sum;   /* exact sums of straight(c), diagonal(c) over the basin's cells */
+  double   drop_source;                  /* drop(source_cell), the copied double */
+  double   drop_max;                     /* the largest drop in the basin by K */
+} smx_flowpath;
+/* *nbasins = the number of basins, whatever cap is; the first min(cap, *nbasins) records are written in rank order, record k at byte
+ * k * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each record); out may be NULL when cap is 0 (counting
+ * only). The planes (NULL = skip) hold dimx*dimy words -- drop: doubles -- in cell order, terminal and source as cell indices.
+ * *nprofile (NULL = skip) = the profile's length, whatever profile_cap is; the first min(profile_cap, *nprofile) entries of profile
+ * are written, and profile may be NULL when profile_cap is 0. The profile and every plane cover ALL basins, whatever cap is: only
+ * the records are cut at cap. In the ensemble call member i's records start at out + i * cap_per_member records, nbasins holds one
+ * count per member and profile_at counts within the member; an empty ensemble: 0, nothing written. Both calls run on the context's /
+ * the ensemble's stream (they see every tick queued before them), launch the same kernels whatever the map holds and however many
+ * members there are (one table upload; the drainage chain with its statistics on the call's own scratch, writing no basin record;
+ * k_drain_pending; k_path_init; k rounds of k_hill_jump, k the smallest number with 2^k >= cells of the largest map - 1, at most 32
+ * and known before the launch; k_path_fold; k_path_up; k_path_lengths; a prefix sum; k_path_stem; the RESULTS copied back),
+ * synchronise once and change no map, flag, counter or generator; the results and the scratch of the sibling analyses are not
+ * touched. No kernel waits for another lane or workgroup. A strip context, a null argument, struct_size == 0, records asked for
+ * with out == NULL and profile_cap > 0 with profile == NULL return -2, a context without a device -3. The scratch -- ten u32 planes
+ * and one 64-bit plane per cell, the records asked for and min(profile_cap, cells) words -- is allocated at first use and kept; an
+ * allocation that fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells
+ * per call. */
+int smx_flowpaths(smx_ctx* ctx, smx_flowpath* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* terminal,
+                  uint32_t* straight, uint32_t* diagonal, double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem,
+                  uint32_t* profile, uint32_t profile_cap, uint32_t* nprofile);
+int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

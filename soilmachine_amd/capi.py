@@ -6,6 +6,7 @@ context without a visible HIP device fails with the library's own error text.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -149,6 +150,18 @@ class Hillslope(C.Structure):
         return d
 
 
+class Flowpath(C.Structure):
+    """smx_flowpath: one basin's record of smx_flowpaths / smx_ensemble_flowpaths (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("source_cell", C.c_uint32), ("terminal_cell", C.c_uint32),
+                ("steps_max", C.c_uint32), ("diagonal", C.c_uint32), ("profile_at", C.c_uint32), ("flags", C.c_uint32),
+                ("straight_sum", C.c_uint64), ("diagonal_sum", C.c_uint64), ("drop_source", C.c_double), ("drop_max", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["length"] = (int(self.steps_max) - int(self.diagonal)) + int(self.diagonal) * math.sqrt(2.0)    # of the main stem, in cell widths
+        return d
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -179,6 +192,8 @@ THROUGH_NONE = 0xFFFFFFFF              # smx_through_record.exit_to / down: off 
 THROUGH_LAKE, THROUGH_OFFMAP, THROUGH_NOT_POUR, THROUGH_WET_ENTRY = 1, 2, 4, 8   # smx_through_record.flags
 HILL_NONE = 0xFFFFFFFF                 # the entry / hillslope planes: a wet cell; hillslope: unchannelled land; smx_hillslope.farthest_cell: no cell
 HILL_HAND_UNRELIABLE = 1                # smx_hillslope.flags
+PATH_NONE = 0xFFFFFFFF                 # the stem plane: a cell off the stems
+PATH_TERMINAL_WET = 1                  # smx_flowpath.flags
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
@@ -204,6 +219,7 @@ SYMBOLS = [
     "smx_spill", "smx_ensemble_spill", "smx_get_spill_sweeps", "smx_ensemble_get_spill_sweeps",
     "smx_through", "smx_ensemble_through", "smx_get_through_sweeps", "smx_ensemble_get_through_sweeps",
     "smx_hillslopes", "smx_ensemble_hillslopes",
+    "smx_flowpaths", "smx_ensemble_flowpaths",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -344,6 +360,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_get_through_sweeps.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.smx_hillslopes.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp, vp]
     L.smx_ensemble_hillslopes.argtypes = [vp, u32, vp, u64, u32, vp]
+    L.smx_flowpaths.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32)]
+    L.smx_ensemble_flowpaths.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -52,6 +52,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_through.h"
 #include "soil_streams.h"
 #include "soil_hills.h"
+#include "soil_paths.h"
 #include "soil_strata.h"
 #include "soil_scratch.h"
 #include <algorithm>
@@ -509,6 +510,49 @@ __global__ void __launch_bounds__(LAKE_LANES) k_hill_fold(const LakeMember* __re
   if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   hill_fold_group<LAKE_SLOTS>(m, g, blockIdx.x, t, s.J, s.S, s.G, SG, D, B, acc, nsegments + blockIdx.y, entry, hillslope, hand);
+}
+
+// ---------------- the flow paths (smx_flowpaths / smx_ensemble_flowpaths; bodies: soil_paths.h) ----------------
+// Behind the drainage chain and k_drain_pending, on their planes; the pointer doubling is k_hill_jump. One lane per cell throughout;
+// k_path_up is the lane-serial walk of k_drain_area with a 64-bit max for the add. k_path_fold's table holds 512 cells' worth of
+// basins (20 KB of LDS).
+struct PathPlanes {   // what the kernels behind the jump rounds work on (soil_paths.h): s the settled set
+  uint32_t *T, *R, *P, *FH, *FS, *L, *PA;
+  uint64_t* UP;
+  HillSet s;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_path_init(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ R, HillSet s, uint32_t* FH, PathAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  const uint64_t n = (uint64_t)m.dimx * (uint64_t)m.dimy;
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= n) return;
+  ObsGroup g;
+  path_init_group(m, g, blockIdx.x, (uint32_t)((n + LAKE_LANES - 1) / LAKE_LANES), R, s.J, s.S, s.G, FH, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_path_fold(const LakeMember* __restrict__ tab, PathPlanes p, PathAcc* acc) {
+  __shared__ PathTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  path_fold_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.T, p.R, p.s.J, p.s.S, p.s.G, p.UP, p.FH, p.FS, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_path_up(const LakeMember* __restrict__ tab, PathPlanes p) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  path_up_group(m, g, blockIdx.x, p.R, p.P, p.UP);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_path_lengths(const LakeMember* __restrict__ tab, PathPlanes p, const uint32_t* __restrict__ nbasins) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  path_lengths_group(m, g, blockIdx.x, p.T, p.s.S, p.s.G, p.FH, p.FS, p.L, nbasins + blockIdx.y);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_path_stem(const LakeMember* __restrict__ tab, PathPlanes p, PathAcc* acc, const uint32_t* __restrict__ nbasins,
+                                                          uint32_t* nprofile, PathOut o) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  path_stem_group(m, g, blockIdx.x, p.T, p.s.J, p.s.S, p.s.G, p.UP, p.FH, p.FS, p.PA, acc, nbasins + blockIdx.y, nprofile + blockIdx.y, o);
 }
 
 // ---------------- spill analysis (smx_spill / smx_ensemble_spill; bodies: soil_spill.h) ----------------
@@ -2069,7 +2113,7 @@ struct smx_ctx : EventTimer {
   uint32_t* d_tdone = nullptr; uint32_t* d_tpend[2] = {nullptr, nullptr}; uint32_t* d_tcount = nullptr; uint32_t* h_tcount = nullptr; void* d_tsort = nullptr; size_t tsort_bytes = 0; uint32_t tsort_cap = 0;   // grid pass: tile states, pending lists
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
-  AnalysisScratch lakes, drain, streams, spill, through, hills;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes: one each
+  AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths: one each
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3649,7 +3693,7 @@ struct smx_ensemble : EventTimer {
   void* d_obs = nullptr; size_t d_obs_cap = 0;
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
-  AnalysisScratch lakes, drain, streams, spill, through, hills;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes: one each
+  AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes, _flowpaths: one each
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4108,9 +4152,9 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 
 }  // extern "C"
 
-// ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes ----------------
-// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes and their smx_ensemble_* twins; kernels: soil_lakes.h,
-// soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h)
+// ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes, the flow paths ----------------
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths and their smx_ensemble_* twins; kernels:
+// soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h)
 // One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
 // cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
 // stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
@@ -4588,6 +4632,76 @@ static int hills_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t thresho
   return 0;
 }
 
+// ---- the flow paths: ten planes and the f64 plane, which holds the 64-bit words UP. The drainage chain with its statistics through
+// the bare table (T becomes the rank plane, the counts go to d_n, no basin record is written), k_drain_pending (its AR plane is the
+// first set's J, overwritten next), k_path_init through the table with the record caps (B's plane becomes FH), k rounds of
+// k_hill_jump between the sets (4, 5, 6) and (7, 8, 9) -- k is known before the launch from the cells of the largest map --, then on
+// the set the last round wrote: k_path_fold, k_path_up, k_path_lengths, the scan of the lengths, k_path_stem. The other set is dead
+// by then: its planes are FS, L and PA. stem goes over T, the terminal over J, the drop over UP, upstream and source to the planes
+// of R and P, dead behind k_path_up; the steps are the settled set itself; the profile is scattered into the result region behind
+// the records. The counts (the basins, then the profiles' lengths), the records, the profile and the planes asked for copied back,
+// one synchronisation.
+static_assert(sizeof(smx_flowpath) == 64 && sizeof(PathRec) == sizeof(smx_flowpath) && offsetof(smx_flowpath, source_cell) == offsetof(PathRec, source_cell) &&
+              offsetof(smx_flowpath, profile_at) == offsetof(PathRec, profile_at) && offsetof(smx_flowpath, straight_sum) == offsetof(PathRec, straight_sum) &&
+              offsetof(smx_flowpath, drop_source) == offsetof(PathRec, drop_source) && offsetof(smx_flowpath, drop_max) == offsetof(PathRec, drop_max),
+              "smx_flowpath layout");
+static int paths_run(const AnalysisCall& c, AnalysisScratch& k, smx_flowpath* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* terminal,
+                     uint32_t* straight, uint32_t* diagonal, double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem, uint32_t* profile,
+                     uint32_t profile_cap, uint32_t* nprofile) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_CELLS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(2 * c.nm), prof_at = rec_at + (size_t)pl.nrec * sizeof(PathAcc);
+  const uint32_t pcap = profile ? (uint32_t)std::min<uint64_t>(profile_cap, pl.words) : 0u;   // (a profile has at most a cell per cell)
+  need.words = (size_t)pl.words; need.planes = 10; need.f64 = true; need.members = c.nm; need.res_bytes = prof_at + (size_t)pcap * 4;
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes) || !scan_bytes(c, (const uint32_t*)nullptr, pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "flow path", pl.nrec)) return rc;
+  const HillSet set[2] = {{k.plane[4], k.plane[5], k.plane[6]}, {k.plane[7], k.plane[8], k.plane[9]}};
+  uint64_t largest = 0;
+  for (uint32_t i = 0; i < c.nm; i++) largest = std::max<uint64_t>(largest, c.ms[i]->ncells);
+  const uint32_t rounds = hill_rounds(largest - 1u);   // (a path has at most cells - 1 steps)
+  const HillSet& spare = set[(rounds + 1u) & 1u];
+  PathPlanes p;
+  p.T = k.plane[0]; p.FH = k.plane[1]; p.R = k.plane[2]; p.P = k.plane[3]; p.FS = spare.J; p.L = spare.S; p.PA = spare.G;
+  p.UP = reinterpret_cast<uint64_t*>(k.h64); p.s = set[rounds & 1u];
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  PathAcc* acc = reinterpret_cast<PathAcc*>(k.d_res + rec_at);
+  PathOut o;
+  o.want_terminal = terminal ? 1u : 0u; o.want_stem = stem ? 1u : 0u; o.want_drop = drop ? 1u : 0u; o.profile_cap = pcap;
+  o.upstream = upstream ? p.R : nullptr; o.source = source ? p.P : nullptr; o.profile = pcap ? reinterpret_cast<uint32_t*>(k.d_res + prof_at) : nullptr;
+  const LakeMember* bare = k.d_tab + c.nm;
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  if (ok) {
+    ok = launch_drain_chain(pl, c.st, k, bare, bare, p.T, p.FH, p.R, nullptr, d_n, nullptr, nullptr);
+    hipLaunchKernelGGL(k_drain_pending, pl.gf, pl.wg, 0, c.st, bare, p.R, p.P, set[0].J);
+    hipLaunchKernelGGL(k_path_init, pl.gf, pl.wg, 0, c.st, k.d_tab, p.R, set[0], p.FH, acc);
+    for (uint32_t r = 0; r < rounds; r++) hipLaunchKernelGGL(k_hill_jump, pl.gf, pl.wg, 0, c.st, bare, set[r & 1u], set[(r + 1u) & 1u]);
+    hipLaunchKernelGGL(k_path_fold, pl.gs, pl.wg, 0, c.st, k.d_tab, p, acc);
+    hipLaunchKernelGGL(k_path_up, pl.gf, pl.wg, 0, c.st, bare, p);
+    hipLaunchKernelGGL(k_path_lengths, pl.gf, pl.wg, 0, c.st, bare, p, d_n);
+    ok = ok && scan_words(k, (const uint32_t*)p.L, p.PA, pl.words, c.st);
+    hipLaunchKernelGGL(k_path_stem, pl.gf, pl.wg, 0, c.st, k.d_tab, p, acc, d_n, d_n + c.nm, o);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_flowpaths only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, terminal, p.s.J, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, straight, p.s.S, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, diagonal, p.s.G, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, drop, k.h64, (size_t)pl.words * 8);
+  ok = copy_back(c, ok, upstream, p.R, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, source, p.P, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, stem, p.T, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "the flow paths")) return -1;
+  const uint32_t* n = reinterpret_cast<const uint32_t*>(k.h_res);
+  if (nprofile) *nprofile = n[c.nm];
+  if (pcap) memcpy(profile, k.h_res + prof_at, (size_t)std::min(pcap, n[c.nm]) * 4);
+  const PathAcc* a = reinterpret_cast<const PathAcc*>(k.h_res + rec_at);
+  cut_records<PathRec>(pl, n, out, struct_size, cap, nbasins, [a](size_t j, PathRec& rec) -> const PathRec& { path_finish(a[j], rec); return rec; });
+  return 0;
+}
+
 extern "C" {
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
   if (!ctx) return -2;
@@ -4698,6 +4812,26 @@ int smx_ensemble_hillslopes(smx_ensemble* e, uint32_t threshold, smx_hillslope* 
   roctx_range rr("soilmx:ensemble_hillslopes");
   HIPCHK(e, hipSetDevice(e->device));
   return hills_run(c, e->hills, threshold, out, struct_size, cap_per_member, nsegments, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+int smx_flowpaths(smx_ctx* ctx, smx_flowpath* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint32_t* terminal, uint32_t* straight, uint32_t* diagonal,
+                  double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem, uint32_t* profile, uint32_t profile_cap, uint32_t* nprofile) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_flowpaths", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_flowpath", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
+  if (!profile && profile_cap) { ctx->err = "smx_flowpaths: profile is null while profile_cap is " + std::to_string(profile_cap); return -2; }
+  roctx_range rr("soilmx:flowpaths");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return paths_run(c, ctx->paths, out, struct_size, cap, nbasins, terminal, straight, diagonal, drop, upstream, source, stem, profile, profile_cap, nprofile);
+}
+int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_flowpaths", e);
+  int rc;
+  if (!analysis_begin(c, "smx_flowpath", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_flowpaths");
+  HIPCHK(e, hipSetDevice(e->device));
+  return paths_run(c, e->paths, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
 }
 // (sweeps launched, batches) of the last spill call; (level sweeps, hop sweeps, batches) of the last through call
 static int sweeps_of(const AnalysisScratch& k, std::string& err, const char* who, uint32_t* a, uint32_t* b, uint32_t* batches) {

@@ -292,6 +292,13 @@ class Ensemble:
         return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_hillslopes(self.h, threshold, out, C.sizeof(capi.Hillslope), cap, counts),
                               capi.Hillslope, cap)
 
+    def flowpaths(self, cap: int | None = None) -> list:
+        """The flow path records of every member (``smx_ensemble_flowpaths``: the same launches whatever the member count): one list
+        of dicts per member, in member order, each as ``Layermap.flowpaths()`` gives it, record k for basin k of ``drainage()``;
+        ``profile_at`` counts within the member. ``cap`` None: two calls, a count with no records and the fetch sized by the largest
+        count; else at most ``cap`` basins per member. Members may differ in size."""
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_flowpaths(self.h, out, C.sizeof(capi.Flowpath), cap, counts), capi.Flowpath, cap)
+
     def spill(self, cap: int | None = None) -> list:
         """The spill records of every member (``smx_ensemble_spill``: the same launches whatever the member count): one list of
         dicts per member, in member order, each as ``Layermap.spill()`` gives it. ``cap`` None: two calls, the basin counts and the

@@ -295,6 +295,33 @@ class Layermap:
         self._chk(self.L.smx_get_through_sweeps(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    def flowpaths(self, cap: int | None = None, terminal: bool = False, straight: bool = False, diagonal: bool = False, drop: bool = False,
+                  upstream: bool = False, source: bool = False, stem: bool = False, profiles: bool = False):
+        """The flow paths (``smx_flowpaths``): one dict per basin, record k for basin k of ``drainage()`` -- ``first_cell`` and
+        ``cells`` (the basin), ``source_cell`` / ``terminal_cell`` (the two ends of the main stem, the basin's longest flow path, of
+        equally long ones the one from the smallest cell), ``steps_max`` / ``diagonal`` (its steps and how many are diagonal) and
+        ``length`` (straight + diagonal * sqrt(2)), ``profile_at`` (where the stem starts in the profile), ``flags`` (1: the stem
+        ends in a wet cell), ``straight_sum`` / ``diagonal_sum`` (exact sums of the steps to the terminal over the basin's cells),
+        ``drop_source`` and ``drop_max``. A dry cell's terminal is the sink or the first wet cell on its way down, a wet cell its
+        own; ``drop`` is the cell's height above its terminal. With a plane asked for the result is ``(records, planes)``,
+        ``planes`` a dict of (dimx, dimy) arrays: ``terminal`` (a cell index), ``straight`` / ``diagonal`` (steps to the terminal),
+        ``upstream`` (the steps of the longest path that arrives at the cell), ``source`` (where that path starts), ``stem`` (the
+        position on the basin's main stem counted from its source, 0xFFFFFFFF off the stems), all uint32, and ``drop`` (float64).
+        ``profiles``: every record also gets ``profile``, the cells of its stem from source to terminal -- a slice of one list, the
+        long profile being the heights along it; the stems of ALL basins are found whatever ``cap`` is. ``cap`` None: two calls, a
+        count and the fetch; else at most ``cap`` basins. Sees every tick queued before it and changes nothing."""
+        prof = np.zeros(self.dimx * self.dimy if profiles else 1, np.uint32)
+        pcap, nprof = (prof.size if profiles else 0), C.c_uint32()
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_flowpaths(self.h, out, C.sizeof(capi.Flowpath), cap, n, *pl,
+                                                                                     capi.ptr(prof) if out is not None and profiles else None,
+                                                                                     pcap if out is not None else 0, C.byref(nprof)),
+                                      capi.Flowpath, cap, [("terminal", terminal), ("straight", straight), ("diagonal", diagonal), ("drop", drop), ("upstream", upstream),
+                                                           ("source", source), ("stem", stem)], dtype={"drop": np.float64})
+        if profiles:
+            for r in recs:
+                r["profile"] = prof[r["profile_at"]:r["profile_at"] + r["steps_max"] + 1].copy()
+        return (recs, planes) if planes else recs
+
     def hillslopes(self, threshold: int, entry: bool = False, hillslope: bool = False, straight: bool = False, diagonal: bool = False, hand: bool = False,
                    cap: int | None = None):
         """The land beside the channels (``smx_hillslopes``): one dict per segment, record k for segment k of ``streams(threshold)``
