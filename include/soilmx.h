@@ -576,6 +576,58 @@ int smx_flowpaths(smx_ctx* ctx, smx_flowpath* out, uint64_t struct_size, uint32_
                   uint32_t* straight, uint32_t* diagonal, double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem,
                   uint32_t* profile, uint32_t profile_cap, uint32_t* nprofile);
 int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
+/* ---- dispersed flow: the multiple-flow-direction (MFD) contributing area in fixed point, every cell's donors and receivers, and per
+ *      basin what arrives at its terminal and what leaks over its divides ----
+ * Cells, h(c), wet cells, lakes, the receiver R(c), sinks, basins, first_cell and the rank are those of smx_drainage.
+ * ONE = 2^24. exponent is a u32 from 0 to 16.
+ * The LOWER neighbours of a dry cell c are the in-map cells n among its eight neighbours with h(n) < h(c), plain f64 `<`: a NaN is
+ * never lower and never has a lower neighbour. A dry cell with at least one lower neighbour is a GIVER; sinks and wet cells give
+ * nothing; R(c) is always one of c's lower neighbours.
+ * For a lower neighbour n of c: s = (h(c) - h(n)) * k, k = 1.0 for a straight step and 0x3FE6A09E667F3BCD (0.7071067811865476) for a
+ * diagonal one; w(n) is the product of `exponent` factors s, multiplied left to right, starting from 1.0 (exponent 0: every lower
+ * neighbour weighs 1.0); W is the f64 sum of the w(n) in ascending cell index, starting from 0.0; no operation is contracted.
+ * If W > 0 and W is finite, f(n) = (u32)((w(n) / W) * 16777216.0), truncated; otherwise -- the products overflowed or all underflowed
+ * -- every f(n) is 0. The f(n) sum to at most ONE.
+ * A(c), a u64, is ONE plus what c is given. A giver c hands share(n) = (A(c) * f(n)) >> 24, the product 128 bits wide, to every lower
+ * neighbour n, and the remainder A(c) - sum of the shares to R(c) on top of its share: nothing is lost, and with all f = 0 the cell
+ * behaves exactly as in D8. A(c) is at most cells * ONE < 2^56.
+ * donors(c) is the number of givers among c's neighbours that are higher than c (counted for a wet cell too); receivers(c) the number
+ * of lower neighbours of a giver, 0 for a sink and for a wet cell.
+ * Per basin b, in rank order: inflow_q24 is the sum of A over the basin's terminal cells (the sink, or every wet cell of the lake);
+ * leak_out_q24 the sum of every amount, remainders included, that a giver labelled b hands to a cell of another basin; leak_in_q24
+ * the same sum seen from the receiving basin; peak_q24 the largest A among the basin's dry cells and peak_cell the smallest cell that
+ * holds it (a lake without dry land: 0 and 0xFFFFFFFF); givers counts the basin's givers, split_cells those with receivers(c) >= 2.
+ * So inflow = cells * ONE + leak_in - leak_out for every basin, the inflows sum to dimx * dimy * ONE, and the leak_in sum to the
+ * leak_out. Every figure is a comparison or an exact integer: a host restatement reproduces each bit. */
+typedef struct smx_dispersal_record {    /* 64 bytes; record k belongs to basin k of smx_drainage on the same state */
+  uint32_t first_cell, cells;            /* the basin's identity and D8 size */
+  uint32_t flags;                        /* as smx_basin.flags */
+  uint32_t peak_cell;
+  uint64_t inflow_q24, leak_in_q24, leak_out_q24, peak_q24;
+  uint32_t givers, split_cells;
+  uint32_t reserved[2];                  /* written as 0 */
+} smx_dispersal_record;
+/* *nbasins = the number of basins, whatever cap is; the first min(cap, *nbasins) records are written in rank order, record k at byte
+ * k * struct_size; out may be NULL when cap is 0 (counting only). The planes (NULL = skip) hold dimx*dimy words in cell order -- area:
+ * u64, A(c); divide by 2^24 for cells -- and cover the whole map: only the records are cut at cap. In the ensemble call member i's
+ * records start at out + i * cap_per_member records and nbasins holds one count per member; an empty ensemble: 0, nothing written.
+ * Both calls run on the context's / the ensemble's stream (they see every tick queued before them): the drainage chain with its
+ * statistics on the call's own scratch; k_disp_pending; k_disp_flow in rounds, one ready giver per lane, each lane carrying on with a
+ * receiver its hand-over completed and listing the others for the next round -- the launches are queued in batches, after each batch
+ * one word is read back (a bit per launch, whatever the member count), and the loop ends with the first launch that found its part of the list empty (smx_get_dispersal_rounds:
+ * the launches that found work, and the batches, of the last call); k_disp_fold; k_disp_peak; the RESULTS copied back. No kernel
+ * waits for another lane or workgroup; the result does not depend on the launch shape or on the order of arrival. The calls change
+ * no map, flag, counter or generator and do not touch the results or the scratch of the sibling analyses. A strip context, a null
+ * argument, struct_size == 0, exponent > 16 and records asked for with out == NULL return -2, a context without a device -3. The
+ * scratch -- six u32 planes and one 64-bit plane per cell and two records per basin asked for -- is allocated at first use and
+ * kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable. Maps of up to 65536 cells a side and
+ * 2^32 - 2 cells per call. */
+int smx_dispersal(smx_ctx* ctx, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
+                  uint64_t* area, uint32_t* donors, uint32_t* receivers);
+int smx_ensemble_dispersal(smx_ensemble* e, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap_per_member,
+                           uint32_t* nbasins);
+int smx_get_dispersal_rounds(smx_ctx* ctx, uint32_t* rounds, uint32_t* batches);
+int smx_ensemble_get_dispersal_rounds(smx_ensemble* e, uint32_t* rounds, uint32_t* batches);
 /* ---- the strata read on the device: how much of each soil there is, how thick a soil lies and how deep it is buried, and the
  *      columns under listed cells -- without exporting the map ----
  * A column is walked TOP -> BOTTOM, the inline top record first, then the prev links, one lane per column (k_strata_totals,

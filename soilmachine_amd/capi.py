@@ -162,6 +162,19 @@ class Flowpath(C.Structure):
         return d
 
 
+class Dispersal(C.Structure):
+    """smx_dispersal_record: one basin's record of smx_dispersal / smx_ensemble_dispersal (64 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("flags", C.c_uint32), ("peak_cell", C.c_uint32),
+                ("inflow_q24", C.c_uint64), ("leak_in_q24", C.c_uint64), ("leak_out_q24", C.c_uint64), ("peak_q24", C.c_uint64),
+                ("givers", C.c_uint32), ("split_cells", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        for f in ("inflow", "leak_in", "leak_out", "peak"):
+            d[f] = d[f + "_q24"] / DISPERSAL_ONE               # in cells
+        return d
+
+
 class SoilTotal(C.Structure):
     """smx_soil_total: one soil type's record of smx_soil_totals / smx_ensemble_soil_totals (48 bytes)."""
     _fields_ = [("sections", C.c_uint64), ("cells", C.c_uint64), ("top_cells", C.c_uint64), ("volume_q40", C.c_uint64),
@@ -194,6 +207,8 @@ HILL_NONE = 0xFFFFFFFF                 # the entry / hillslope planes: a wet cel
 HILL_HAND_UNRELIABLE = 1                # smx_hillslope.flags
 PATH_NONE = 0xFFFFFFFF                 # the stem plane: a cell off the stems
 PATH_TERMINAL_WET = 1                  # smx_flowpath.flags
+DISPERSAL_ONE = 1 << 24                # one cell of dispersed area (the area plane, the *_q24 fields)
+DISPERSAL_MAX_EXPONENT = 16
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
 PLANES = {"height": PLANE_HEIGHT, "water": PLANE_WATER, "wfreq": PLANE_WFREQ, "windfreq": PLANE_WINDFREQ}
@@ -220,6 +235,7 @@ SYMBOLS = [
     "smx_through", "smx_ensemble_through", "smx_get_through_sweeps", "smx_ensemble_get_through_sweeps",
     "smx_hillslopes", "smx_ensemble_hillslopes",
     "smx_flowpaths", "smx_ensemble_flowpaths",
+    "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_switches",
 ]
@@ -362,6 +378,10 @@ def load() -> C.CDLL:
     L.smx_ensemble_hillslopes.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_flowpaths.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32)]
     L.smx_ensemble_flowpaths.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_dispersal.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
+    L.smx_ensemble_dispersal.argtypes = [vp, u32, vp, u64, u32, vp]
+    L.smx_get_dispersal_rounds.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.smx_ensemble_get_dispersal_rounds.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.smx_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -53,6 +53,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_streams.h"
 #include "soil_hills.h"
 #include "soil_paths.h"
+#include "soil_disp.h"
 #include "soil_strata.h"
 #include "soil_scratch.h"
 #include <algorithm>
@@ -553,6 +554,45 @@ __global__ void __launch_bounds__(LAKE_LANES) k_path_stem(const LakeMember* __re
   if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   path_stem_group(m, g, blockIdx.x, p.T, p.s.J, p.s.S, p.s.G, p.UP, p.FH, p.FS, p.PA, acc, nbasins + blockIdx.y, nprofile + blockIdx.y, o);
+}
+
+// ---------------- dispersed flow (smx_dispersal / smx_ensemble_dispersal; bodies: soil_disp.h) ----------------
+// Behind the drainage chain with its statistics, on its planes. k_disp_pending holds the height and dry-mark tiles with their halo of
+// one and a slot per cell of the tile (18 KB of LDS); k_disp_flow strides over the round's part of the ready list with at most
+// DISP_FLOW_BLOCKS workgroups: the list's length is read on the device. k_disp_fold's table holds 512 cells' worth of basins (14 KB).
+struct DispPlanes {   // the planes of one call (soil_disp.h)
+  uint32_t *T, *R, *P, *RC, *Q;
+  uint64_t* AQ;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_disp_pending(const LakeMember* __restrict__ tab, DispPlanes p, DispAcc* acc, uint32_t* ring) {
+  __shared__ double hs[(LAKE_TX + 2) * (LAKE_TY + 2)];
+  __shared__ uint32_t ds[(LAKE_TX + 2) * (LAKE_TY + 2)];
+  __shared__ uint32_t sl[LAKE_TX * LAKE_TY];
+  __shared__ uint32_t wc[2];
+  const LakeMember m = tab[blockIdx.y];
+  const uint32_t nt = lake_tiles(m, LAKE_TX, LAKE_TY);
+  if (blockIdx.x >= nt) return;
+  ObsGroup g;
+  disp_pending_group<LAKE_TX, LAKE_TY>(m, g, blockIdx.x, nt, hs, ds, sl, wc, p.P, p.RC, p.Q, p.AQ, acc, ring + DISP_RING * blockIdx.y);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_disp_flow(const LakeMember* __restrict__ tab, uint32_t round, uint32_t exponent, DispPlanes p, DispAcc* acc, uint32_t* ring,
+                                                          uint32_t* busy, uint32_t bit) {
+  const LakeMember m = tab[blockIdx.y];
+  ObsGroup g;
+  disp_flow_group(m, g, blockIdx.x, gridDim.x, round, exponent, p.T, p.R, p.P, p.RC, p.Q, p.AQ, acc, ring + DISP_RING * blockIdx.y, busy, bit);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_disp_fold(const LakeMember* __restrict__ tab, DispPlanes p, DispAcc* acc) {
+  __shared__ DispTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  disp_fold_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.T, p.R, p.RC, p.AQ, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_disp_peak(const LakeMember* __restrict__ tab, DispPlanes p, DispAcc* acc, uint32_t want_donors, uint32_t want_receivers) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  disp_peak_group(m, g, blockIdx.x, p.T, p.P, p.RC, p.AQ, acc, want_donors, want_receivers);
 }
 
 // ---------------- spill analysis (smx_spill / smx_ensemble_spill; bodies: soil_spill.h) ----------------
@@ -2114,6 +2154,7 @@ struct smx_ctx : EventTimer {
   uint64_t batch_epochs = 0, batch_generations = 0, batch_children_lost = 0, grid_passes = 0;
   ForkScratch fork;                   // smx_copy_state into this context
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths: one each
+  AnalysisScratch disp;                                                  // smx_dispersal
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
 };
 
@@ -3694,6 +3735,7 @@ struct smx_ensemble : EventTimer {
   void* h_obs = nullptr; size_t h_obs_cap = 0;
   ForkScratch fork;                       // smx_ensemble_fork
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes, _flowpaths: one each
+  AnalysisScratch disp;                                                  // smx_ensemble_dispersal
   StrataScratch strata;                   // smx_ensemble_soil_totals
 };
 
@@ -4702,6 +4744,80 @@ static int paths_run(const AnalysisCall& c, AnalysisScratch& k, smx_flowpath* ou
   return 0;
 }
 
+// ---- dispersed flow: planes T, B, R of the chain, P, RC, the list plane Q, and the 64-bit plane AQ in the f64 plane's place. The
+// drainage chain with its statistics and ITS records (first_cell, cells and flags of a dispersal record are the basin's), then
+// k_disp_pending. k_disp_flow in the round loop: DISP_BATCH launches, then ONE word back -- a bit per launch that found cells in
+// the range of a member, however many members; a launch that found none ends the loop (every launch retires all cells listed before it and the graph strictly descends in
+// h: giving up after cells + 2 launches cannot happen). k_disp_fold, k_disp_peak; the counts, the two tables and the planes asked
+// for copied back, the last synchronisation. The counter words: DISP_RING per member, then the batch's word.
+static_assert(sizeof(smx_dispersal_record) == 64 && sizeof(DispRec) == sizeof(smx_dispersal_record) && offsetof(smx_dispersal_record, peak_cell) == offsetof(DispRec, peak_cell) &&
+              offsetof(smx_dispersal_record, inflow_q24) == offsetof(DispRec, inflow_q24) && offsetof(smx_dispersal_record, peak_q24) == offsetof(DispRec, peak_q24) &&
+              offsetof(smx_dispersal_record, givers) == offsetof(DispRec, givers), "smx_dispersal_record layout");
+static_assert(sizeof(BasinAcc) % alignof(DispAcc) == 0, "the second table of the result region is aligned");
+static int disp_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
+                    uint64_t* area, uint32_t* donors, uint32_t* receivers) {
+  k.sweeps[0] = 0; k.batches = 0;
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, cap, CAP_CELLS, pl)) return rc;
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm), disp_at = rec_at + (size_t)pl.nrec * sizeof(BasinAcc);
+  need.words = (size_t)pl.words; need.planes = 6; need.f64 = true; need.members = c.nm; need.count_words = (size_t)c.nm * DISP_RING + 16;
+  need.res_bytes = disp_at + (size_t)pl.nrec * sizeof(DispAcc);
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "dispersal", pl.nrec)) return rc;
+  const DispPlanes p{k.plane[0], k.plane[2], k.plane[3], k.plane[4], k.plane[5], reinterpret_cast<uint64_t*>(k.h64)};
+  uint32_t* const B = k.plane[1];
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  BasinAcc* bacc = reinterpret_cast<BasinAcc*>(k.d_res + rec_at);
+  DispAcc* acc = reinterpret_cast<DispAcc*>(k.d_res + disp_at);
+  uint32_t* const ring = k.d_cnt;
+  uint32_t* const d_busy = k.d_cnt + (size_t)c.nm * DISP_RING;
+  uint32_t* const h_busy = k.h_cnt + (size_t)c.nm * DISP_RING;
+  uint64_t largest = 0;
+  for (uint32_t i = 0; i < c.nm; i++) largest = std::max<uint64_t>(largest, c.ms[i]->ncells);
+  const dim3 gw(std::min<unsigned>(pl.gf.x, DISP_FLOW_BLOCKS), pl.gf.y);
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  ok = ok && hipMemsetAsync(ring, 0, (size_t)c.nm * DISP_RING * 4, c.st) == hipSuccess;
+  if (ok) {
+    ok = launch_drain_chain(pl, c.st, k, k.d_tab + c.nm, k.d_tab, p.T, B, p.R, bacc, d_n, nullptr, nullptr);
+    if (ok) hipLaunchKernelGGL(k_disp_pending, pl.gt, pl.wg, 0, c.st, k.d_tab, p, acc, ring);
+  }
+  if (!ok) return analysis_wait(c, false, "the dispersal");
+  uint64_t launched = 0;
+  for (bool done = false; !done;) {
+    if (launched >= largest + 2u) {
+      (void)hipStreamSynchronize(c.st);
+      c.err = std::string(c.who) + ": the ready list did not run empty within " + std::to_string(launched) + " launches (" + std::to_string(largest) + " cells)";
+      return -1;
+    }
+    ok = hipMemsetAsync(d_busy, 0, 4, c.st) == hipSuccess;
+    for (uint32_t j = 0; ok && j < DISP_BATCH; j++) hipLaunchKernelGGL(k_disp_flow, gw, pl.wg, 0, c.st, k.d_tab, (uint32_t)((launched + j) % 3u), exponent, p, acc, ring, d_busy, 1u << j);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = copy_back(c, ok, h_busy, d_busy, 4);
+    if (analysis_wait(c, ok, "the dispersal")) return -1;
+    launched += DISP_BATCH; k.batches++;
+    // (bit j: launch j of the batch found cells in some member's range. Once every list is empty it stays empty, so the set bits are
+    // the batch's first launches, and a clear bit ends the loop.)
+    k.sweeps[0] += (uint32_t)__builtin_popcount(*h_busy);
+    done = *h_busy != (DISP_BATCH == 32u ? 0xFFFFFFFFu : (1u << (DISP_BATCH & 31u)) - 1u);
+  }
+  hipLaunchKernelGGL(k_disp_fold, pl.gs, pl.wg, 0, c.st, k.d_tab, p, acc);
+  hipLaunchKernelGGL(k_disp_peak, pl.gf, pl.wg, 0, c.st, k.d_tab, p, acc, donors ? 1u : 0u, receivers ? 1u : 0u);
+  ok = hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, need.res_bytes);
+  // (smx_dispersal only: one map, off = 0)
+  ok = copy_back(c, ok, area, p.AQ, (size_t)pl.words * 8);
+  ok = copy_back(c, ok, donors, p.P, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, receivers, p.RC, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "the dispersal")) return -1;
+  const BasinAcc* b = reinterpret_cast<const BasinAcc*>(k.h_res + rec_at);
+  const DispAcc* a = reinterpret_cast<const DispAcc*>(k.h_res + disp_at);
+  cut_records<DispRec>(pl, reinterpret_cast<const uint32_t*>(k.h_res), out, struct_size, cap, nbasins,
+                       [a, b](size_t j, DispRec& rec) -> const DispRec& { disp_finish(b[j], a[j], rec); return rec; });
+  return 0;
+}
+
 extern "C" {
 int smx_lakes(smx_ctx* ctx, smx_lake* out, uint64_t struct_size, uint32_t cap, uint32_t* nlakes, uint32_t* labels) {
   if (!ctx) return -2;
@@ -4833,6 +4949,27 @@ int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_s
   HIPCHK(e, hipSetDevice(e->device));
   return paths_run(c, e->paths, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
 }
+int smx_dispersal(smx_ctx* ctx, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint64_t* area, uint32_t* donors,
+                  uint32_t* receivers) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_dispersal", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_dispersal_record", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
+  if (exponent > DISP_MAX_EXPONENT) { ctx->err = "smx_dispersal: exponent is " + std::to_string(exponent) + " (0 to 16)"; return -2; }
+  roctx_range rr("soilmx:dispersal");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return disp_run(c, ctx->disp, exponent, out, struct_size, cap, nbasins, area, donors, receivers);
+}
+int smx_ensemble_dispersal(smx_ensemble* e, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_dispersal", e);
+  int rc;
+  if (exponent > DISP_MAX_EXPONENT) { e->err = "smx_ensemble_dispersal: exponent is " + std::to_string(exponent) + " (0 to 16)"; return -2; }
+  if (!analysis_begin(c, "smx_dispersal_record", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_dispersal");
+  HIPCHK(e, hipSetDevice(e->device));
+  return disp_run(c, e->disp, exponent, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr);
+}
 // (sweeps launched, batches) of the last spill call; (level sweeps, hop sweeps, batches) of the last through call
 static int sweeps_of(const AnalysisScratch& k, std::string& err, const char* who, uint32_t* a, uint32_t* b, uint32_t* batches) {
   if (!a || !b || !batches) { err = std::string(who) + ": a null argument"; return -2; }
@@ -4852,6 +4989,15 @@ int smx_get_through_sweeps(smx_ctx* ctx, uint32_t* level_sweeps, uint32_t* hop_s
 }
 int smx_ensemble_get_through_sweeps(smx_ensemble* e, uint32_t* level_sweeps, uint32_t* hop_sweeps, uint32_t* batches) {
   return e ? sweeps_of(e->through, e->err, "smx_ensemble_get_through_sweeps", level_sweeps, hop_sweeps, batches) : -2;
+}
+// (rounds that found cells in their range, batches) of the last dispersal call
+int smx_get_dispersal_rounds(smx_ctx* ctx, uint32_t* rounds, uint32_t* batches) {
+  uint32_t none;
+  return ctx ? sweeps_of(ctx->disp, ctx->err, "smx_get_dispersal_rounds", rounds, &none, batches) : -2;
+}
+int smx_ensemble_get_dispersal_rounds(smx_ensemble* e, uint32_t* rounds, uint32_t* batches) {
+  uint32_t none;
+  return e ? sweeps_of(e->disp, e->err, "smx_ensemble_get_dispersal_rounds", rounds, &none, batches) : -2;
 }
 
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------

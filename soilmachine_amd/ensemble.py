@@ -299,6 +299,21 @@ class Ensemble:
         count; else at most ``cap`` basins per member. Members may differ in size."""
         return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_flowpaths(self.h, out, C.sizeof(capi.Flowpath), cap, counts), capi.Flowpath, cap)
 
+    def dispersal(self, exponent: int = 1, cap: int | None = None) -> list:
+        """The dispersed-flow records of every member (``smx_ensemble_dispersal``: the same launches whatever the member count): one
+        list of dicts per member, in member order, each as ``Layermap.dispersal(exponent)`` gives it, record k for basin k of
+        ``drainage()``. ``cap`` None: two calls, the basin counts and the fetch sized by the largest; else at most ``cap`` basins per
+        member. Members may differ in size."""
+        exponent = int(exponent)
+        return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_dispersal(self.h, exponent, out, C.sizeof(capi.Dispersal), cap, counts), capi.Dispersal, cap,
+                              count=self._basin_counts)
+
+    def dispersal_rounds(self) -> tuple:
+        """(rounds that found ready cells, batches) of the last ``dispersal()`` (``smx_ensemble_get_dispersal_rounds``)."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_ensemble_get_dispersal_rounds(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def spill(self, cap: int | None = None) -> list:
         """The spill records of every member (``smx_ensemble_spill``: the same launches whatever the member count): one list of
         dicts per member, in member order, each as ``Layermap.spill()`` gives it. ``cap`` None: two calls, the basin counts and the

@@ -322,6 +322,31 @@ class Layermap:
                 r["profile"] = prof[r["profile_at"]:r["profile_at"] + r["steps_max"] + 1].copy()
         return (recs, planes) if planes else recs
 
+    def dispersal(self, exponent: int = 1, area: bool = False, donors: bool = False, receivers: bool = False, cap: int | None = None):
+        """Dispersed flow (``smx_dispersal``): the multiple-flow-direction contributing area next to the D8 one of ``drainage()``. A
+        dry cell splits its water over ALL lower neighbours in proportion to slope ** ``exponent`` (0 to 16; a diagonal step counts
+        0.7071...), in fixed point with one cell = 2^24, so that every figure is an exact integer; what the truncated shares leave
+        goes to the D8 receiver and nothing is lost. One dict per basin, record k for basin k of ``drainage()`` -- ``first_cell``,
+        ``cells`` and ``flags`` (the basin), ``inflow_q24`` (what arrives at the sink or in the lake), ``leak_in_q24`` /
+        ``leak_out_q24`` (what crosses the basin's divides: inflow = cells * 2^24 + leak_in - leak_out), ``peak_q24`` / ``peak_cell``
+        (the largest area on the basin's dry land and the smallest cell that holds it; 0 and 0xFFFFFFFF for a lake without dry
+        land), ``givers`` (dry cells with a lower neighbour) and ``split_cells`` (those with two or more), and the floats
+        ``inflow``, ``leak_in``, ``leak_out`` and ``peak`` in cells. With a plane asked for the result is ``(records, planes)``,
+        ``planes`` a dict of (dimx, dimy) arrays: ``area`` (uint64: divide by 2^24 for cells), ``donors`` (the higher dry
+        neighbours) and ``receivers`` (the lower neighbours of a dry cell), uint32. ``cap`` None: two calls, the basin count and the
+        fetch; else at most ``cap`` basins. Sees every tick queued before it and changes nothing; the number of rounds depends on the
+        map (``dispersal_rounds()``)."""
+        exponent = int(exponent)
+        recs, planes = self._analysis(lambda out, cap, n, *pl: self.L.smx_dispersal(self.h, exponent, out, C.sizeof(capi.Dispersal), cap, n, *pl), capi.Dispersal, cap,
+                                      [("area", area), ("donors", donors), ("receivers", receivers)], dtype={"area": np.uint64}, count=self._basin_count)
+        return (recs, planes) if planes else recs
+
+    def dispersal_rounds(self) -> tuple:
+        """(rounds that found ready cells, batches) of the last ``dispersal()`` (``smx_get_dispersal_rounds``)."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.smx_get_dispersal_rounds(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def hillslopes(self, threshold: int, entry: bool = False, hillslope: bool = False, straight: bool = False, diagonal: bool = False, hand: bool = False,
                    cap: int | None = None):
         """The land beside the channels (``smx_hillslopes``): one dict per segment, record k for segment k of ``streams(threshold)``
