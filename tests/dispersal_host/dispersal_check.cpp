@@ -14,44 +14,8 @@
 //   u32 dimx, u32 dimy, u32 exponent, u32 nbasins, u32 count[cells], u32 nsec, u32 type[nsec], f64 size[nsec], f64 floor[nsec],
 //   u64 area[cells], u32 donors[cells], u32 receivers[cells], 64-byte records[nbasins]
 // Exit status 0 = all equal.
-#include <cstdio>
-#include <cstdlib>
-#include <numeric>
-
 #include "dispersal_host.cpp"
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
-
-struct Input { int dx, dy; std::vector<double> h; std::vector<uint8_t> wet; };
-
-static Input make(const char* kind, int dx, int dy) {
-  Input in{dx, dy, std::vector<double>((size_t)dx * dy), std::vector<uint8_t>((size_t)dx * dy, 0)};
-  const size_t n = in.h.size();
-  std::vector<uint32_t> perm(n);
-  std::iota(perm.begin(), perm.end(), 0u);
-  for (size_t i = n; i > 1; i--) std::swap(perm[i - 1], perm[rnd() % i]);
-  for (size_t c = 0; c < n; c++) {
-    double v = perm[c];
-    if (!strcmp(kind, "ramp")) v = (double)c;
-    if (!strcmp(kind, "plateau")) v = 1024.0;
-    in.h[c] = v * 0.0009765625;
-    if (!strcmp(kind, "lakes")) in.wet[c] = (double)(rnd() >> 11) * (1.0 / 9007199254740992.0) < 0.2 ? 1 : 0;
-  }
-  return in;
-}
-
-static dh_map* host_map(const Input& in) {
-  const size_t n = in.h.size();
-  std::vector<uint32_t> count(n), type;
-  std::vector<double> size, floor;
-  for (size_t c = 0; c < n; c++) {
-    count[c] = in.wet[c] ? 2 : 1;
-    type.push_back(1); size.push_back(in.h[c]); floor.push_back(0.0);
-    if (in.wet[c]) { type.push_back(0); size.push_back(0.5); floor.push_back(in.h[c]); }
-  }
-  return dh_create(in.dx, in.dy, count.data(), type.data(), size.data(), floor.data());
-}
+#include "../analysis_host/analysis_check.h"
 
 struct Want { std::vector<uint64_t> area; std::vector<uint32_t> donors, receivers; std::vector<DispRec> recs; };
 
@@ -180,18 +144,17 @@ static int check(const char* name, const std::vector<Input>& ins) {
   return bad;
 }
 
-template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
+// (this dump has a head of its own, not the common one of analysis_check.h: no magic word, the exponent and the count in front)
 static int check_dump(const char* path) {
   FILE* f = fopen(path, "rb");
   if (!f) { printf("%s: cannot open\n", path); return 1; }
   std::vector<uint32_t> head, count, nsec, type;
   std::vector<double> size, floor;
   Want w;
-  bool ok = rd(f, head, 4);
+  bool ok = take(f, head, 4);
   const size_t n = ok ? (size_t)head[0] * head[1] : 0;
-  ok = ok && rd(f, count, n) && rd(f, nsec, 1) && rd(f, type, nsec[0]) && rd(f, size, nsec[0]) && rd(f, floor, nsec[0]);
-  ok = ok && rd(f, w.area, n) && rd(f, w.donors, n) && rd(f, w.receivers, n) && rd(f, w.recs, head[3]);
+  ok = ok && take(f, count, n) && take(f, nsec, 1) && take(f, type, nsec[0]) && take(f, size, nsec[0]) && take(f, floor, nsec[0]);
+  ok = ok && take(f, w.area, n) && take(f, w.donors, n) && take(f, w.receivers, n) && take(f, w.recs, head[3]);
   fclose(f);
   if (!ok) { printf("%s: short file\n", path); return 1; }
   std::vector<dh_map*> maps{dh_create((int)head[0], (int)head[1], count.data(), type.data(), size.data(), floor.data())};

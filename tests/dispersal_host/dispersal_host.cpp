@@ -5,7 +5,7 @@
 // a workgroup one after the other, the workgroups of a launch one after the other, both first to last or last to first -- legal
 // orders of the device's (the lanes of k_disp_pending and k_disp_fold, which have barriers, always first to last). The flow launches
 // take their own order and their own number of workgroups, so that the ready list is taken first to last or last to first and in
-// one stride or in many. tests/dispersal_host_lib.py builds and binds this file; the product never loads it.
+// one stride or in many. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include <algorithm>
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_disp.h"
@@ -77,48 +77,29 @@ extern "C" {
 // 0; -2 for a bad argument, an exponent above 16 among them; -1 where the ready list did not run empty within cells + 2 launches.
 int dph_dispersal(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int launch_order, uint32_t flow_blocks, uint32_t exponent, uint32_t cap, void* out,
                   uint32_t* nbasins, uint64_t* area, uint32_t* donors, uint32_t* receivers, uint32_t* rounds_out) {
-  if (nm == 0 || !nbasins || !(lanes == 64 || lanes == 128 || lanes == 256) || flow_blocks == 0 || exponent > DISP_MAX_EXPONENT || (!out && cap)) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    const uint64_t most = (uint64_t)m.dimx * m.dimy;
-    m.cap = (uint32_t)(cap < most ? cap : most);
-    words += most; nrec += m.cap;
-  }
-  Planes p;   // (as the device's planes: whatever the last call left)
-  p.T.assign(words, 0xDEADBEEFu); p.B.assign(words, 0xDEADBEEFu); p.R.assign(words, 0xDEADBEEFu); p.P.assign(words, 0xDEADBEEFu);
-  std::vector<uint32_t> RC(words, 0xDEADBEEFu), Q(words, 0xDEADBEEFu);
+  if (nm == 0 || !nbasins || !lanes_ok(lanes) || flow_blocks == 0 || exponent > DISP_MAX_EXPONENT || (!out && cap)) return -2;
+  const Members pl = plan_members(maps, nm, cap, CAP_CELLS);
+  const uint64_t words = pl.words;
+  Planes p;
+  std::vector<uint32_t> RC, Q;
+  poison({&p.T, &p.B, &p.R, &p.P, &RC, &Q}, words);
   std::vector<uint64_t> AQ(words, 0xABABABABABABABABull);
-  std::vector<BasinAcc> bacc(nrec ? nrec : 1);
-  std::vector<DispAcc> acc(nrec ? nrec : 1);
-  memset(bacc.data(), 0xAB, bacc.size() * sizeof(BasinAcc));
-  memset(acc.data(), 0xAB, acc.size() * sizeof(DispAcc));
+  std::vector<BasinAcc> bacc = poisoned_records<BasinAcc>(pl.nrec);
+  std::vector<DispAcc> acc = poisoned_records<DispAcc>(pl.nrec);
   std::vector<uint32_t> ring((size_t)nm * DISP_RING, 0u);   // (the library clears them in front of the chain)
   const int desc = launch_order & 1, ldesc = (launch_order >> 1) & 1, fo = (launch_order ^ (launch_order >> 2)) & 3;
   uint32_t rounds = 0;
-  switch (variant) {
-    case 0: rounds = run_disp<16, 64, 512>(tab, lanes, desc, ldesc, fo, flow_blocks, exponent, p, RC, Q, AQ, bacc, acc, ring, nbasins, donors != nullptr, receivers != nullptr); break;   // the kernels' own shape
-    case 1: rounds = run_disp<8, 8, 256>(tab, lanes, desc, ldesc, fo, flow_blocks, exponent, p, RC, Q, AQ, bacc, acc, ring, nbasins, donors != nullptr, receivers != nullptr); break;
-    case 2: rounds = run_disp<5, 7, 320>(tab, lanes, desc, ldesc, fo, flow_blocks, exponent, p, RC, Q, AQ, bacc, acc, ring, nbasins, donors != nullptr, receivers != nullptr); break;
-    case 3: rounds = run_disp<32, 4, 1024>(tab, lanes, desc, ldesc, fo, flow_blocks, exponent, p, RC, Q, AQ, bacc, acc, ring, nbasins, donors != nullptr, receivers != nullptr); break;
-    default: return -2;
-  }
+  if (!with_shape<TILE_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        rounds = run_disp<S::TX, S::TY, S::SLOTS>(pl.tab, lanes, desc, ldesc, fo, flow_blocks, exponent, p, RC, Q, AQ, bacc, acc, ring, nbasins, donors != nullptr,
+                                                  receivers != nullptr);
+      })) return -2;
   if (rounds == 0xFFFFFFFFu) return -1;
   if (rounds_out) *rounds_out = rounds;
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nbasins[i] < tab[i].cap ? nbasins[i] : tab[i].cap;
-    for (uint32_t r = 0; r < w; r++) {
-      DispRec rec;
-      disp_finish(bacc[tab[i].rec0 + r], acc[tab[i].rec0 + r], rec);
-      memcpy(static_cast<char*>(out) + ((size_t)i * cap + r) * sizeof(DispRec), &rec, sizeof(rec));
-    }
-  }
-  if (area) memcpy(area, AQ.data(), words * 8);
-  if (donors) memcpy(donors, p.P.data(), words * 4);
-  if (receivers) memcpy(receivers, RC.data(), words * 4);
+  cut_records<DispRec>(pl, nbasins, cap, out, sizeof(DispRec), [&](size_t j, DispRec& rec) { disp_finish(bacc[j], acc[j], rec); });
+  copy_plane(area, AQ.data(), words);
+  copy_plane(donors, p.P.data(), words);
+  copy_plane(receivers, RC.data(), words);
   return 0;
 }
 

@@ -11,35 +11,8 @@
 //   u32 magic 0x4E415244, i32 dimx, i32 dimy, u32 nsec, u32 count[cells], u32 type[nsec], f64 size[nsec], f64 floor[nsec],
 //   u32 nbasins, u32 receivers[cells], u32 labels[cells], u32 area[cells], 48-byte records[nbasins]
 // Exit status 0 = all equal.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <numeric>
-
 #include "drainage_host.cpp"
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
-
-struct Input { int dx, dy; std::vector<double> h; std::vector<uint8_t> wet; };
-
-static Input make(const char* kind, int dx, int dy) {
-  Input in{dx, dy, std::vector<double>((size_t)dx * dy), std::vector<uint8_t>((size_t)dx * dy, 0)};
-  const size_t n = in.h.size();
-  std::vector<uint32_t> perm(n);
-  std::iota(perm.begin(), perm.end(), 0u);
-  for (size_t i = n; i > 1; i--) std::swap(perm[i - 1], perm[rnd() % i]);
-  for (size_t c = 0; c < n; c++) {
-    const int x = (int)(c / dy), y = (int)(c % dy);
-    double v = perm[c];
-    if (!strcmp(kind, "cone")) v = ((x - dx / 2) * (x - dx / 2) + (y - dy / 2) * (y - dy / 2)) * 16384.0 + perm[c];
-    if (!strcmp(kind, "ramp")) v = (double)c;
-    if (!strcmp(kind, "plateau")) v = 1024.0;
-    in.h[c] = v * 0.0009765625;
-    if (!strcmp(kind, "lakes")) in.wet[c] = (double)(rnd() >> 11) * (1.0 / 9007199254740992.0) < 0.2 ? 1 : 0;
-  }
-  return in;
-}
+#include "../analysis_host/analysis_check.h"
 
 struct Want { std::vector<uint32_t> recv, label, area, cells, wetc, x0, y0, x1, y1; };
 static Want plain(const Input& in) {
@@ -93,18 +66,6 @@ static Want plain(const Input& in) {
   return w;
 }
 
-static dh_map* host_map(const Input& in) {
-  const size_t n = in.h.size();
-  std::vector<uint32_t> count(n), type;
-  std::vector<double> size, floor;
-  for (size_t c = 0; c < n; c++) {
-    count[c] = in.wet[c] ? 2 : 1;
-    type.push_back(1); size.push_back(in.h[c]); floor.push_back(0.0);
-    if (in.wet[c]) { type.push_back(0); size.push_back(0.5); floor.push_back(in.h[c]); }
-  }
-  return dh_create(in.dx, in.dy, count.data(), type.data(), size.data(), floor.data());
-}
-
 static int check(const char* name, const std::vector<Input>& ins) {
   std::vector<dh_map*> maps;
   std::vector<Want> wants;
@@ -143,24 +104,16 @@ static int check(const char* name, const std::vector<Input>& ins) {
   return bad;
 }
 
-template <class T> static bool take(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 static int check_dump(const char* path) {
-  FILE* f = fopen(path, "rb");
-  if (!f) { printf("FAIL cannot open %s\n", path); return 1; }
-  uint32_t head[4] = {0, 0, 0, 0}, nb = 0;
-  std::vector<uint32_t> count, type, recv, label, area;
-  std::vector<double> size, floor;
+  Columns in;
+  uint32_t nb = 0;
+  std::vector<uint32_t> recv, label, area;
   std::vector<BasinRec> recs;
-  bool ok = fread(head, 4, 4, f) == 4 && head[0] == 0x4E415244u && (int32_t)head[1] > 0 && (int32_t)head[2] > 0 && head[1] <= 4096u && head[2] <= 4096u;
-  const size_t n = ok ? (size_t)head[1] * head[2] : 0;
-  ok = ok && take(f, count, n) && take(f, type, head[3]) && take(f, size, head[3]) && take(f, floor, head[3]);
-  uint64_t sum = 0;
-  for (uint32_t c : count) sum += c;
-  ok = ok && sum == head[3] && fread(&nb, 4, 1, f) == 1 && nb <= n && take(f, recv, n) && take(f, label, n) && take(f, area, n) && take(f, recs, nb);
-  fclose(f);
-  if (!ok) { printf("FAIL %s is not a dump\n", path); return 1; }
-  dh_map* h = dh_create((int)head[1], (int)head[2], count.data(), type.data(), size.data(), floor.data());
+  if (!read_dump(path, 0x4E415244u, in, [&](FILE* f) {
+        return fread(&nb, 4, 1, f) == 1 && nb <= in.cells && take(f, recv, in.cells) && take(f, label, in.cells) && take(f, area, in.cells) && take(f, recs, nb);
+      })) return 1;
+  const size_t n = in.cells;
+  dh_map* h = in.map();
   int bad = 0;
   for (int v = 0; v < dh_variants(); v++)
     for (uint32_t lanes : {64u, 256u})
@@ -174,20 +127,11 @@ static int check_dump(const char* path) {
         if (!same) { printf("FAIL %s variant %d lanes %u order %d: %u basins, expected %u\n", path, v, lanes, order, got, nb); bad++; }
       }
   dh_destroy(h);
-  const char* name = strrchr(path, '/');
-  printf("%-32s %4ux%-4u %6u basins  %s\n", name ? name + 1 : path, head[1], head[2], nb, bad ? "FAILED" : "ok");
+  printf("%-32s %4ux%-4u %6u basins  %s\n", file_name(path), in.dimx, in.dimy, nb, bad ? "FAILED" : "ok");
   return bad;
 }
 
 int main(int argc, char** argv) {
-  int bad = 0;
-  if (argc > 1) {
-    for (int i = 1; i < argc; i++) bad += check_dump(argv[i]);
-    return bad ? 1 : 0;
-  }
-  const int dims[2][2] = {{33, 47}, {96, 80}};
-  for (const auto& d : dims)
-    for (const char* kind : {"cone", "ramp", "plateau", "random", "lakes"}) bad += check(kind, {make(kind, d[0], d[1])});
-  bad += check("three maps", {make("lakes", 33, 47), make("cone", 70, 1), make("random", 1, 70)});
-  return bad ? 1 : 0;
+  return check_main(argc, argv, check_dump, {"cone", "ramp", "plateau", "random", "lakes"}, {{"lakes", 33, 47}, {"cone", 70, 1}, {"random", 1, 70}},
+                    [](const char* name, const std::vector<MapSpec>& specs) { return check(name, make_all(specs)); });
 }

@@ -4,24 +4,12 @@
 // The same headers the kernels are made of, compiled by g++ (-ffp-contract=off) and run with the lanes of a workgroup looped one
 // after the other and the workgroups of a launch one after the other (in ascending or descending order; lanes_descending: the lanes
 // of every workgroup last to first as well): legal orders of the device's. A map is the top records of a snapshot's columns; several
-// maps share the planes as the members of an ensemble do. tests/drainage_host_lib.py builds and binds this file; the product never
+// maps share the planes as the members of an ensemble do. tests/analysis_host_lib.py builds and binds this file; the product never
 // loads it.
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-#include <vector>
-
-#define SMX_D inline
-#define SMX_HOSTSIM 1
-#include "../../soilmachine_amd/csrc/soil_core.h"
+#include "../analysis_host/analysis_host.h"
 #include "../../soilmachine_amd/csrc/soil_drain.h"
 
-using namespace smx;
-
-struct dh_map {
-  int dimx, dimy;
-  std::vector<Sec> cells;
-};
+using dh_map = ah_map;
 
 struct DrainHostGroup {   // a workgroup whose lanes the caller runs one after the other
   uint32_t n;
@@ -39,8 +27,6 @@ struct DrainHostLane {
   uint32_t hi() const { return l + 1u; }
   void barrier() const {}
 };
-
-static inline uint32_t nth(uint32_t b, uint32_t nb, int descending) { return descending ? nb - 1u - b : b; }
 
 struct Planes { std::vector<uint32_t> T, B, R, P, AR; };
 
@@ -97,29 +83,17 @@ static void run_drainage(const std::vector<LakeMember>& tab, uint32_t lanes, int
 
 extern "C" {
 
-// columns bottom -> top in cell order (the snapshot layout): a map keeps each column's top record
 dh_map* dh_create(int dimx, int dimy, const uint32_t* count, const uint32_t* type, const double* size, const double* floor) {
-  dh_map* m = new dh_map();
-  m->dimx = dimx; m->dimy = dimy;
-  const size_t n = (size_t)dimx * dimy;
-  m->cells.resize(n);
-  size_t off = 0;
-  for (size_t i = 0; i < n; i++) {
-    Sec c; c.size = c.floor = c.sat = 0; c.type = EMPTY; c.prev = NIL;
-    if (count[i]) { const size_t t = off + count[i] - 1; c.size = size[t]; c.floor = floor[t]; c.type = type[t]; }
-    off += count[i];
-    m->cells[i] = c;
-  }
-  return m;
+  return ah_create(dimx, dimy, count, type, size, floor);
 }
 void dh_destroy(dh_map* m) { delete m; }
 
-int dh_variants() { return 4; }
+int dh_variants() { return (int)std::size(TILE_SHAPES); }
 // (tile columns, tile rows, slots of the statistics table) of a variant
 int dh_variant(int v, int* tx, int* ty, int* slots) {
-  static const int t[4][3] = {{16, 64, 512}, {8, 8, 256}, {5, 7, 320}, {32, 4, 1024}};
-  if (v < 0 || v >= 4) return -2;
-  *tx = t[v][0]; *ty = t[v][1]; *slots = t[v][2];
+  const Shape* s = shape_at(TILE_SHAPES, v);
+  if (!s) return -2;
+  *tx = s->tx; *ty = s->ty; *slots = s->slots;
   return 0;
 }
 
@@ -130,46 +104,28 @@ int dh_variant(int v, int* tx, int* ty, int* slots) {
 // first in the steps without a barrier. 0, or -2 for a bad argument.
 int dh_drainage(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t cap, void* out, uint32_t* nbasins,
                 uint32_t* receivers, uint32_t* labels, uint32_t* area) {
-  if (nm == 0 || !(lanes == 64 || lanes == 128 || lanes == 256)) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    const uint64_t most = (uint64_t)m.dimx * m.dimy;
-    m.cap = (uint32_t)(cap < most ? cap : most);
-    words += most; nrec += m.cap;
-  }
-  Planes p;   // (as the device's planes: whatever the last call left)
-  p.T.assign(words, 0xDEADBEEFu); p.B.assign(words, 0xDEADBEEFu); p.R.assign(words, 0xDEADBEEFu);
-  if (area) { p.P.assign(words, 0xDEADBEEFu); p.AR.assign(words, 0xDEADBEEFu); }
-  std::vector<BasinAcc> acc(nrec ? nrec : 1);
-  memset(acc.data(), 0xAB, acc.size() * sizeof(BasinAcc));
+  if (nm == 0 || !lanes_ok(lanes)) return -2;
+  const Members pl = plan_members(maps, nm, cap, CAP_CELLS);
+  const std::vector<LakeMember>& tab = pl.tab;
+  const uint64_t words = pl.words;
+  Planes p;
+  poison({&p.T, &p.B, &p.R}, words);
+  if (area) poison({&p.P, &p.AR}, words);
+  std::vector<BasinAcc> acc = poisoned_records<BasinAcc>(pl.nrec);
   const int desc = order & 1, ldesc = (order >> 1) & 1;
-  switch (variant) {
-    case 0: run_drainage<16, 64, 512>(tab, lanes, desc, ldesc, area != nullptr, p, acc, nbasins); break;   // the kernels' own shape
-    case 1: run_drainage<8, 8, 256>(tab, lanes, desc, ldesc, area != nullptr, p, acc, nbasins); break;
-    case 2: run_drainage<5, 7, 320>(tab, lanes, desc, ldesc, area != nullptr, p, acc, nbasins); break;     // a tile no dimension is a multiple of
-    case 3: run_drainage<32, 4, 1024>(tab, lanes, desc, ldesc, area != nullptr, p, acc, nbasins); break;
-    default: return -2;
-  }
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nbasins[i] < tab[i].cap ? nbasins[i] : tab[i].cap;
-    for (uint32_t r = 0; r < w; r++) {
-      BasinRec rec;
-      drain_finish(acc[tab[i].rec0 + r], rec);
-      memcpy(static_cast<char*>(out) + ((size_t)i * cap + r) * sizeof(BasinRec), &rec, sizeof(rec));
-    }
-  }
+  if (!with_shape<TILE_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        run_drainage<S::TX, S::TY, S::SLOTS>(tab, lanes, desc, ldesc, area != nullptr, p, acc, nbasins);
+      })) return -2;
+  cut_records<BasinRec>(pl, nbasins, cap, out, sizeof(BasinRec), [&](size_t j, BasinRec& rec) { drain_finish(acc[j], rec); });
   if (receivers)
     for (uint32_t i = 0; i < nm; i++)
       for (uint64_t c = 0, n = (uint64_t)tab[i].dimx * tab[i].dimy; c < n; c++) {
         const uint32_t r = p.R[tab[i].off + c];
         receivers[tab[i].off + c] = r == DRAIN_NONE ? DRAIN_NONE : r - tab[i].off;
       }
-  if (labels) memcpy(labels, p.T.data(), words * 4);
-  if (area) memcpy(area, p.AR.data(), words * 4);
+  copy_plane(labels, p.T.data(), words);
+  copy_plane(area, p.AR.data(), words);
   return 0;
 }
 

@@ -5,7 +5,7 @@
 // The same headers the kernels are made of, compiled by g++ (-ffp-contract=off) and run as tests/drainage_host runs them: the lanes of
 // a workgroup one after the other, the workgroups of a launch one after the other, both first to last or last to first -- legal
 // orders of the device's (the lanes of k_path_fold, which has barriers, always first to last). The maps, the lane groups and the tile
-// variants are those of the drainage host build. tests/flowpaths_host_lib.py builds and binds this file; the product never loads it.
+// variants are those of the drainage host build. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_paths.h"
 
@@ -81,25 +81,15 @@ extern "C" {
 int fh_flowpaths(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int launch_order, uint32_t cap, void* out, uint32_t* nbasins, uint32_t* terminal,
                  uint32_t* straight, uint32_t* diagonal, double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem, uint32_t* profile, uint32_t profile_cap,
                  uint32_t* nprofile, uint32_t* rounds_out) {
-  if (nm == 0 || !nbasins || !nprofile || !(lanes == 64 || lanes == 128 || lanes == 256) || (profile_cap && (!profile || nm != 1))) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0, largest = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    const uint64_t most = (uint64_t)m.dimx * m.dimy;
-    m.cap = (uint32_t)(cap < most ? cap : most);
-    words += most; nrec += m.cap;
-    if (most > largest) largest = most;
-  }
-  const uint32_t rounds = hill_rounds(largest - 1u);
+  if (nm == 0 || !nbasins || !nprofile || !lanes_ok(lanes) || (profile_cap && (!profile || nm != 1))) return -2;
+  const Members pl = plan_members(maps, nm, cap, CAP_CELLS);
+  const uint64_t words = pl.words;
+  const uint32_t rounds = hill_rounds(pl.largest - 1u);
   if (rounds_out) *rounds_out = rounds;
-  std::vector<std::vector<uint32_t>> plane(10);   // (as the device's planes: whatever the last call left)
-  for (auto& v : plane) v.assign(words, 0xDEADBEEFu);
+  std::vector<std::vector<uint32_t>> plane(10);
+  for (auto& v : plane) poison({&v}, words);
   std::vector<uint64_t> up(words, 0xABABABABABABABABull);
-  std::vector<PathAcc> acc(nrec ? nrec : 1);
-  memset(acc.data(), 0xAB, acc.size() * sizeof(PathAcc));
+  std::vector<PathAcc> acc = poisoned_records<PathAcc>(pl.nrec);
   const uint32_t pcap = profile_cap < words ? profile_cap : (uint32_t)words;
   std::vector<uint32_t> prof(pcap ? pcap : 1, 0xDEADBEEFu);
   PathOut o;
@@ -107,28 +97,18 @@ int fh_flowpaths(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, 
   o.upstream = nullptr; o.source = nullptr; o.profile = pcap ? prof.data() : nullptr;
   const int desc = launch_order & 1, ldesc = (launch_order >> 1) & 1, upo = (launch_order ^ (launch_order >> 2)) & 3;
   PathHostOut res{};
-  switch (variant) {
-    case 0: run_paths<16, 64, 512>(tab, lanes, desc, ldesc, upo, rounds, plane, up, acc, nbasins, nprofile, o, upstream != nullptr, source != nullptr, res); break;   // the kernels' own shape
-    case 1: run_paths<8, 8, 256>(tab, lanes, desc, ldesc, upo, rounds, plane, up, acc, nbasins, nprofile, o, upstream != nullptr, source != nullptr, res); break;
-    case 2: run_paths<5, 7, 320>(tab, lanes, desc, ldesc, upo, rounds, plane, up, acc, nbasins, nprofile, o, upstream != nullptr, source != nullptr, res); break;
-    case 3: run_paths<32, 4, 1024>(tab, lanes, desc, ldesc, upo, rounds, plane, up, acc, nbasins, nprofile, o, upstream != nullptr, source != nullptr, res); break;
-    default: return -2;
-  }
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nbasins[i] < tab[i].cap ? nbasins[i] : tab[i].cap;
-    for (uint32_t r = 0; r < w; r++) {
-      PathRec rec;
-      path_finish(acc[tab[i].rec0 + r], rec);
-      memcpy(static_cast<char*>(out) + ((size_t)i * cap + r) * sizeof(PathRec), &rec, sizeof(rec));
-    }
-  }
-  if (terminal) memcpy(terminal, res.terminal, words * 4);
-  if (straight) memcpy(straight, res.straight, words * 4);
-  if (diagonal) memcpy(diagonal, res.diagonal, words * 4);
-  if (drop) memcpy(drop, res.drop, words * 8);
-  if (upstream) memcpy(upstream, res.upstream, words * 4);
-  if (source) memcpy(source, res.source, words * 4);
-  if (stem) memcpy(stem, res.stem, words * 4);
+  if (!with_shape<TILE_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        run_paths<S::TX, S::TY, S::SLOTS>(pl.tab, lanes, desc, ldesc, upo, rounds, plane, up, acc, nbasins, nprofile, o, upstream != nullptr, source != nullptr, res);
+      })) return -2;
+  cut_records<PathRec>(pl, nbasins, cap, out, sizeof(PathRec), [&](size_t j, PathRec& rec) { path_finish(acc[j], rec); });
+  copy_plane(terminal, res.terminal, words);
+  copy_plane(straight, res.straight, words);
+  copy_plane(diagonal, res.diagonal, words);
+  if (drop) memcpy(drop, res.drop, words * 8);   // (the up-walk's 64-bit words)
+  copy_plane(upstream, res.upstream, words);
+  copy_plane(source, res.source, words);
+  copy_plane(stem, res.stem, words);
   if (pcap) memcpy(profile, prof.data(), (size_t)(pcap < nprofile[0] ? pcap : nprofile[0]) * 4);
   return 0;
 }

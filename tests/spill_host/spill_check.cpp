@@ -10,30 +10,8 @@
 //   u32 magic 0x4C495053, i32 dimx, i32 dimy, u32 nsec, u32 count[cells], u32 type[nsec], f64 size[nsec], f64 floor[nsec],
 //   u32 nbasins, 64-byte records[nbasins], f64 filled[cells]
 // Exit status 0 = all equal.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-
 #include "spill_host.cpp"
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
-
-static dh_map* make(const char* kind, int dx, int dy) {
-  const size_t n = (size_t)dx * dy;
-  std::vector<uint32_t> count(n), type;
-  std::vector<double> size, floor;
-  for (size_t c = 0; c < n; c++) {
-    double h = (double)(rnd() % 4096) * 0.0009765625;
-    if (!strcmp(kind, "plateau")) h = 1.0;
-    if (!strcmp(kind, "sawtooth")) h = (c % 2 ? 1.0 : 0.25) + (double)(c / dy) * 4.0;
-    const bool wet = !strcmp(kind, "lakes") && rnd() % 5 == 0;
-    count[c] = wet ? 2 : 1;
-    type.push_back(1); size.push_back(h); floor.push_back(0.0);
-    if (wet) { type.push_back(0); size.push_back(0.5); floor.push_back(h); }
-  }
-  return dh_create(dx, dy, count.data(), type.data(), size.data(), floor.data());
-}
+#include "../analysis_host/analysis_check.h"
 
 struct Result { std::vector<uint32_t> nb; std::vector<SpillRec> recs; std::vector<double> filled; uint32_t sweeps = 0, batches = 0; };
 
@@ -75,24 +53,14 @@ static int check(const char* name, const std::vector<dh_map*>& maps) {
   return bad;
 }
 
-template <class T> static bool take(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 static int check_dump(const char* path) {
-  FILE* f = fopen(path, "rb");
-  if (!f) { printf("FAIL cannot open %s\n", path); return 1; }
-  uint32_t head[4] = {0, 0, 0, 0}, nb = 0;
-  std::vector<uint32_t> count, type;
-  std::vector<double> size, floor, filled;
+  Columns in;
+  uint32_t nb = 0;
+  std::vector<double> filled;
   std::vector<SpillRec> recs;
-  bool ok = fread(head, 4, 4, f) == 4 && head[0] == 0x4C495053u && (int32_t)head[1] > 0 && (int32_t)head[2] > 0 && head[1] <= 4096u && head[2] <= 4096u;
-  const size_t n = ok ? (size_t)head[1] * head[2] : 0;
-  ok = ok && take(f, count, n) && take(f, type, head[3]) && take(f, size, head[3]) && take(f, floor, head[3]);
-  uint64_t sum = 0;
-  for (uint32_t c : count) sum += c;
-  ok = ok && sum == head[3] && fread(&nb, 4, 1, f) == 1 && nb <= n && take(f, recs, nb) && take(f, filled, n);
-  fclose(f);
-  if (!ok) { printf("FAIL %s is not a dump\n", path); return 1; }
-  std::vector<dh_map*> maps{dh_create((int)head[1], (int)head[2], count.data(), type.data(), size.data(), floor.data())};
+  if (!read_dump(path, 0x4C495053u, in, [&](FILE* f) { return fread(&nb, 4, 1, f) == 1 && nb <= in.cells && take(f, recs, nb) && take(f, filled, in.cells); })) return 1;
+  const size_t n = in.cells;
+  std::vector<dh_map*> maps{in.map()};
   int bad = 0;
   for (int v = 0; v < sh_variants(); v++)
     for (uint32_t lanes : {64u, 256u})
@@ -103,26 +71,11 @@ static int check_dump(const char* path) {
         if (!same) { printf("FAIL %s variant %d lanes %u order %d: %u basins, expected %u\n", path, v, lanes, order, got.nb[0], nb); bad++; }
       }
   dh_destroy(maps[0]);
-  const char* name = strrchr(path, '/');
-  printf("%-32s %4ux%-4u %6u basins  %s\n", name ? name + 1 : path, head[1], head[2], nb, bad ? "FAILED" : "ok");
+  printf("%-32s %4ux%-4u %6u basins  %s\n", file_name(path), in.dimx, in.dimy, nb, bad ? "FAILED" : "ok");
   return bad;
 }
 
 int main(int argc, char** argv) {
-  int bad = 0;
-  if (argc > 1) {
-    for (int i = 1; i < argc; i++) bad += check_dump(argv[i]);
-    return bad ? 1 : 0;
-  }
-  const int dims[2][2] = {{33, 47}, {96, 80}};
-  for (const auto& d : dims)
-    for (const char* kind : {"random", "lakes", "plateau", "sawtooth"}) {
-      std::vector<dh_map*> maps{make(kind, d[0], d[1])};
-      bad += check(kind, maps);
-      dh_destroy(maps[0]);
-    }
-  std::vector<dh_map*> three{make("lakes", 33, 47), make("sawtooth", 70, 1), make("random", 1, 70)};
-  bad += check("three maps", three);
-  for (dh_map* m : three) dh_destroy(m);
-  return bad ? 1 : 0;
+  return check_main(argc, argv, check_dump, {"random", "lakes", "plateau", "sawtooth"}, {{"lakes", 33, 47}, {"sawtooth", 70, 1}, {"random", 1, 70}},
+                    [](const char* name, const std::vector<MapSpec>& specs) { return check_columns(name, specs, check); });
 }

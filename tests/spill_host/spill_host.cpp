@@ -5,7 +5,7 @@
 // after the other and the workgroups of a launch one after the other, in ascending or descending order, as drainage_host does; the
 // relax sweeps run lane by lane (the body has no barrier), so the order decides how far a level travels in one sweep -- and must not
 // decide where it ends. The host loop around the sweeps is the library's: batches of SPILL_BATCH, stop after the batch that holds a
-// sweep that changed nothing, give up after nbasins + 2. tests/spill_host_lib.py builds and binds this file; the product never loads it.
+// sweep that changed nothing, give up after nbasins + 2. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_spill.h"
 
@@ -82,12 +82,12 @@ static int run_spill(std::vector<LakeMember> tab, uint32_t lanes, int descending
 
 extern "C" {
 
-int sh_variants() { return 4; }
+int sh_variants() { return (int)std::size(PASS_SHAPES); }
 // (tile columns, tile rows, slots of the pass table, slots of the store table) of a variant
 int sh_variant(int v, int* tx, int* ty, int* pslots, int* slots) {
-  static const int t[4][4] = {{16, 64, 1024, 512}, {8, 8, 64, 256}, {5, 7, 40, 320}, {32, 4, 128, 1024}};
-  if (v < 0 || v >= 4) return -2;
-  *tx = t[v][0]; *ty = t[v][1]; *pslots = t[v][2]; *slots = t[v][3];
+  const Shape* s = shape_at(PASS_SHAPES, v);
+  if (!s) return -2;
+  *tx = s->tx; *ty = s->ty; *pslots = s->pslots; *slots = s->slots;
   return 0;
 }
 uint32_t sh_batch() { return SPILL_BATCH; }
@@ -98,38 +98,20 @@ uint32_t sh_batch() { return SPILL_BATCH; }
 // settle within the bound.
 int sh_spill(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t cap, void* out, uint64_t struct_size, uint32_t* nbasins,
              double* filled, uint32_t* sweeps, uint32_t* batches) {
-  if (nm == 0 || struct_size == 0 || !(lanes == 64 || lanes == 128 || lanes == 256) || !nbasins || !sweeps || !batches || (!out && cap)) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;
-    words += (uint64_t)m.dimx * m.dimy;
-  }
-  std::vector<double> H(words, -12345.0);
+  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || !nbasins || !sweeps || !batches || (!out && cap)) return -2;
+  Members pl = plan_members(maps, nm, cap, CAP_NONE);
+  std::vector<double> H(pl.words, -12345.0);
   std::vector<SpillAcc> acc;
   const int desc = order & 1, ldesc = (order >> 1) & 1;
-  int rc;
-  switch (variant) {
-    case 0: rc = run_spill<16, 64, 1024, 512>(tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches); break;   // the kernels' own shape
-    case 1: rc = run_spill<8, 8, 64, 256>(tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches); break;
-    case 2: rc = run_spill<5, 7, 40, 320>(tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches); break;       // a tile no dimension is a multiple of
-    case 3: rc = run_spill<32, 4, 128, 1024>(tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches); break;
-    default: return -2;
-  }
+  int rc = 0;
+  if (!with_shape<PASS_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        rc = run_spill<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches);
+      })) return -2;
   if (rc) return rc;
-  uint64_t rec0 = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nbasins[i] < cap ? nbasins[i] : cap;
-    for (uint32_t r = 0; r < w; r++) {
-      SpillRec rec;
-      spill_finish(acc[rec0 + r], rec);
-      memcpy(static_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, struct_size < sizeof(rec) ? (size_t)struct_size : sizeof(rec));
-    }
-    rec0 += nbasins[i];
-  }
-  if (filled) memcpy(filled, H.data(), words * 8);
+  plan_basins(pl, nbasins);   // (as run_spill laid its copy of the table out)
+  cut_records<SpillRec>(pl, nbasins, cap, out, (size_t)struct_size, [&](size_t j, SpillRec& rec) { spill_finish(acc[j], rec); });
+  copy_plane(filled, H.data(), pl.words);
   return 0;
 }
 

@@ -10,35 +10,8 @@
 //   u32 magic 0x4D525453, i32 dimx, i32 dimy, u32 nsec, u32 count[cells], u32 type[nsec], f64 size[nsec], f64 floor[nsec],
 //   u32 threshold, u32 nstreams, u32 order[cells], u32 segments[cells], u32 reach[cells], u32 heads[cells], 64-byte records[nstreams]
 // Exit status 0 = all equal.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <numeric>
-
 #include "streams_host.cpp"
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
-
-struct Input { int dx, dy; std::vector<double> h; std::vector<uint8_t> wet; };
-
-static Input make(const char* kind, int dx, int dy) {
-  Input in{dx, dy, std::vector<double>((size_t)dx * dy), std::vector<uint8_t>((size_t)dx * dy, 0)};
-  const size_t n = in.h.size();
-  std::vector<uint32_t> perm(n);
-  std::iota(perm.begin(), perm.end(), 0u);
-  for (size_t i = n; i > 1; i--) std::swap(perm[i - 1], perm[rnd() % i]);
-  for (size_t c = 0; c < n; c++) {
-    const int x = (int)(c / dy), y = (int)(c % dy);
-    double v = perm[c];
-    if (!strcmp(kind, "cone")) v = ((x - dx / 2) * (x - dx / 2) + (y - dy / 2) * (y - dy / 2)) * 16384.0 + perm[c];
-    if (!strcmp(kind, "ramp")) v = (double)c;
-    if (!strcmp(kind, "plateau")) v = 1024.0;
-    in.h[c] = v * 0.0009765625;
-    if (!strcmp(kind, "lakes")) in.wet[c] = (double)(rnd() >> 11) * (1.0 / 9007199254740992.0) < 0.2 ? 1 : 0;
-  }
-  return in;
-}
+#include "../analysis_host/analysis_check.h"
 
 struct Want { std::vector<uint32_t> order, seg, reach, heads; std::vector<StreamRec> recs; };
 static Want plain(const Input& in, uint32_t threshold) {
@@ -113,18 +86,6 @@ static Want plain(const Input& in, uint32_t threshold) {
   return w;
 }
 
-static dh_map* host_map(const Input& in) {
-  const size_t n = in.h.size();
-  std::vector<uint32_t> count(n), type;
-  std::vector<double> size, floor;
-  for (size_t c = 0; c < n; c++) {
-    count[c] = in.wet[c] ? 2 : 1;
-    type.push_back(1); size.push_back(in.h[c]); floor.push_back(0.0);
-    if (in.wet[c]) { type.push_back(0); size.push_back(0.5); floor.push_back(in.h[c]); }
-  }
-  return dh_create(in.dx, in.dy, count.data(), type.data(), size.data(), floor.data());
-}
-
 static int check(const char* name, const std::vector<Input>& ins) {
   std::vector<dh_map*> maps;
   size_t words = 0;
@@ -163,25 +124,18 @@ static int check(const char* name, const std::vector<Input>& ins) {
   return bad;
 }
 
-template <class T> static bool take(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 static int check_dump(const char* path) {
-  FILE* f = fopen(path, "rb");
-  if (!f) { printf("FAIL cannot open %s\n", path); return 1; }
-  uint32_t head[4] = {0, 0, 0, 0}, tn[2] = {0, 0};
-  std::vector<uint32_t> count, type, o, sg, re, hd;
-  std::vector<double> size, floor;
+  Columns in;
+  uint32_t tn[2] = {0, 0};
+  std::vector<uint32_t> o, sg, re, hd;
   std::vector<StreamRec> recs;
-  bool ok = fread(head, 4, 4, f) == 4 && head[0] == 0x4D525453u && (int32_t)head[1] > 0 && (int32_t)head[2] > 0 && head[1] <= 4096u && head[2] <= 4096u;
-  const size_t n = ok ? (size_t)head[1] * head[2] : 0;
-  ok = ok && take(f, count, n) && take(f, type, head[3]) && take(f, size, head[3]) && take(f, floor, head[3]);
-  uint64_t sum = 0;
-  for (uint32_t c : count) sum += c;
-  ok = ok && sum == head[3] && fread(tn, 4, 2, f) == 2 && tn[0] >= 1u && tn[1] <= n && take(f, o, n) && take(f, sg, n) && take(f, re, n) && take(f, hd, n) && take(f, recs, tn[1]);
-  fclose(f);
-  if (!ok) { printf("FAIL %s is not a dump\n", path); return 1; }
+  if (!read_dump(path, 0x4D525453u, in, [&](FILE* f) {
+        const size_t n = in.cells;
+        return fread(tn, 4, 2, f) == 2 && tn[0] >= 1u && tn[1] <= n && take(f, o, n) && take(f, sg, n) && take(f, re, n) && take(f, hd, n) && take(f, recs, tn[1]);
+      })) return 1;
+  const size_t n = in.cells;
   const uint32_t threshold = tn[0], ns = tn[1];
-  dh_map* h = dh_create((int)head[1], (int)head[2], count.data(), type.data(), size.data(), floor.data());
+  dh_map* h = in.map();
   int bad = 0;
   for (int v = 0; v < dh_variants(); v++)
     for (uint32_t lanes : {64u, 256u})
@@ -195,20 +149,11 @@ static int check_dump(const char* path) {
         if (!same) { printf("FAIL %s variant %d lanes %u order %d: %u segments, expected %u\n", path, v, lanes, order, got, ns); bad++; }
       }
   dh_destroy(h);
-  const char* name = strrchr(path, '/');
-  printf("%-36s %4ux%-4u threshold %2u %6u segments  %s\n", name ? name + 1 : path, head[1], head[2], threshold, ns, bad ? "FAILED" : "ok");
+  printf("%-36s %4ux%-4u threshold %2u %6u segments  %s\n", file_name(path), in.dimx, in.dimy, threshold, ns, bad ? "FAILED" : "ok");
   return bad;
 }
 
 int main(int argc, char** argv) {
-  int bad = 0;
-  if (argc > 1) {
-    for (int i = 1; i < argc; i++) bad += check_dump(argv[i]);
-    return bad ? 1 : 0;
-  }
-  const int dims[2][2] = {{33, 47}, {96, 80}};
-  for (const auto& d : dims)
-    for (const char* kind : {"cone", "ramp", "plateau", "random", "lakes"}) bad += check(kind, {make(kind, d[0], d[1])});
-  bad += check("three maps", {make("lakes", 33, 47), make("cone", 70, 1), make("random", 1, 70)});
-  return bad ? 1 : 0;
+  return check_main(argc, argv, check_dump, {"cone", "ramp", "plateau", "random", "lakes"}, {{"lakes", 33, 47}, {"cone", 70, 1}, {"random", 1, 70}},
+                    [](const char* name, const std::vector<MapSpec>& specs) { return check(name, make_all(specs)); });
 }

@@ -4,7 +4,7 @@
 // The same headers the kernels are made of, compiled by g++ (-ffp-contract=off) and run as tests/drainage_host runs them: the lanes
 // of a workgroup one after the other, the workgroups of a launch one after the other, both first to last or last to first -- legal
 // orders of the device's. The maps, the lane groups and the tile variants are those of tests/drainage_host/drainage_host.cpp, which
-// this file includes. tests/streams_host_lib.py builds and binds this file; the product never loads it.
+// this file includes. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_streams.h"
 
@@ -69,38 +69,21 @@ extern "C" {
 // to first; bit 1: the lanes of a workgroup run last to first. 0, or -2 for a bad argument.
 int sh_streams(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int launch_order, uint32_t threshold, uint32_t cap, void* out, uint32_t* nstreams,
                uint32_t* order, uint32_t* segments, uint32_t* reach, uint32_t* heads) {
-  if (nm == 0 || threshold == 0 || !(lanes == 64 || lanes == 128 || lanes == 256)) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0, nrec = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = (uint32_t)nrec;
-    const uint64_t most = (uint64_t)m.dimx * m.dimy;
-    m.cap = (uint32_t)(cap < most ? cap : most);
-    words += most; nrec += m.cap;
-  }
-  StreamPlanes p;   // (as the device's planes: whatever the last call left)
-  for (std::vector<uint32_t>* v : {&p.T, &p.R, &p.P, &p.AR, &p.D, &p.O, &p.H, &p.RE, &p.B, &p.SG}) v->assign(words, 0xDEADBEEFu);
-  std::vector<StreamRec> recs(nrec ? nrec : 1);
-  memset(recs.data(), 0xAB, recs.size() * sizeof(StreamRec));
+  if (nm == 0 || threshold == 0 || !lanes_ok(lanes)) return -2;
+  const Members pl = plan_members(maps, nm, cap, CAP_CELLS);
+  StreamPlanes p;
+  poison({&p.T, &p.R, &p.P, &p.AR, &p.D, &p.O, &p.H, &p.RE, &p.B, &p.SG}, pl.words);
+  std::vector<StreamRec> recs = poisoned_records<StreamRec>(pl.nrec);
   const int desc = launch_order & 1, ldesc = (launch_order >> 1) & 1;
-  const bool with_plane = segments != nullptr;
-  switch (variant) {
-    case 0: run_streams<16, 64>(tab, lanes, desc, ldesc, threshold, with_plane, p, recs, nstreams); break;   // the kernels' own shape
-    case 1: run_streams<8, 8>(tab, lanes, desc, ldesc, threshold, with_plane, p, recs, nstreams); break;
-    case 2: run_streams<5, 7>(tab, lanes, desc, ldesc, threshold, with_plane, p, recs, nstreams); break;     // a tile no dimension is a multiple of
-    case 3: run_streams<32, 4>(tab, lanes, desc, ldesc, threshold, with_plane, p, recs, nstreams); break;
-    default: return -2;
-  }
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nstreams[i] < tab[i].cap ? nstreams[i] : tab[i].cap;
-    if (w) memcpy(static_cast<char*>(out) + (size_t)i * cap * sizeof(StreamRec), recs.data() + tab[i].rec0, (size_t)w * sizeof(StreamRec));
-  }
-  if (order) memcpy(order, p.O.data(), words * 4);
-  if (segments) memcpy(segments, p.SG.data(), words * 4);
-  if (reach) memcpy(reach, p.RE.data(), words * 4);
-  if (heads) memcpy(heads, p.H.data(), words * 4);
+  if (!with_shape<TILE_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        run_streams<S::TX, S::TY>(pl.tab, lanes, desc, ldesc, threshold, segments != nullptr, p, recs, nstreams);
+      })) return -2;
+  cut_records<StreamRec>(pl, nstreams, cap, out, sizeof(StreamRec), [&](size_t j, StreamRec& rec) { memcpy(&rec, &recs[j], sizeof(rec)); });   // (the bodies write whole records)
+  copy_plane(order, p.O.data(), pl.words);
+  copy_plane(segments, p.SG.data(), pl.words);
+  copy_plane(reach, p.RE.data(), pl.words);
+  copy_plane(heads, p.H.data(), pl.words);
   return 0;
 }
 

@@ -5,13 +5,11 @@ Every record field and the three planes must equal the restatement exactly, for 
 launch order the host build offers -- the workgroups and the lanes, first to last and last to first, the flow launches also against
 the order of the other launches (which takes the ready list last to first) and with one workgroup (which takes it in many strides):
 nothing in the result may depend on them."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import dispersal_host_lib as H
+from analysis_host_lib import dispersal as H, build_check, run_check
 import dispersal_ref as R
 import drainage_ref as D
 import lakes_ref as L
@@ -31,7 +29,7 @@ def _check_all_shapes(s, want, what, exponent, cap=None):
         for lanes in WIDTHS:
             for order in ((ORDERS + FLOW_ORDERS) if v in (0, 2) else (0,)):
                 for blocks in ((H.FLOW_BLOCKS, 1) if order in (0, 12) else (H.FLOW_BLOCKS,)):
-                    recs, planes, n, rounds = H.dispersal_many([m], exponent, v, lanes, order, blocks, cap)[0]
+                    recs, planes, n, rounds = H.run_many([m], exponent, v, lanes, order, blocks, cap)[0]
                     tag = f"{what} exponent {exponent} variant {H.variants()[v]} lanes {lanes} order {order} flow workgroups {blocks}"
                     k = len(want[0]) if cap is None else min(cap, len(want[0]))
                     R.assert_same_dispersal((recs, planes), (want[0][:k], want[1]), tag)
@@ -39,7 +37,7 @@ def _check_all_shapes(s, want, what, exponent, cap=None):
 
 
 def test_variants_are_the_drainage_host_builds():
-    import drainage_host_lib
+    from analysis_host_lib import drainage as drainage_host_lib
     assert drainage_host_lib.variants() == H.variants() and H.variants()[0] == (16, 64, 512)
 
 
@@ -111,7 +109,7 @@ def test_hand_built_map(exponent):
     R.assert_invariants(s, *want, what="the restatement, hand-built")
     check_hand(*want, exponent)
     _check_all_shapes(s, want, "hand-built", exponent)
-    recs, planes, n, rounds = H.dispersal(s, exponent)
+    recs, planes, n, rounds = H.run(s, exponent)
     check_hand(recs, planes, exponent)
 
 
@@ -121,12 +119,12 @@ def test_ramp_on_one_row_and_one_column_is_d8():
     for dims in ((1, 70), (70, 1)):
         s, drain = D.case("ramp_x", dims)
         for e in (0, 1, 4, 16):
-            recs, planes, n, rounds = H.dispersal(s, e)
+            recs, planes, n, rounds = H.run(s, e)
             assert np.array_equal(planes["area"], drain[1]["area"].astype(np.uint64) * ONE), f"ramp_x {dims} exponent {e}"
             assert int(planes["receivers"].max()) == 1 and len(recs) == 1 and recs[0]["leak_out_q24"] == 0 and recs[0]["split_cells"] == 0 and recs[0]["givers"] == 69
             R.assert_invariants(s, recs, planes, what=f"ramp_x {dims}")
         s, drain = D.case("random_bernoulli20", dims)
-        recs, planes, n, rounds = H.dispersal(s, 1)
+        recs, planes, n, rounds = H.run(s, 1)
         R.assert_same_dispersal((recs, planes), R.dispersal(s, 1, drain), f"random {dims}", count=n)
         assert int(planes["receivers"].max()) == 2
 
@@ -144,23 +142,23 @@ def test_weights_that_overflow_or_underflow_fall_back_to_d8(high, low):
     s = _steps(23, 19, high, low)
     drain = D.drainage(s)
     want = R.dispersal(s, 4, drain)
-    recs, planes, n, rounds = H.dispersal(s, 4)
+    recs, planes, n, rounds = H.run(s, 4)
     R.assert_same_dispersal((recs, planes), want, "steps", count=n)
     assert np.array_equal(planes["area"], drain[1]["area"].astype(np.uint64) * ONE)
     assert int(planes["receivers"].max()) >= 2 or high == 1.0 + 3e-200
     R.assert_invariants(s, recs, planes, what="steps")
     # with exponent 1 the same maps do split (where there is a slope at all)
-    recs1, planes1, _, _ = H.dispersal(s, 1)
+    recs1, planes1, _, _ = H.run(s, 1)
     R.assert_same_dispersal((recs1, planes1), R.dispersal(s, 1, drain), "steps, exponent 1")
     assert high == 1.0 + 3e-200 or not np.array_equal(planes1["area"], planes["area"])
 
 
 def test_exponent_16_is_accepted_and_17_refused():
     s, drain = D.case("cone", (9, 7))
-    recs, planes, n, rounds = H.dispersal(s, 16)
+    recs, planes, n, rounds = H.run(s, 16)
     R.assert_same_dispersal((recs, planes), R.dispersal(s, 16, drain), "cone (9, 7) exponent 16", count=n)
     m = H.HostMap(s)
-    assert H.dispersal_rc([m], 16) == 0 and H.dispersal_rc([m], 17) == -2 and H.dispersal_rc([m], 0xFFFFFFFF) == -2
+    assert H.rc([m], 16) == 0 and H.rc([m], 17) == -2 and H.rc([m], 0xFFFFFFFF) == -2
     with pytest.raises(AssertionError):
         R.dispersal(s, 17, drain)
 
@@ -169,12 +167,12 @@ def test_the_chain_through_every_cell_and_the_rounds():
     """ramp_x: every cell waits for the one before it -- one lane walks the whole map in one launch; a second launch finds nothing."""
     s, drain, want = R.case("ramp_x", (33, 47), 1)
     for blocks in (1, H.FLOW_BLOCKS):
-        recs, planes, n, rounds = H.dispersal(s, 1, flow_blocks=blocks)
+        recs, planes, n, rounds = H.run(s, 1, flow_blocks=blocks)
         R.assert_same_dispersal((recs, planes), want, "ramp_x")
         assert 1 <= rounds <= 33 * 47
     assert len(recs) == 1 and recs[0]["inflow_q24"] == 33 * 47 * ONE == recs[0]["peak_q24"] and recs[0]["peak_cell"] == 0
     s, drain, want = R.case("plateau", (33, 47), 1)
-    assert H.dispersal(s, 1)[3] == 0 and all(r["inflow_q24"] == ONE and r["givers"] == 0 for r in want[0])
+    assert H.run(s, 1)[3] == 0 and all(r["inflow_q24"] == ONE and r["givers"] == 0 for r in want[0])
 
 
 def test_caps_smaller_equal_and_larger_than_the_counts():
@@ -183,7 +181,7 @@ def test_caps_smaller_equal_and_larger_than_the_counts():
     assert n > 8
     for cap in (0, 1, n - 1, n, n + 5):
         _check_all_shapes(s, want, f"cap {cap}", 1, cap=cap) if cap in (1, n + 5) else None
-        recs, planes, cnt, rounds = H.dispersal(s, 1, cap=cap)
+        recs, planes, cnt, rounds = H.run(s, 1, cap=cap)
         R.assert_same_dispersal((recs, planes), (want[0][:cap], want[1]), f"cap {cap}")   # the planes cover every basin
         assert cnt == n
 
@@ -194,9 +192,9 @@ def test_maps_of_mixed_dimensions_in_one_launch():
         cases = [R.case(nm, dm, e) for nm, dm in which]
         maps = [H.HostMap(c[0]) for c in cases]
         for v, lanes, order, blocks in ((0, 256, 0, H.FLOW_BLOCKS), (2, 64, 15, 1), (1, 256, 4, 3)):
-            for got, c in zip(H.dispersal_many(maps, e, v, lanes, order, blocks), cases):
+            for got, c in zip(H.run_many(maps, e, v, lanes, order, blocks), cases):
                 R.assert_same_dispersal(got[:2], c[2], f"mixed, variant {v} order {order}", count=got[2])
-        for got, c in zip(H.dispersal_many(maps, e, cap=3), cases):
+        for got, c in zip(H.run_many(maps, e, cap=3), cases):
             R.assert_same_dispersal(got[:2], (c[2][0][:3], c[2][1]), "mixed, cap 3")
             assert got[2] == len(c[2][0])
 
@@ -210,8 +208,8 @@ def test_many_tiny_members_in_one_launch():
         cases = [(c[0], R.dispersal(c[0], e)) for c in cases]
         maps = [H.HostMap(c[0]) for c in cases]
         for v, lanes, order, blocks in ((0, 256, 0, H.FLOW_BLOCKS), (2, 64, 15, 1), (0, 64, 12, H.FLOW_BLOCKS)):
-            assert H.dispersal_rc(maps, e, v, lanes, order, blocks) == 0
-            got = H.dispersal_many(maps, e, v, lanes, order, blocks)
+            assert H.rc(maps, e, v, lanes, order, blocks) == 0
+            got = H.run_many(maps, e, v, lanes, order, blocks)
             for g, c in zip(got, cases):
                 R.assert_same_dispersal(g[:2], c[1], f"tiny members, variant {v} order {order}", count=g[2])
             assert 10 <= got[0][3] <= 25, f"{got[0][3]} rounds for members of at most 25 cells"
@@ -225,7 +223,7 @@ def test_goldens(case, tick):
         want = R.dispersal(s, e, drain)
         R.assert_invariants(s, *want, what=f"{case}.t{tick}")
         for v, lanes, order in ((0, 256, 0), (2, 64, 15)):
-            got = H.dispersal(s, e, v, lanes, order)
+            got = H.run(s, e, v, lanes, order)
             R.assert_same_dispersal(got[:2], want, f"{case}.t{tick} exponent {e}", count=got[2])
 
 
@@ -251,15 +249,13 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/dispersal_host/dispersal_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in,
     run as a child process -- nothing sanitized is loaded into this interpreter. Its own maps first (a one-cell map and the smallest
     shapes among them), then inputs of this suite with the restatement's results."""
-    src = os.path.join(H.HERE, "dispersal_check.cpp")
-    exe = str(tmp_path / "dispersal_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "dispersal_check: OK" in r.stdout, r.stdout[-4000:]
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert "dispersal_check: OK" in out, out[-4000:]
     dumps = []
     for k, (name, dims, e) in enumerate((("hand", (16, 16), 1), ("ties", (9, 7), 4), ("random_bernoulli20", (33, 47), 0), ("empty", (1, 70), 1), ("cone", (33, 47), 4))):
         s, drain, want = R.case(name, dims, e)
         dumps.append(str(tmp_path / f"case{k}.bin"))
         _dump(dumps[-1], s, want, e)
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and f"dispersal_check: OK ({len(dumps)} files)" in r.stdout, r.stdout[-4000:]
+    out = run_check(exe, dumps)
+    assert f"dispersal_check: OK ({len(dumps)} files)" in out, out[-4000:]

@@ -4,14 +4,12 @@ Every record field, the count and the three planes must equal the restatement ex
 every workgroup width and every launch order the host build offers -- the workgroups and the lanes, first to last and last to first:
 nothing in the result may depend on them."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-import drainage_host_lib as H
+from analysis_host_lib import drainage as H, build_check, run_check, write_columns
 import drainage_ref as R
 import lakes_ref
 from common import golden_snapshot
@@ -27,7 +25,7 @@ def _check_all_shapes(s, want, what, cap=None):
     for v in VARIANTS:
         for lanes in WIDTHS:
             for order in ((0, 1, 2, 3) if v in (0, 2) else (0,)):
-                recs, planes, n = H.drainage_many([m], v, lanes, order, cap)[0]
+                recs, planes, n = H.run_many([m], v, lanes, order, cap)[0]
                 tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
                 k = len(want[0]) if cap is None else min(cap, len(want[0]))
                 assert n == len(want[0]), f"{tag}: {n} basins counted, expected {len(want[0])}"
@@ -113,15 +111,15 @@ def test_maps_of_mixed_dimensions_in_one_launch():
     maps = [H.HostMap(s) for s, _ in cases]
     for v in VARIANTS:
         for lanes in WIDTHS:
-            got = H.drainage_many(maps, v, lanes, v & 3)
+            got = H.run_many(maps, v, lanes, v & 3)
             for (recs, planes, n), (_, want) in zip(got, cases):
                 R.assert_same_drainage((recs, planes), want, f"mixed variant {v} lanes {lanes}", count=n)
-            got = H.drainage_many(maps, v, lanes, 0, cap=3)          # a cap below one member's count: the counts stay, the records are cut
+            got = H.run_many(maps, v, lanes, 0, cap=3)          # a cap below one member's count: the counts stay, the records are cut
             for (recs, planes, n), (_, want) in zip(got, cases):
                 assert n == len(want[0])
                 R.assert_same_drainage((recs, planes), (want[0][:3], want[1]), f"mixed cap 3 variant {v} lanes {lanes}")
     # without the area plane the accumulation does not run, and nothing else changes
-    got = H.drainage_many(maps, 0, 256, 0, planes=("receivers", "labels"))
+    got = H.run_many(maps, 0, 256, 0, planes=("receivers", "labels"))
     for (recs, planes, n), (_, want) in zip(got, cases):
         assert "area" not in planes
         R.assert_same_drainage((recs, planes), want, "no area plane", count=n)
@@ -156,9 +154,7 @@ def _dump(path, s, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x4E415244, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x4E415244, s)
         f.write(struct.pack("<I", len(recs)))
         for p in R.PLANES:
             f.write(np.ascontiguousarray(planes[p], "<u4").tobytes())
@@ -168,18 +164,14 @@ def _dump(path, s, want):
 def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/drainage_host/drainage_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in,
     over its own inputs and over every input of drainage_ref at every size, 128 x 128 included."""
-    src = os.path.join(H.HERE, "drainage_check.cpp")
-    exe = str(tmp_path / "drainage_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 11, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 11, out
     dumps = []
     for name, dims in R.all_cases():
         s, want = R.case(name, dims)
         dumps.append(str(tmp_path / f"{name}_{dims[0]}x{dims[1]}.bin"))
         _dump(dumps[-1], s, want)
     assert len(dumps) == 54 and {"spiral", "ties", "ramp_y", "random_checker", "corners", "empty"} <= {n for n, _ in R.all_cases()}
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

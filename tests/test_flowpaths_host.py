@@ -5,15 +5,13 @@ Every record field, both counts, the seven planes and the profile must equal the
 every tile shape, every workgroup width and every launch order the host build offers -- the workgroups and the lanes, first to last
 and last to first, the up-walk also against the order of the other launches: nothing in the result may depend on them."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import drainage_ref as D
-import flowpaths_host_lib as H
+from analysis_host_lib import flowpaths as H, build_check, run_check, write_columns
 import flowpaths_ref as R
 from common import golden_snapshot
 from soilmachine_amd import capi
@@ -32,7 +30,7 @@ def _check_all_shapes(s, want, what, cap=None, drain=None):
     for v in VARIANTS:
         for lanes in WIDTHS:
             for order in ((ORDERS + UP_ORDERS) if v in (0, 2) else (0,)):
-                recs, planes, prof, n, npr, rounds = H.flowpaths_many([m], v, lanes, order, cap, profile_cap=cells)[0]
+                recs, planes, prof, n, npr, rounds = H.run_many([m], v, lanes, order, cap, profile_cap=cells)[0]
                 tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
                 k = len(want[0]) if cap is None else min(cap, len(want[0]))
                 assert rounds == R.rounds(cells), f"{tag}: {rounds} rounds"
@@ -42,7 +40,7 @@ def _check_all_shapes(s, want, what, cap=None, drain=None):
 
 
 def test_variants_are_the_drainage_host_builds():
-    import drainage_host_lib
+    from analysis_host_lib import drainage as drainage_host_lib
     assert drainage_host_lib.variants() == H.variants() and H.variants()[0] == (16, 64, 512)
 
 
@@ -100,7 +98,7 @@ def test_hand_built_map():
     s, drain, want = R.hand_case()
     check_hand(want[0], want[1], want[2], len(want[0]), len(want[2]))
     R.assert_invariants(s, *want, drain=drain, what="hand-built")
-    got = H.flowpaths(s)
+    got = H.run(s)
     check_hand(*got[:5])
     _check_all_shapes(s, want, "hand-built", drain=drain)
 
@@ -113,7 +111,7 @@ def test_the_long_path():
     at = [trench[int(c)] for c in want[2]]
     assert at == sorted(at) and at[0] == 0 and at[-1] == len(trench) - 1 and 0 < want[0][0]["diagonal"] == int(want[1]["diagonal"][0, 0]) < 2046
     for v, lanes, order in ((0, 256, 0), (0, 64, 3), (2, 256, 5), (3, 64, 10)):
-        got = H.flowpaths(s, v, lanes, order)
+        got = H.run(s, v, lanes, order)
         assert got[5] == 12
         R.assert_same_flowpaths(got, want, f"spiral variant {v} lanes {lanes} order {order}", count=got[3], nprofile=got[4])
 
@@ -124,7 +122,7 @@ def test_plateau_every_cell_its_own_basin():
         n = dims[0] * dims[1]
         assert len(want[0]) == n == len(want[2]) and (want[2] == np.arange(n)).all() and not want[1]["stem"].any()
         assert all(r["steps_max"] == 0 and r["profile_at"] == k for k, r in enumerate(want[0]))
-        got = H.flowpaths(s)
+        got = H.run(s)
         R.assert_same_flowpaths(got, want, f"plateau {dims}", count=got[3], nprofile=got[4])
 
 
@@ -153,7 +151,7 @@ def test_caps_smaller_equal_and_larger_than_the_counts():
     m = H.HostMap(s)
     for pcap in (0, 1, npr - 1, npr, npr + 5):
         for cap in (1, n):
-            recs, planes, prof, nb, got_npr, _ = H.flowpaths_many([m], 0, 256, 0, cap, profile_cap=pcap)[0]
+            recs, planes, prof, nb, got_npr, _ = H.run_many([m], 0, 256, 0, cap, profile_cap=pcap)[0]
             assert got_npr == npr and nb == n and len(prof) == min(pcap, npr)
             R.assert_same_flowpaths((recs, planes, prof), (want[0][:cap], want[1], want[2]), f"profile_cap {pcap} cap {cap}")
 
@@ -163,11 +161,11 @@ def test_maps_of_mixed_dimensions_in_one_launch():
     maps = [H.HostMap(c[0]) for c in cases]
     for v in VARIANTS:
         for lanes in WIDTHS:
-            got = H.flowpaths_many(maps, v, lanes, (v & 3) | ((v ^ 1) << 2))
+            got = H.run_many(maps, v, lanes, (v & 3) | ((v ^ 1) << 2))
             for (recs, planes, _, n, npr, rounds), c in zip(got, cases):
                 assert rounds == R.rounds(96 * 80)                         # one round count for the call: the largest map's
                 R.assert_same_flowpaths((recs, planes), c[2], f"mixed variant {v} lanes {lanes}", count=n, nprofile=npr)   # (profile_at: within the member)
-            got = H.flowpaths_many(maps, v, lanes, 0, cap=3)            # a cap below one member's count: the counts stay, the records are cut
+            got = H.run_many(maps, v, lanes, 0, cap=3)            # a cap below one member's count: the counts stay, the records are cut
             for (recs, planes, _, n, npr, _), c in zip(got, cases):
                 assert n == len(c[2][0]) and npr == len(c[2][2])
                 R.assert_same_flowpaths((recs, planes), (c[2][0][:3], c[2][1]), f"mixed cap 3 variant {v} lanes {lanes}")
@@ -177,12 +175,12 @@ def test_one_plane_at_a_time_against_all_planes():
     s, drain, want = R.case("random_checker", (96, 80))
     for order in (0, 3):
         for p in R.PLANES:
-            recs, planes, prof, n, npr, _ = H.flowpaths(s, 0, 256, order, planes=(p,), profile_cap=None)
+            recs, planes, prof, n, npr, _ = H.run(s, 0, 256, order, planes=(p,), profile_cap=None)
             assert list(planes) == [p] and prof is None
             R.assert_same_flowpaths((recs, planes), want, f"{p} alone, order {order}", count=n, nprofile=npr)
-        got = H.flowpaths(s, 0, 256, order, planes=())
+        got = H.run(s, 0, 256, order, planes=())
         R.assert_same_flowpaths(got, want, "the profile alone", count=got[3], nprofile=got[4])
-        got = H.flowpaths(s, 0, 256, order, planes=(), profile_cap=None)
+        got = H.run(s, 0, 256, order, planes=(), profile_cap=None)
         R.assert_same_flowpaths(got, want, "records only", count=got[3], nprofile=got[4])
 
 
@@ -207,9 +205,7 @@ def _dump(path, s, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x48544150, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x48544150, s)
         f.write(struct.pack("<II", len(recs), len(profile)))
         for p in R.PLANES:
             f.write(np.ascontiguousarray(planes[p], "<f8" if p == "drop" else "<u4").tobytes())
@@ -221,17 +217,13 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/flowpaths_host/flowpaths_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in,
     over its own inputs (a spiral, a random map with lakes, a plateau) and over the restatement's results for the hand-built map, the
     long path and a random map."""
-    src = os.path.join(H.HERE, "flowpaths_check.cpp")
-    exe = str(tmp_path / "flowpaths_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 9, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 9, out
     dumps = []
     for name, (s, _, want) in (("hand_16x16", R.hand_case()), ("spiral_64x64", R.case("spiral", (64, 64))), ("random_33x47", R.case("random_bernoulli20", (33, 47))),
                                ("empty_96x80", R.case("empty", (96, 80))), ("ties_1x70", R.case("ties", (1, 70)))):
         dumps.append(str(tmp_path / f"{name}.bin"))
         _dump(dumps[-1], s, want)
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

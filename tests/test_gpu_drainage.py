@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import drainage_host_lib as H
+from analysis_host_lib import drainage as H
 import drainage_ref as R
 import lakes_ref
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
@@ -45,7 +45,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(dims):
         s, want = R.case(name, dims)
         m.load(s)
         got = check(m, s, want, f"{name} {dims}")
-        hrecs, hplanes, hn = H.drainage(s)
+        hrecs, hplanes, hn = H.run(s)
         R.assert_same_drainage(got, (hrecs, hplanes), f"{name} {dims}: device against the host-compiled bodies")
         assert hn == len(got[0])
         # records only, and one plane at a time: the same records, the same plane

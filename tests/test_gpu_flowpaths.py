@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import drainage_ref as D
-import flowpaths_host_lib as H
+from analysis_host_lib import flowpaths as H
 import flowpaths_ref as R
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
 from soilmachine_amd import capi
@@ -61,7 +61,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(dims):
         m.load(s)
         what = f"{name} {dims}"
         got = check(m, s, want, what, drain)
-        host = H.flowpaths(s)
+        host = H.run(s)
         R.assert_same_flowpaths(got, host[:3], f"{what}: device against the host-compiled bodies", count=host[3], nprofile=host[4])
         only = m.flowpaths()                                               # records only
         assert len(only) == len(want[0]) and not any(R.same(a, b) for a, b in zip(only, want[0])) and "profile" not in only[0]
@@ -103,7 +103,7 @@ def test_hand_built_map():
     m.load(s)
     got = check(m, s, want, "hand-built", drain)
     check_hand(got[0], got[1], got[2], len(got[0]), len(got[2]))           # the numbers tests/test_flowpaths_host.py writes out by hand
-    host = H.flowpaths(s)
+    host = H.run(s)
     R.assert_same_flowpaths(got, host[:3], "hand-built: device against the host-compiled bodies", count=host[3], nprofile=host[4])
     m.close()
 

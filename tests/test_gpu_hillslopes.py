@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import drainage_ref as D
-import hillslopes_host_lib as H
+from analysis_host_lib import hillslopes as H
 import hillslopes_ref as R
 import lakes_ref
 import oddmaps
@@ -52,7 +52,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(dims):
             s, drain, strm, want = R.case(name, dims, t)
             what = f"{name} {dims} threshold {t}"
             got = check(m, s, t, want, what, drain, strm)
-            hrecs, hplanes, hn, _ = H.hillslopes(s, t)
+            hrecs, hplanes, hn, _ = H.run(s, t)
             R.assert_same_hillslopes(got, (hrecs, hplanes), f"{what}: device against the host-compiled bodies")
             assert hn == len(got[0])
             only = m.hillslopes(t)                                         # records only
@@ -94,7 +94,7 @@ def test_hand_built_network():
         s, drain, strm, want = R.hand_case(t)
         m.load(s)
         got = check(m, s, t, want, f"hand-built, threshold {t}", drain, strm)
-        R.assert_same_hillslopes(got, H.hillslopes(s, t)[:2], f"hand-built, threshold {t}: device against the host-compiled bodies")
+        R.assert_same_hillslopes(got, H.run(s, t)[:2], f"hand-built, threshold {t}: device against the host-compiled bodies")
     # the records of threshold 3 as tests/test_hillslopes_host.py writes them out by hand: two of them here
     by = {r["first_cell"]: r for r in got[0]}
     r = by[14 * 16 + 14]
@@ -137,7 +137,7 @@ def test_odd_maps(shape):
     for t in (1, 3, 8):
         strm = S.streams(s, t, drain)
         got = check(m, s, t, R.hillslopes(s, t, drain, strm), f"odd map {shape} threshold {t}", drain, strm)
-        R.assert_same_hillslopes(got, H.hillslopes(s, t)[:2], f"odd map {shape} threshold {t}: device against the host-compiled bodies")
+        R.assert_same_hillslopes(got, H.run(s, t)[:2], f"odd map {shape} threshold {t}: device against the host-compiled bodies")
     m.close()
 
 

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import lakes_host_lib as H
+from analysis_host_lib import lakes as H
 import lakes_ref as R
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
 from observe_ref import figures_ref
@@ -40,7 +40,7 @@ def test_shapes_equal_the_restatement_and_the_host_bodies(dims):
         s, want = R.case(name, dims)
         m.load(s)
         recs = check(m, want, f"{name} {dims}")
-        hrecs, hlabels, hn = H.census(s)
+        hrecs, hlabels, hn = H.run(s)
         R.assert_same_census((recs, None), (hrecs, None), f"{name} {dims}: device against the host-compiled bodies")
         assert hn == len(recs)
     m.close()

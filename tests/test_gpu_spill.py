@@ -8,7 +8,7 @@ import pytest
 
 import drainage_ref
 import lakes_ref
-import spill_host_lib as H
+from analysis_host_lib import spill as H
 import spill_ref as R
 import streams_ref
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
@@ -62,7 +62,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(maps, name, dims):
     s, base, want = R.case(name, dims)
     m.load(s)
     got = check(m, s, want, f"{name} {dims}")
-    (hrecs, hfilled, hn), _ = H.spill(s)
+    (hrecs, hfilled, hn), _ = H.run(s)
     R.assert_same_spill(got, (hrecs, hfilled), f"{name} {dims}: device against the host-compiled bodies", count=hn)
     only = m.spill()                                        # records only: the same records
     R.assert_same_spill((only, None), want, f"{name} {dims}: records only")

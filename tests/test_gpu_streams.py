@@ -8,7 +8,7 @@ import pytest
 
 import drainage_ref as D
 import lakes_ref
-import streams_host_lib as H
+from analysis_host_lib import streams as H
 import streams_ref as R
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
 from soilmachine_amd import capi
@@ -47,7 +47,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(dims):
             s, drain, want = R.case(name, dims, t)
             what = f"{name} {dims} threshold {t}"
             got = check(m, s, t, want, what, drain)
-            hrecs, hplanes, hn = H.streams(s, t)
+            hrecs, hplanes, hn = H.run(s, t)
             R.assert_same_streams(got, (hrecs, hplanes), f"{what}: device against the host-compiled bodies")
             assert hn == len(got[0])
             # records only, and one plane at a time: the same records, the same plane
@@ -78,7 +78,7 @@ def test_hand_built_network():
         s, drain, want = R.hand_case(t)
         m.load(s)
         got = check(m, s, t, want, f"hand-built, threshold {t}", drain)
-        R.assert_same_streams(got, H.streams(s, t)[:2], f"hand-built, threshold {t}: device against the host-compiled bodies")
+        R.assert_same_streams(got, H.run(s, t)[:2], f"hand-built, threshold {t}: device against the host-compiled bodies")
     assert len(R.hand_case(1)[2][0]) == 22
     m.close()
 

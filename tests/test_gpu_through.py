@@ -11,7 +11,7 @@ import drainage_ref
 import lakes_ref
 import spill_ref
 import streams_ref
-import through_host_lib as H
+from analysis_host_lib import through as H
 import through_ref as R
 from common import SNAP_CASES, digests, golden_snapshot, load_cfg
 from soilmachine_amd import capi
@@ -78,7 +78,7 @@ def test_inputs_equal_the_restatement_and_the_host_bodies(maps, name, dims):
     s, base, sp, want = R.case(name, dims)
     m.load(s)
     got = check(m, s, want, f"{name} {dims}")
-    (hrecs, hplanes, hn), _ = H.through(s)
+    (hrecs, hplanes, hn), _ = H.run(s)
     R.assert_same_through(got, (hrecs, hplanes), f"{name} {dims}: device against the host-compiled bodies", count=hn)
     only = m.through()                                      # records only: the same records
     R.assert_same_through((only, None), want, f"{name} {dims}: records only")

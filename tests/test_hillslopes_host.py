@@ -5,15 +5,13 @@ Every record field, the count and the five planes must equal the restatement exa
 every workgroup width and every launch order the host build offers -- the workgroups and the lanes, first to last and last to first:
 nothing in the result may depend on them."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import drainage_ref as D
-import hillslopes_host_lib as H
+from analysis_host_lib import hillslopes as H, build_check, run_check, write_columns
 import hillslopes_ref as R
 import streams_ref as S
 from common import golden_snapshot
@@ -30,7 +28,7 @@ def _check_all_shapes(s, threshold, want, what, cap=None, drain=None, strm=None)
     for v in VARIANTS:
         for lanes in WIDTHS:
             for order in ((0, 1, 2, 3) if v in (0, 2) else (0,)):
-                recs, planes, n, rounds = H.hillslopes_many([m], threshold, v, lanes, order, cap)[0]
+                recs, planes, n, rounds = H.run_many([m], threshold, v, lanes, order, cap)[0]
                 tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
                 k = len(want[0]) if cap is None else min(cap, len(want[0]))
                 assert n == len(want[0]), f"{tag}: {n} segments counted, expected {len(want[0])}"
@@ -41,7 +39,7 @@ def _check_all_shapes(s, threshold, want, what, cap=None, drain=None, strm=None)
 
 
 def test_variants_are_the_drainage_host_builds():
-    import drainage_host_lib
+    from analysis_host_lib import drainage as drainage_host_lib
     assert drainage_host_lib.variants() == H.variants() and H.variants()[0] == (16, 64, 512)
 
 
@@ -110,7 +108,7 @@ def test_the_long_path():
             assert want[0][0]["cells"] == 4095 and want[0][0]["steps_max"] == 2046 and want[0][0]["head_cells"] == 4095
         assert int((want[1]["straight"] + want[1]["diagonal"]).max()) == 2046
         for v, lanes, order in ((0, 256, 0), (0, 64, 3), (2, 256, 1), (3, 64, 2)):
-            recs, planes, n, rounds = H.hillslopes(s, t, v, lanes, order)
+            recs, planes, n, rounds = H.run(s, t, v, lanes, order)
             assert rounds == 12
             R.assert_same_hillslopes((recs, planes), want, f"spiral threshold {t} variant {v} lanes {lanes} order {order}", count=n)
         R.assert_invariants(s, t, want[0], want[1], drain=drain, strm=strm, what=f"spiral threshold {t}")
@@ -122,7 +120,7 @@ def test_cone_paths_at_the_bound_and_below_it():
         s, drain, strm, want = R.case("cone", (128, 128), t)
         assert want[2]["longest"] == longest == max(r["steps_max"] for r in want[0])
         for v, lanes, order in ((0, 256, 0), (2, 64, 3)):
-            recs, planes, n, rounds = H.hillslopes(s, t, v, lanes, order)
+            recs, planes, n, rounds = H.run(s, t, v, lanes, order)
             assert rounds == R.rounds(t, 128 * 128) == (6 if t == 64 else 10)
             R.assert_same_hillslopes((recs, planes), want, f"cone threshold {t} variant {v}", count=n)
         R.assert_invariants(s, t, want[0], want[1], drain=drain, strm=strm, what=f"cone threshold {t}")
@@ -147,7 +145,7 @@ def test_plateau_has_no_record():
             s, drain, strm, want = R.case("plateau", dims, t)
             assert want[0] == [] and want[2] == {"longest": 0, "unchannelled": 0} and (want[1]["hillslope"] == NONE).all()
             assert (want[1]["entry"].reshape(-1) == np.arange(dims[0] * dims[1])).all()
-            recs, planes, n, _ = H.hillslopes(s, t)
+            recs, planes, n, _ = H.run(s, t)
             R.assert_same_hillslopes((recs, planes), want, f"plateau {dims} threshold {t}", count=n)
 
 
@@ -166,11 +164,11 @@ def test_maps_of_mixed_dimensions_in_one_launch():
         maps = [H.HostMap(c[0]) for c in cases]
         for v in VARIANTS:
             for lanes in WIDTHS:
-                got = H.hillslopes_many(maps, t, v, lanes, v & 3)
+                got = H.run_many(maps, t, v, lanes, v & 3)
                 for (recs, planes, n, rounds), c in zip(got, cases):
                     assert rounds == R.rounds(t, 96 * 80)                  # one round count for the call: the largest map's
                     R.assert_same_hillslopes((recs, planes), c[3], f"mixed threshold {t} variant {v} lanes {lanes}", count=n)
-                got = H.hillslopes_many(maps, t, v, lanes, 0, cap=3)    # a cap below one member's count: the counts stay, the records are cut
+                got = H.run_many(maps, t, v, lanes, 0, cap=3)    # a cap below one member's count: the counts stay, the records are cut
                 for (recs, planes, n, _), c in zip(got, cases):
                     assert n == len(c[3][0])
                     R.assert_same_hillslopes((recs, planes), (c[3][0][:3], c[3][1]), f"mixed cap 3 threshold {t} variant {v} lanes {lanes}")
@@ -180,10 +178,10 @@ def test_one_plane_at_a_time_against_all_planes():
     s, drain, strm, want = R.case("random_checker", (96, 80), 8)
     for order in (0, 3):
         for p in R.PLANES:
-            recs, planes, n, _ = H.hillslopes(s, 8, 0, 256, order, planes=(p,))
+            recs, planes, n, _ = H.run(s, 8, 0, 256, order, planes=(p,))
             assert list(planes) == [p]
             R.assert_same_hillslopes((recs, planes), want, f"{p} alone, order {order}", count=n)
-        recs, planes, n, _ = H.hillslopes(s, 8, 0, 256, order, planes=())
+        recs, planes, n, _ = H.run(s, 8, 0, 256, order, planes=())
         R.assert_same_hillslopes((recs, None), want, "no plane", count=n)
 
 
@@ -212,9 +210,7 @@ def _dump(path, s, threshold, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x4C4C4948, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x4C4C4948, s)
         f.write(struct.pack("<II", int(threshold), len(recs)))
         for p in R.PLANES:
             f.write(np.ascontiguousarray(planes[p], "<f8" if p == "hand" else "<u4").tobytes())
@@ -225,12 +221,9 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/hillslopes_host/hillslopes_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked
     in, over its own inputs and over every input of drainage_ref at every size, 128 x 128 included, with thresholds 1, 3 and 8, the
     hand-built input and the long path."""
-    src = os.path.join(H.HERE, "hillslopes_check.cpp")
-    exe = str(tmp_path / "hillslopes_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 11, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 11, out
     dumps = []
     for name, dims in R.all_cases():
         for t in R.THRESHOLDS:
@@ -244,6 +237,5 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     dumps.append(str(tmp_path / "spiral_64x64_a4096.bin"))
     _dump(dumps[-1], s, 4096, want)
     assert len(dumps) == 54 * 3 + 2
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

@@ -7,7 +7,7 @@ import math
 import numpy as np
 import pytest
 
-import lakes_host_lib as H
+from analysis_host_lib import lakes as H
 import lakes_ref as R
 from common import golden_snapshot
 from observe_ref import figures_ref
@@ -23,7 +23,7 @@ def _check_all_shapes(s, want, what, cap=None):
     for v in VARIANTS:
         for lanes in WIDTHS:
             for desc in ((False, True) if v in (0, 2) else (False,)):
-                recs, labels, n = H.census_many([m], v, lanes, desc, cap)[0]
+                recs, labels, n = H.run_many([m], v, lanes, desc, cap)[0]
                 tag = f"{what} variant {H.variants()[v]} lanes {lanes} descending {desc}"
                 assert n == len(want[0]), f"{tag}: nlakes {n}, expected {len(want[0])}"
                 k = n if cap is None else min(cap, n)
@@ -46,7 +46,7 @@ def test_shape(name, dims):
 def test_no_wet_cell_is_no_lake():
     s, (recs, labels) = _case("none", (64, 64))
     assert recs == [] and (labels == R.DRY).all()
-    assert H.census(s)[2] == 0
+    assert H.run(s)[2] == 0
 
 
 @pytest.mark.parametrize("name", ["diagonal", "antidiagonal"])
@@ -57,7 +57,7 @@ def test_diagonals_join_through_corners_only(name):
         n = min(dims)
         assert len(r8) == 1 and r8[0]["cells"] == n, "one lake under eight neighbours"
         assert len(r4) == n, "the input tells the neighbourhoods apart: one lake per cell under four"
-        assert H.census(s)[2] == 1
+        assert H.run(s)[2] == 1
 
 
 def test_checkerboard_is_one_lake_under_eight_neighbours():
@@ -78,7 +78,7 @@ def test_half_planes_stay_two_lakes():
         for dims in ((64, 64), (96, 80), (33, 47)):
             s, (recs, _) = _case(name, dims)
             assert len(recs) == 2, (name, dims)
-            assert H.census(s)[2] == 2
+            assert H.run(s)[2] == 2
     # a ONE-cell-thick dry diagonal does not separate under eight neighbours (corner steps cross it); it does under four
     s, (recs, _) = _case("thin_diag", (64, 64))
     assert len(recs) == 1 and len(R.census(s, 4)[0]) == 2
@@ -87,7 +87,7 @@ def test_half_planes_stay_two_lakes():
 def test_corner_cells_flags_and_boxes():
     for dx, dy in ((64, 64), (96, 80), (33, 47)):
         s, _ = _case("corners", (dx, dy))
-        recs, labels, n = H.census(s)
+        recs, labels, n = H.run(s)
         assert n == 4
         assert [(r["x0"], r["y0"], r["x1"], r["y1"]) for r in recs] == [(0, 0, 0, 0), (0, dy - 1, 0, dy - 1), (dx - 1, 0, dx - 1, 0), (dx - 1, dy - 1, dx - 1, dy - 1)]
         assert all(r["flags"] == R.F_BORDER and r["cells"] == 1 for r in recs)
@@ -95,7 +95,7 @@ def test_corner_cells_flags_and_boxes():
     # an inner lake does not carry the border bit
     w = np.zeros((33, 47), bool)
     w[5:9, 7:30] = True
-    recs, _, _ = H.census(R.make_snapshot(w))
+    recs, _, _ = H.run(R.make_snapshot(w))
     assert len(recs) == 1 and recs[0]["flags"] == 0 and (recs[0]["x0"], recs[0]["y0"], recs[0]["x1"], recs[0]["y1"]) == (5, 7, 8, 29)
 
 
@@ -144,12 +144,12 @@ def test_maps_of_mixed_dimensions_in_one_launch():
     maps = [H.HostMap(s) for s, _ in cases]
     for v in VARIANTS:
         for lanes in WIDTHS:
-            got = H.census_many(maps, v, lanes, v == 1)
+            got = H.run_many(maps, v, lanes, v == 1)
             for (recs, labels, n), (_, want) in zip(got, cases):
                 assert n == len(want[0])
                 R.assert_same_census((recs, labels), want, f"mixed variant {v} lanes {lanes}")
             # a cap below one member's count: every count stays right, the records are cut
-            got = H.census_many(maps, v, lanes, False, cap=3)
+            got = H.run_many(maps, v, lanes, False, cap=3)
             for (recs, labels, n), (_, want) in zip(got, cases):
                 assert n == len(want[0])
                 R.assert_same_census((recs, labels), (want[0][:3], want[1]), f"mixed cap 3 variant {v} lanes {lanes}")
@@ -171,7 +171,7 @@ def test_goldens(case, tick, wet, lakes, largest):
         assert len(R.census(s, 4)[0]) == 5
     _check_all_shapes(s, want, f"{case}.t{tick}")
     # consistency with the figures the project already has
-    recs, _, _ = H.census(s)
+    recs, _, _ = H.run(s)
     fig = figures_ref(s)
     assert sum(r["cells"] for r in recs) == fig["wet_cells"]
     wetmask, size, _ = R.tops(s)

@@ -4,15 +4,13 @@ Every record field, the count and the filled plane must equal the restatement ex
 every workgroup width and every launch order the host build offers: the order decides how many sweeps the fill levels take, never
 where they end. The filled plane is held against a heap priority flood that knows nothing of basins."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import lakes_ref as L
-import spill_host_lib as H
+from analysis_host_lib import spill as H, build_check, run_check, write_columns
 import spill_ref as R
 from common import golden_snapshot
 from soilmachine_amd import capi
@@ -36,7 +34,7 @@ def _runs(dims):
 def _check_all_shapes(s, want, what, dims, cap=None):
     m = H.HostMap(s)
     for v, lanes, order in _runs(dims):
-        res, (sweeps, batches) = H.spill_many([m], v, lanes, order, cap)
+        res, (sweeps, batches) = H.run_many([m], v, lanes, order, cap)
         recs, filled, n = res[0]
         tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
         k = len(want[0]) if cap is None else min(cap, len(want[0]))
@@ -119,8 +117,8 @@ def test_the_new_inputs_are_what_they_are_meant_to_be():
 def test_chain_the_order_decides_the_sweeps_not_the_levels():
     for dims in ((33, 47), (64, 64), (96, 80)):
         s, base, want = R.case("chain", dims)
-        (up, fu, _), (su, bu) = H.spill(s, 0, 256, 0)
-        (down, fd, _), (sd, bd) = H.spill(s, 0, 256, 3)
+        (up, fu, _), (su, bu) = H.run(s, 0, 256, 0)
+        (down, fd, _), (sd, bd) = H.run(s, 0, 256, 3)
         assert su > G and bu >= 2, f"{dims}: ascending, {su} sweeps in {bu} batches"
         assert sd < su and bd < bu, f"{dims}: descending {sd} sweeps, ascending {su}"
         assert su <= _bound(want[2]["rounds"]) and sd <= _bound(want[2]["rounds"])
@@ -163,15 +161,15 @@ def test_maps_of_mixed_dimensions_in_one_launch():
     most = max(w[2]["rounds"] for _, _, w in cases)
     for v in VARIANTS:
         for lanes in WIDTHS:
-            got, (sweeps, batches) = H.spill_many(maps, v, lanes, v & 3)
+            got, (sweeps, batches) = H.run_many(maps, v, lanes, v & 3)
             for (recs, filled, n), (_, _, want) in zip(got, cases):
                 R.assert_same_spill((recs, filled), want, f"mixed variant {v} lanes {lanes}", count=n)
             assert sweeps <= _bound(most)
-            got, _ = H.spill_many(maps, v, lanes, 0, cap=3)              # a cap below one member's count: the counts stay, the records are cut
+            got, _ = H.run_many(maps, v, lanes, 0, cap=3)              # a cap below one member's count: the counts stay, the records are cut
             for (recs, filled, n), (_, _, want) in zip(got, cases):
                 assert n == len(want[0])
                 R.assert_same_spill((recs, filled), (want[0][:3], want[1]), f"mixed cap 3 variant {v} lanes {lanes}")
-    got, _ = H.spill_many(maps, 0, 256, 0, filled=False)                # without the plane nothing else changes
+    got, _ = H.run_many(maps, 0, 256, 0, filled=False)                # without the plane nothing else changes
     for (recs, filled, n), (_, _, want) in zip(got, cases):
         assert filled is None
         R.assert_same_spill((recs, None), want, "no filled plane", count=n)
@@ -215,9 +213,7 @@ def _dump(path, s, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x4C495053, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x4C495053, s)
         f.write(struct.pack("<I", len(recs)))
         f.write(bytes(out)[:len(recs) * C.sizeof(capi.Spill)])
         f.write(np.ascontiguousarray(filled, "<f8").tobytes())
@@ -226,18 +222,14 @@ def _dump(path, s, want):
 def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/spill_host/spill_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in, over its
     own inputs and over every input of spill_ref at every size, 128 x 128 included. Host code only; nothing is loaded into Python."""
-    src = os.path.join(H.HERE, "spill_check.cpp")
-    exe = str(tmp_path / "spill_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 9, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 9, out
     dumps = []
     for name, dims in R.all_cases():
         s, _, want = R.case(name, dims)
         dumps.append(str(tmp_path / f"{name}_{dims[0]}x{dims[1]}.bin"))
         _dump(dumps[-1], s, want)
     assert len(dumps) == 15 * 6 and set(R.NEW_INPUTS) <= {n for n, _ in R.all_cases()}
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

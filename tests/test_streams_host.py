@@ -5,15 +5,13 @@ Every record field, the count and the four planes must equal the restatement exa
 every workgroup width and every launch order the host build offers -- the workgroups and the lanes, first to last and last to first:
 nothing in the result may depend on them."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import drainage_ref as D
-import streams_host_lib as H
+from analysis_host_lib import streams as H, build_check, run_check, write_columns
 import streams_ref as R
 from common import golden_snapshot
 from soilmachine_amd import capi
@@ -29,7 +27,7 @@ def _check_all_shapes(s, threshold, want, what, cap=None, drain=None):
     for v in VARIANTS:
         for lanes in WIDTHS:
             for order in ((0, 1, 2, 3) if v in (0, 2) else (0,)):
-                recs, planes, n = H.streams_many([m], threshold, v, lanes, order, cap)[0]
+                recs, planes, n = H.run_many([m], threshold, v, lanes, order, cap)[0]
                 tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
                 k = len(want[0]) if cap is None else min(cap, len(want[0]))
                 assert n == len(want[0]), f"{tag}: {n} segments counted, expected {len(want[0])}"
@@ -39,7 +37,7 @@ def _check_all_shapes(s, threshold, want, what, cap=None, drain=None):
 
 
 def test_variants_are_the_drainage_host_builds():
-    import drainage_host_lib
+    from analysis_host_lib import drainage as drainage_host_lib
     assert {v: t[:2] for v, t in drainage_host_lib.variants().items()} == H.variants() and H.variants()[0] == (16, 64)
 
 
@@ -144,10 +142,10 @@ def test_maps_of_mixed_dimensions_in_one_launch():
         maps = [H.HostMap(s) for s, _, _ in cases]
         for v in VARIANTS:
             for lanes in WIDTHS:
-                got = H.streams_many(maps, t, v, lanes, v & 3)
+                got = H.run_many(maps, t, v, lanes, v & 3)
                 for (recs, planes, n), (_, _, want) in zip(got, cases):
                     R.assert_same_streams((recs, planes), want, f"mixed threshold {t} variant {v} lanes {lanes}", count=n)
-                got = H.streams_many(maps, t, v, lanes, 0, cap=3)      # a cap below one member's count: the counts stay, the records are cut
+                got = H.run_many(maps, t, v, lanes, 0, cap=3)      # a cap below one member's count: the counts stay, the records are cut
                 for (recs, planes, n), (_, _, want) in zip(got, cases):
                     assert n == len(want[0])
                     R.assert_same_streams((recs, planes), (want[0][:3], want[1]), f"mixed cap 3 threshold {t} variant {v} lanes {lanes}")
@@ -157,13 +155,13 @@ def test_one_plane_at_a_time_against_all_planes():
     s, drain, want = R.case("random_checker", (96, 80), 3)
     for order in (0, 3):
         for p in R.PLANES:
-            recs, planes, n = H.streams(s, 3, 0, 256, order, planes=(p,))
+            recs, planes, n = H.run(s, 3, 0, 256, order, planes=(p,))
             assert list(planes) == [p]
             R.assert_same_streams((recs, planes), want, f"{p} alone, order {order}", count=n)
-        recs, planes, n = H.streams(s, 3, 0, 256, order, planes=())
+        recs, planes, n = H.run(s, 3, 0, 256, order, planes=())
         R.assert_same_streams((recs, None), want, "no plane", count=n)
         # records cut and no segments plane: the segments beyond the cap are not walked, the count and the other planes stay
-        recs, planes, n = H.streams(s, 3, 0, 256, order, cap=2, planes=("order", "reach", "heads"))
+        recs, planes, n = H.run(s, 3, 0, 256, order, cap=2, planes=("order", "reach", "heads"))
         R.assert_same_streams((recs, planes), (want[0][:2], want[1]), "cap 2 without the segments plane", count=None)
         assert n == len(want[0])
 
@@ -196,9 +194,7 @@ def _dump(path, s, threshold, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x4D525453, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x4D525453, s)
         f.write(struct.pack("<II", int(threshold), len(recs)))
         for p in R.PLANES:
             f.write(np.ascontiguousarray(planes[p], "<u4").tobytes())
@@ -209,12 +205,9 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/streams_host/streams_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in,
     over its own inputs and over every input of drainage_ref at every size, 128 x 128 included, with thresholds 1, 3 and 8, and the
     hand-built input."""
-    src = os.path.join(H.HERE, "streams_check.cpp")
-    exe = str(tmp_path / "streams_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 11, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 11, out
     dumps = []
     for name, dims in R.all_cases():
         for t in R.THRESHOLDS:
@@ -225,6 +218,5 @@ def test_the_bodies_under_the_sanitizers(tmp_path):
     dumps.append(str(tmp_path / "hand_16x16_a1.bin"))
     _dump(dumps[-1], s, 1, want)
     assert len(dumps) == 54 * 3 + 1
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

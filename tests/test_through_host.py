@@ -6,9 +6,7 @@ workgroup width and every launch order the host build offers: the order decides 
 and which lane finishes a walk, never a result. The restatement's levels and hop counts are held against a heap Dijkstra over the
 basins that shares nothing with its Jacobi rounds."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +14,7 @@ import pytest
 import drainage_ref as D
 import lakes_ref as L
 import spill_ref as S
-import through_host_lib as H
+from analysis_host_lib import through as H, build_check, run_check, write_columns
 import through_ref as R
 from common import golden_snapshot
 from soilmachine_amd import capi
@@ -40,7 +38,7 @@ def _runs(dims):
 def _check_all_shapes(s, want, what, dims, cap=None):
     m = H.HostMap(s)
     for v, lanes, order in _runs(dims):
-        res, (lsw, hsw, batches) = H.through_many([m], v, lanes, order, cap)
+        res, (lsw, hsw, batches) = H.run_many([m], v, lanes, order, cap)
         recs, planes, n = res[0]
         tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
         k = len(want[0]) if cap is None else min(cap, len(want[0]))
@@ -127,8 +125,8 @@ def test_the_new_inputs_are_what_they_are_meant_to_be():
 def test_ring_the_order_decides_the_sweeps_not_the_result():
     for dims in ((33, 47), (64, 64)):
         s, base, sp, want = R.case("ring", dims)
-        (up, pu, _), su = H.through(s, 0, 256, 0)
-        (down, pd, _), sd = H.through(s, 0, 256, 3)
+        (up, pu, _), su = H.run(s, 0, 256, 0)
+        (down, pd, _), sd = H.run(s, 0, 256, 3)
         assert su != sd, f"{dims}: {su} and {sd}"
         R.assert_same_through((up, pu), want, f"ring {dims} ascending")
         R.assert_same_through((down, pd), (up, pu), f"ring {dims} descending against ascending")
@@ -170,15 +168,15 @@ def test_maps_of_mixed_dimensions_in_one_launch():
     hop = max(c[3][2]["hop_rounds"] for c in cases)
     for v in VARIANTS:
         for lanes in WIDTHS:
-            got, (lsw, hsw, batches) = H.through_many(maps, v, lanes, v & 3)
+            got, (lsw, hsw, batches) = H.run_many(maps, v, lanes, v & 3)
             for (recs, planes, n), c in zip(got, cases):
                 R.assert_same_through((recs, planes), c[3], f"mixed variant {v} lanes {lanes}", count=n)
             assert lsw <= _bound(level) and hsw <= _bound(hop) and lsw + hsw == batches * G
-            got, _ = H.through_many(maps, v, lanes, 0, cap=3)            # a cap below one member's count: the counts stay, the records are cut
+            got, _ = H.run_many(maps, v, lanes, 0, cap=3)            # a cap below one member's count: the counts stay, the records are cut
             for (recs, planes, n), c in zip(got, cases):
                 assert n == len(c[3][0])
                 R.assert_same_through((recs, planes), (c[3][0][:3], c[3][1]), f"mixed cap 3 variant {v} lanes {lanes}")
-    got, _ = H.through_many(maps, 0, 256, 0, planes=False)              # without the planes nothing else changes
+    got, _ = H.run_many(maps, 0, 256, 0, planes=False)              # without the planes nothing else changes
     for (recs, planes, n), c in zip(got, cases):
         assert planes is None
         R.assert_same_through((recs, None), c[3], "no planes", count=n)
@@ -211,9 +209,7 @@ def _dump(path, s, want):
         for f in R.FIELDS:
             setattr(out[k], f, r[f])
     with open(path, "wb") as f:
-        f.write(struct.pack("<Iiii", 0x55524854, int(s.dimx), int(s.dimy), int(s.type.size)))
-        for a, dt in ((s.count, "<u4"), (s.type, "<u4"), (s.size, "<f8"), (s.floor, "<f8")):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
+        write_columns(f, 0x55524854, s)
         f.write(struct.pack("<I", len(recs)))
         f.write(bytes(out)[:len(recs) * C.sizeof(capi.Through)])
         f.write(np.ascontiguousarray(planes["through_area"], "<u4").tobytes())
@@ -223,18 +219,14 @@ def _dump(path, s, want):
 def test_the_bodies_under_the_sanitizers(tmp_path):
     """tests/through_host/through_check.cpp: a program of its own with the address and undefined-behaviour sanitizers linked in, over
     its own inputs and over every input of through_ref at every size, 128 x 128 included. Host code only; nothing is loaded into Python."""
-    src = os.path.join(H.HERE, "through_check.cpp")
-    exe = str(tmp_path / "through_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == 9, r.stdout
+    exe = build_check(tmp_path, H)
+    out = run_check(exe)
+    assert out.count(" ok") == 9, out
     dumps = []
     for name, dims in R.all_cases():
         s, _, _, want = R.case(name, dims)
         dumps.append(str(tmp_path / f"{name}_{dims[0]}x{dims[1]}.bin"))
         _dump(dumps[-1], s, want)
     assert len(dumps) == 18 * 6 and set(R.NEW_INPUTS) <= {n for n, _ in R.all_cases()}
-    r = subprocess.run([exe] + dumps, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert "FAIL" not in r.stdout and r.stdout.count(" ok") == len(dumps), r.stdout
+    out = run_check(exe, dumps)
+    assert out.count(" ok") == len(dumps), out

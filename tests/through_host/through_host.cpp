@@ -7,7 +7,7 @@
 // bodies without a barrier (the sweeps, the exit, the link, the two walks) run lane by lane, so the order decides how far a level or
 // a hop count travels in one sweep and which lane finishes a walk -- and must not decide any result. The host loops around the
 // sweeps are the library's. The planes are shared as the library shares them: the boundary marks and the pending words are one plane,
-// the boundary list and the area another. tests/through_host_lib.py builds and binds this file; the product never loads it.
+// the boundary list and the area another. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_through.h"
 
@@ -119,12 +119,12 @@ static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descendi
 
 extern "C" {
 
-int th_variants() { return 4; }
+int th_variants() { return (int)std::size(PASS_SHAPES); }
 // (tile columns, tile rows, slots of the pass table, slots of the count table) of a variant
 int th_variant(int v, int* tx, int* ty, int* pslots, int* slots) {
-  static const int t[4][4] = {{16, 64, 1024, 512}, {8, 8, 64, 256}, {5, 7, 40, 320}, {32, 4, 128, 1024}};
-  if (v < 0 || v >= 4) return -2;
-  *tx = t[v][0]; *ty = t[v][1]; *pslots = t[v][2]; *slots = t[v][3];
+  const Shape* s = shape_at(PASS_SHAPES, v);
+  if (!s) return -2;
+  *tx = s->tx; *ty = s->ty; *pslots = s->pslots; *slots = s->slots;
   return 0;
 }
 uint32_t th_batch() { return SPILL_BATCH; }
@@ -135,40 +135,21 @@ uint32_t th_batch() { return SPILL_BATCH; }
 // batches. lanes and order as dh_drainage. 0, -2 for a bad argument, -1 where the sweeps did not settle within the bound.
 int th_through(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t cap, void* out, uint64_t struct_size, uint32_t* nbasins,
                uint32_t* through_area, uint32_t* outlets, uint32_t* sweeps) {
-  if (nm == 0 || struct_size == 0 || !(lanes == 64 || lanes == 128 || lanes == 256) || !nbasins || !sweeps || (!out && cap)) return -2;
-  std::vector<LakeMember> tab(nm);
-  uint64_t words = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    LakeMember& m = tab[i];
-    m.cells = maps[i]->cells.data(); m.dimx = maps[i]->dimx; m.dimy = maps[i]->dimy; m.pad = 0;
-    m.off = (uint32_t)words; m.rec0 = 0u; m.cap = 0u;
-    words += (uint64_t)m.dimx * m.dimy;
-  }
+  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || !nbasins || !sweeps || (!out && cap)) return -2;
+  Members pl = plan_members(maps, nm, cap, CAP_NONE);
   ThroughOut o;
   const int desc = order & 1, ldesc = (order >> 1) & 1;
-  const bool wa = through_area != nullptr, wo = outlets != nullptr;
-  int rc;
-  switch (variant) {
-    case 0: rc = run_through<16, 64, 1024, 512>(tab, lanes, desc, ldesc, wa, wo, (size_t)words, o, nbasins); break;   // the kernels' own shape
-    case 1: rc = run_through<8, 8, 64, 256>(tab, lanes, desc, ldesc, wa, wo, (size_t)words, o, nbasins); break;
-    case 2: rc = run_through<5, 7, 40, 320>(tab, lanes, desc, ldesc, wa, wo, (size_t)words, o, nbasins); break;       // a tile no dimension is a multiple of
-    case 3: rc = run_through<32, 4, 128, 1024>(tab, lanes, desc, ldesc, wa, wo, (size_t)words, o, nbasins); break;
-    default: return -2;
-  }
+  int rc = 0;
+  if (!with_shape<PASS_SHAPES>(variant, [&](auto s) {
+        using S = decltype(s);
+        rc = run_through<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, through_area != nullptr, outlets != nullptr, (size_t)pl.words, o, nbasins);
+      })) return -2;
   if (rc) return rc;
   sweeps[0] = o.level_sweeps; sweeps[1] = o.hop_sweeps; sweeps[2] = o.batches;
-  uint64_t rec0 = 0;
-  for (uint32_t i = 0; i < nm; i++) {
-    const uint32_t w = nbasins[i] < cap ? nbasins[i] : cap;
-    for (uint32_t r = 0; r < w; r++) {
-      ThroughRec rec;
-      through_finish(o.sacc[rec0 + r], o.acc[rec0 + r], rec);
-      memcpy(static_cast<char*>(out) + ((size_t)i * cap + r) * (size_t)struct_size, &rec, struct_size < sizeof(rec) ? (size_t)struct_size : sizeof(rec));
-    }
-    rec0 += nbasins[i];
-  }
-  if (through_area) memcpy(through_area, o.area.data(), words * 4);
-  if (outlets) memcpy(outlets, o.outlets.data(), words * 4);
+  plan_basins(pl, nbasins);   // (as run_through laid its copy of the table out)
+  cut_records<ThroughRec>(pl, nbasins, cap, out, (size_t)struct_size, [&](size_t j, ThroughRec& rec) { through_finish(o.sacc[j], o.acc[j], rec); });
+  copy_plane(through_area, o.area.data(), pl.words);
+  copy_plane(outlets, o.outlets.data(), pl.words);
   return 0;
 }
 
