@@ -674,6 +674,67 @@ int smx_soil_thickness(smx_ctx* ctx, const uint32_t* types, int32_t ntypes /* 1.
  * Count, scan and scatter run on the device, as the fork's do; only the listed columns come back. */
 int smx_cores(smx_ctx* ctx, const uint32_t* cells, uint32_t n, uint32_t* count, uint64_t cap, uint64_t* total,
               uint32_t* type, double* size, double* floor, double* sat);
+/* ---- the sediment budget: what a run did to the land -- cut, fill and soil change from a BASE map to the map of NOW, per drainage
+ *      basin of the base, per soil type and per cell, without exporting either map ----
+ * "now" is the calling context's map (or an ensemble member's), "base" another context of the same dimensions on the same device,
+ * typically the copy kept before the run with the copy-state call or the source of an ensemble fork. Cells, h(c), wet cells, lakes and
+ * basins are those of the drainage call; the strata are read as the soil totals read them.
+ * Per map and cell: ground(c) is 0.0 for an empty column, the top section's floor where the top section is Air (type 0), else its
+ * floor + size in one f64 addition -- only the top record is read. V_t(c) is the sum over ALL sections of type t in the column, the
+ * top one included, of floor(size * 2^40); a term that is not finite, is negative (-0 is 0) or is >= 2^24 contributes 0 and raises
+ * flag bit 0. H_t(c) is the same on size * sat, the product rounded once. S(c) is the sum of V_t(c) over every t != 0, types >= ntypes
+ * included; W(c) = V_0(c). These sums are taken modulo 2^64 and a wrap raises flag bit 1; "x is positive" below means x_now > x_base
+ * as u64.
+ * Per cell, now against base: dground = ground_now - ground_base and dheight = h_now - h_base, one f64 subtraction each; dsolid =
+ * (int64)(S_now - S_base); dwater = (int64)(W_now - W_base). A cell is LOWERED where ground_now < ground_base and RAISED where >,
+ * plain f64 comparisons; where either ground is a NaN the cell is neither and raises flag bit 2 of its basin. A cell is RESURFACED
+ * where the top types differ, an empty column counting as a type of its own.
+ * BASINS. One record per basin of the BASE's drainage, in rank order; first_cell and cells are the drainage record's: the join key. */
+typedef struct smx_budget_basin {   /* 96 bytes; a caller passes sizeof(ITS struct) and gets that prefix of each record */
+  uint32_t first_cell, cells;
+  uint32_t lowered_cells, raised_cells, resurfaced_cells;
+  uint32_t flags;                   /* bit 0: a volume term of a cell of the basin was unreliable (it contributed 0), bit 1: a 64-bit sum
+                                       wrapped (S or W of a cell, or a sum below), bit 2: a NaN ground */
+  uint64_t eroded_q40;              /* the sum over the basin's cells of S_base - S_now where that is positive */
+  uint64_t deposited_q40;           /* ... of S_now - S_base where that is positive: net = deposited - eroded, the sediment yield is -net */
+  uint64_t water_gained_q40;        /* ... of W_now - W_base where that is positive */
+  uint64_t water_lost_q40;          /* ... of W_base - W_now where that is positive */
+  double cut_max, fill_max;         /* the largest -dground over the lowered cells, the largest dground over the raised ones; +0.0: none */
+  uint32_t cut_cell, fill_cell;     /* the smallest cell that attains it; 0xFFFFFFFF: none */
+  uint32_t reserved[4];             /* written as 0 */
+} smx_budget_basin;
+/* SOILS. Record t covers the sections of type t < ntypes (1..64, as for the soil totals) over the whole map, whatever cap is; sections of a
+ * type >= ntypes count in S alone. */
+typedef struct smx_budget_soil {    /* 64 bytes; the caller passes soil_struct_size likewise */
+  uint64_t gained_q40, lost_q40;            /* the sums over the cells of V_t,now - V_t,base where positive, of V_t,base - V_t,now where positive */
+  uint64_t held_gained_q40, held_lost_q40;  /* the same on H_t */
+  uint32_t cells_gained, cells_lost;        /* the cells with V_t,now > V_t,base, with V_t,now < V_t,base */
+  uint32_t surfaced, covered;               /* cells whose top is t now and was not in base; whose top was t in base and is not now */
+  uint32_t flags;                           /* bit 0: a term of this type (volume or held) was unreliable, bit 1: a sum of this type wrapped */
+  uint32_t reserved[3];                     /* written as 0 */
+} smx_budget_soil;
+/* *nbasins = the number of the base's basins, whatever cap is; the first min(cap, *nbasins) records are written in rank order; out may
+ * be NULL when cap is 0 (counting only). soils (NULL = skip) takes ntypes records. The planes (NULL = skip; the context call only) hold
+ * dimx*dimy values in cell order: dground and dheight f64, dsolid and dwater i64; they cover the whole map. The ensemble call compares
+ * every member with the ONE base: member i's basin records start at out + i * cap_per_member records, its soil records at record
+ * i * ntypes, *nbasins is the single count of the base; the members are folded by the same launches; an empty ensemble: 0, nothing
+ * written.
+ * Both calls run on the context's / the ensemble's stream, behind the work queued on the base's stream (an event, as for the state
+ * copy): the drainage chain with its statistics ONCE, on the base, on the call's own scratch; k_budget_fold, one lane per cell walking
+ * both columns at once; k_budget_where; the results copied back, one synchronisation (the context call waits once more for the planes
+ * it then copies out). Every link of both maps is validated as the soil totals validate it: a bad chain returns -5, the text names
+ * the map and its lowest bad cell, and nothing is written to the caller. Only integers are added, every add detects a wrap, and the
+ * extremes are order-free: no result depends on the launch shape, and a plain loop over two exported maps reproduces each bit. The
+ * calls change no map, flag, counter or generator. -2: a null argument, base being the context or a member compared, unequal
+ * dimensions, another device, a strip context, struct_size == 0, records asked for with out == NULL, and with soils given
+ * soil_struct_size == 0 or ntypes outside 1..64; -3: no device. The scratch -- three u32 planes per cell, a 64-bit plane per plane
+ * asked for, a record per basin asked for and member -- is allocated at first use and kept; an allocation that fails returns < 0 and
+ * leaves the context / the ensemble usable. */
+int smx_budget(smx_ctx* ctx, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
+               smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes,
+               double* dground, double* dheight, int64_t* dsolid, int64_t* dwater);
+int smx_ensemble_budget(smx_ensemble* e, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap_per_member,
+                        uint32_t* nbasins, smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes);
 
 /* ---- point operations for API fidelity (Layermap::add/remove, Particle::cascade, ... called by host code) ---- */
 int smx_add(smx_ctx* ctx, int32_t x, int32_t y, double size, uint32_t type);            /* layermap.h:230 */

@@ -187,6 +187,39 @@ class SoilTotal(C.Structure):
         return d
 
 
+class BudgetBasin(C.Structure):
+    """smx_budget_basin: one basin's record of smx_budget / smx_ensemble_budget (96 bytes)."""
+    _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("lowered_cells", C.c_uint32), ("raised_cells", C.c_uint32),
+                ("resurfaced_cells", C.c_uint32), ("flags", C.c_uint32),
+                ("eroded_q40", C.c_uint64), ("deposited_q40", C.c_uint64), ("water_gained_q40", C.c_uint64), ("water_lost_q40", C.c_uint64),
+                ("cut_max", C.c_double), ("fill_max", C.c_double), ("cut_cell", C.c_uint32), ("fill_cell", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+        d["eroded"] = d["eroded_q40"] / BUDGET_ONE             # in height units x cells
+        d["deposited"] = d["deposited_q40"] / BUDGET_ONE
+        d["net"] = (d["deposited_q40"] - d["eroded_q40"]) / BUDGET_ONE     # the basin's sediment yield is -net
+        return d
+
+
+class BudgetSoil(C.Structure):
+    """smx_budget_soil: one soil type's record of smx_budget / smx_ensemble_budget (64 bytes)."""
+    _fields_ = [("gained_q40", C.c_uint64), ("lost_q40", C.c_uint64), ("held_gained_q40", C.c_uint64), ("held_lost_q40", C.c_uint64),
+                ("cells_gained", C.c_uint32), ("cells_lost", C.c_uint32), ("surfaced", C.c_uint32), ("covered", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self) -> dict:
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+        d["gained"] = d["gained_q40"] / BUDGET_ONE
+        d["lost"] = d["lost_q40"] / BUDGET_ONE
+        d["net"] = (d["gained_q40"] - d["lost_q40"]) / BUDGET_ONE
+        return d
+
+
+BUDGET_ONE = 1 << 40                   # one height unit on one cell (the *_q40 fields of the budget records)
+BUDGET_NONE = 0xFFFFFFFF               # smx_budget_basin.cut_cell / fill_cell: no lowered / raised cell
+BUDGET_TERM_UNRELIABLE, BUDGET_WRAPPED, BUDGET_NAN_GROUND = 1, 2, 4    # smx_budget_basin.flags (the first two: smx_budget_soil.flags too)
 TOTALS_MAX_TYPES = 64                  # SMX_TOTALS_MAX_TYPES
 TOTAL_VOLUME_UNRELIABLE, TOTAL_HELD_UNRELIABLE = 1, 2                  # smx_soil_total.flags
 THICKNESS_MAX_TYPES = 8
@@ -237,6 +270,7 @@ SYMBOLS = [
     "smx_flowpaths", "smx_ensemble_flowpaths",
     "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
+    "smx_budget", "smx_ensemble_budget",
     "smx_switches",
 ]
 
@@ -386,6 +420,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_soil_totals.argtypes = [vp, vp, u64, u32, vp]
     L.smx_soil_thickness.argtypes = [vp, vp, i32, vp, vp, vp]
     L.smx_cores.argtypes = [vp, vp, u32, vp, u64, C.POINTER(u64), vp, vp, vp, vp]
+    L.smx_budget.argtypes = [vp, vp, vp, u64, u32, C.POINTER(u32), vp, u64, u32, vp, vp, vp, vp]
+    L.smx_ensemble_budget.argtypes = [vp, vp, vp, u64, u32, C.POINTER(u32), vp, u64, u32]
     L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)

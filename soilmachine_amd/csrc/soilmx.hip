@@ -14,6 +14,8 @@
 //                                    digest and water figures; one thread per cell folds a plane over the selected members
 //   k_strata_totals / k_strata_thickness / k_core_count / k_core_scatter   the strata read on the device (soil_strata.h): one lane
 //                                    per column walks the chain -- per-type totals, thickness planes, the columns of listed cells
+//   k_budget_fold / k_budget_where   the sediment budget (soil_budget.h): one lane per cell walks the column of two maps at once --
+//                                    cut, fill and soil change per basin of the base, per soil type and per cell
 //   k_init_terrain                   Layermap::initialize (layermap.h:163-216): FBm OpenSimplex2 per cell + column build
 //   k_heights / k_surface / k_normals / k_bilinear   whole-map read-side primitives (layermap.h:341-439)
 //   k_fill_vertices                  Layermap::update(Vertexpool&) (layermap.h:475-555): the 44-byte vertex stream
@@ -55,6 +57,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_paths.h"
 #include "soil_disp.h"
 #include "soil_strata.h"
+#include "soil_budget.h"
 #include "soil_scratch.h"
 #include <algorithm>
 #include <rocprim/rocprim.hpp>   // device radix sort of the nested particles' keys (children -> next generation, batch_generations)
@@ -741,6 +744,26 @@ __global__ void __launch_bounds__(STRATA_LANES) k_core_scatter(StrataMap m, cons
 struct CoreWidenFn {   // the scan's input: a count as a 64-bit word
   __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
 };
+
+// ---------------- the sediment budget (smx_budget / smx_ensemble_budget; bodies: soil_budget.h) ----------------
+// Behind the drainage chain on the BASE, on its rank plane. k_budget_fold: member blockIdx.y of the table, workgroup blockIdx.x a
+// 16 x 16 tile of cells, one lane a cell (a compact tile meets few basins; sixteen consecutive 32-byte records a column); the basin
+// table has a slot per cell and the soil table an entry per type (21 KB of LDS). k_budget_where: LAKE_LANES cells a workgroup.
+constexpr int BUDGET_TX = 16, BUDGET_TY = 16, BUDGET_SLOTS = BUDGET_TX * BUDGET_TY;
+static_assert(BUDGET_SLOTS == LAKE_LANES, "k_budget_fold: one lane a cell");
+__global__ void __launch_bounds__(LAKE_LANES) k_budget_fold(BudgetBase b, const BudgetMap* __restrict__ tab, const uint32_t* __restrict__ T, BudgetAcc* acc,
+                                                            BudgetSoilRec* soils, uint64_t* bad, BudgetPlanes pl) {
+  __shared__ BudgetBasinTable<BUDGET_SLOTS> bt;
+  __shared__ BudgetSoilTable st;
+  const BudgetMap m = tab[blockIdx.y];
+  ObsGroup g;
+  budget_fold_group<BUDGET_TX, BUDGET_TY, BUDGET_SLOTS>(b, m, g, blockIdx.x, bt, st, T, acc, soils, bad, pl);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_budget_where(BudgetBase b, const BudgetMap* __restrict__ tab, const uint32_t* __restrict__ T, BudgetAcc* acc) {
+  const BudgetMap m = tab[blockIdx.y];
+  ObsGroup g;
+  budget_where_group(b, m, g, blockIdx.x, T, acc);
+}
 
 // ---------------- speculative engine kernels (protocol: soil_spec.h) ----------------
 // Particles per wave (env SMX_SPEC_LANES, default 1): a phase has only ~10^3 particles while the chip has 1024
@@ -2087,6 +2110,13 @@ struct StrataScratch {
   char* h_buf = nullptr; size_t h_cap = 0;
 };
 
+// smx_budget / smx_ensemble_budget: the analysis scratch of the chain on the base and of the records, and the 64-bit planes of the
+// cells' changes (smx_budget only, allocated once a plane is asked for)
+struct BudgetScratch {
+  AnalysisScratch a;
+  char* d_planes = nullptr; size_t planes_cap = 0;
+};
+
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
@@ -2156,6 +2186,7 @@ struct smx_ctx : EventTimer {
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths: one each
   AnalysisScratch disp;                                                  // smx_dispersal
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
+  BudgetScratch budget;               // smx_budget of this context against a base
 };
 
 // a failed HIP call: its text and the runtime's message go to the `err` of `obj` (a context, an ensemble, a lattice), the function returns -1
@@ -3737,6 +3768,7 @@ struct smx_ensemble : EventTimer {
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes, _flowpaths: one each
   AnalysisScratch disp;                                                  // smx_ensemble_dispersal
   StrataScratch strata;                   // smx_ensemble_soil_totals
+  BudgetScratch budget;                   // smx_ensemble_budget
 };
 
 static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
@@ -5190,6 +5222,146 @@ int smx_cores(smx_ctx* ctx, const uint32_t* cells, uint32_t n, uint32_t* count, 
   HIPCHK(ctx, hipMemcpyAsync(sat, d_sat, (size_t)tot * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   return 0;
+}
+
+// ---------------- the sediment budget (smx_budget / smx_ensemble_budget; kernels: soil_budget.h) ----------------
+// One path for both calls, through the analyses' driver: the chain's call is the BASE alone (plan_members, the tables, the planes T, B
+// and R, launch_drain_chain with its statistics -- once, whatever the member count) on the owner's stream and scratch, behind the
+// work queued on the base's stream. The maps of NOW go into a table of their own in the result region, which holds, in this order:
+// the base's basin count, the error words (the base's, then one per member), that table, the base's basin records, the members'
+// budget records and their soil records. One upload, two memsets, the chain, k_budget_fold and k_budget_where for all members, the
+// region back, one synchronisation; the planes (smx_budget only) are copied out behind the verdict and waited for once more.
+static_assert(sizeof(smx_budget_basin) == 96 && sizeof(BudgetBasinRec) == sizeof(smx_budget_basin) && offsetof(smx_budget_basin, eroded_q40) == offsetof(BudgetBasinRec, eroded_q40) &&
+              offsetof(smx_budget_basin, cut_max) == offsetof(BudgetBasinRec, cut_max) && offsetof(smx_budget_basin, cut_cell) == offsetof(BudgetBasinRec, cut_cell) &&
+              offsetof(smx_budget_basin, flags) == offsetof(BudgetBasinRec, flags), "smx_budget_basin layout");
+static_assert(sizeof(smx_budget_soil) == 64 && sizeof(BudgetSoilRec) == sizeof(smx_budget_soil) && offsetof(smx_budget_soil, cells_gained) == offsetof(BudgetSoilRec, cells_gained) &&
+              offsetof(smx_budget_soil, flags) == offsetof(BudgetSoilRec, flags) && (int)SMX_TOTALS_MAX_TYPES == BUDGET_MAX_TYPES, "smx_budget_soil layout");
+static int budget_run(const AnalysisCall& c, BudgetScratch& ks, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
+                      smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes, double* dground, double* dheight, int64_t* dsolid, int64_t* dwater) {
+  AnalysisScratch& k = ks.a;
+  const AnalysisCall cb{c.who, false, false, c.mem, c.st, &base, 1u, c.err};   // the chain's call: the base alone
+  AnalysisPlan pl;
+  if (int rc = plan_members(cb, cap, CAP_CELLS, pl)) return rc;
+  const uint32_t nm = c.nm, bcap = pl.tab[0].cap, nt = soils ? ntypes : 0u;
+  if ((uint64_t)nm * bcap > 0xFFFFFFFEull) { c.err = std::string(c.who) + ": more than 2^32 - 2 records in one call"; return -2; }
+  const size_t bad_at = counts_pad(1), tab_at = bad_at + strata_pad((size_t)(1u + nm) * 8), basin_at = tab_at + strata_pad((size_t)nm * sizeof(BudgetMap));
+  const size_t acc_at = basin_at + strata_pad((size_t)bcap * sizeof(BasinAcc)), soil_at = acc_at + (size_t)nm * bcap * sizeof(BudgetAcc);
+  const size_t res_bytes = soil_at + (size_t)nm * nt * sizeof(BudgetSoilRec);
+  AnalysisScratch::Need need;
+  need.words = (size_t)pl.words; need.planes = 3; need.members = 1; need.res_bytes = res_bytes;
+  if (!scan_bytes(cb, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(cb, k, need, "budget", (uint64_t)nm * bcap)) return rc;
+  double* const want64[4] = {dground, dheight, reinterpret_cast<double*>(dsolid), reinterpret_cast<double*>(dwater)};
+  size_t nplanes = 0;
+  for (double* w : want64) nplanes += w ? 1 : 0;
+  const size_t plane_bytes = (size_t)pl.words * 8;
+  // (every call that uses the planes has waited for its stream before it returned: nothing queued still writes what is dropped)
+  if (c.mem.grow(ks.d_planes, ks.planes_cap, nplanes * plane_bytes, nplanes * plane_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c.err = std::string(c.who) + ": out of memory for the planes (" + std::to_string(nplanes * plane_bytes) + " bytes on the device)";
+    return -1;
+  }
+  double* d64[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (size_t j = 0, at = 0; j < 4; j++)
+    if (want64[j]) d64[j] = reinterpret_cast<double*>(ks.d_planes + (at++) * plane_bytes);
+  const BudgetPlanes planes{d64[0], d64[1], reinterpret_cast<int64_t*>(d64[2]), reinterpret_cast<int64_t*>(d64[3])};
+  std::string why;
+  if (fork_order(base, c.st, why)) { c.err = std::string(c.who) + ": " + why; return -1; }
+  uint32_t* const T = k.plane[0]; uint32_t* const B = k.plane[1]; uint32_t* const R = k.plane[2];
+  uint32_t* const d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  uint64_t* const d_bad = reinterpret_cast<uint64_t*>(k.d_res + bad_at);
+  BudgetMap* const d_maps = reinterpret_cast<BudgetMap*>(k.d_res + tab_at);
+  BasinAcc* const d_basin = reinterpret_cast<BasinAcc*>(k.d_res + basin_at);
+  BudgetAcc* const d_acc = reinterpret_cast<BudgetAcc*>(k.d_res + acc_at);
+  BudgetSoilRec* const d_soil = reinterpret_cast<BudgetSoilRec*>(k.d_res + soil_at);
+  BudgetMap* const h_maps = reinterpret_cast<BudgetMap*>(k.h_res + tab_at);
+  for (uint32_t i = 0; i < nm; i++) {
+    const smx_ctx* x = c.ms[i];
+    h_maps[i] = BudgetMap{x->d.cells, x->d.pool, (uint64_t)x->cfg.pool_capacity, i * bcap, i * nt, i, 0u};
+  }
+  const BudgetBase bb{base->d.cells, base->d.pool, (uint64_t)base->cfg.pool_capacity, base->cfg.dimx, base->cfg.dimy, bcap, nt};
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(cb, k, 0, 2);
+  ok = ok && hipMemcpyAsync(d_maps, h_maps, (size_t)nm * sizeof(BudgetMap), hipMemcpyHostToDevice, c.st) == hipSuccess;
+  ok = ok && hipMemsetAsync(d_bad, 0, tab_at - bad_at, c.st) == hipSuccess;
+  ok = ok && (res_bytes == acc_at || hipMemsetAsync(d_acc, 0, res_bytes - acc_at, c.st) == hipSuccess);
+  if (ok) ok = launch_drain_chain(pl, c.st, k, k.d_tab + 1, k.d_tab, T, B, R, d_basin, d_n, nullptr, nullptr);
+  if (ok && (bcap || nt || nplanes)) {   // (a counting call asks for nothing the columns hold: the chain alone)
+    hipLaunchKernelGGL(k_budget_fold, dim3(budget_tiles(bb.dimx, bb.dimy, BUDGET_TX, BUDGET_TY), nm), pl.wg, 0, c.st, bb, d_maps, T, d_acc, d_soil, d_bad, planes);
+    if (bcap) hipLaunchKernelGGL(k_budget_where, dim3(pl.gf.x, nm), pl.wg, 0, c.st, bb, d_maps, T, d_acc);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, res_bytes);
+  if (analysis_wait(c, ok, "the budget")) return -1;
+  const uint64_t* bad = reinterpret_cast<const uint64_t*>(k.h_res + bad_at);
+  for (uint32_t i = 0; i <= nm; i++) {
+    if (!bad[i]) continue;
+    const unsigned long long cell = strata_bad_cell(bad[i]), dy = (unsigned long long)base->cfg.dimy;
+    c.err = std::string(c.who) + ": corrupt section chain in " + (i == 0 ? std::string("the base map") : c.ensemble ? "member " + std::to_string(i - 1) : std::string("the context's map")) +
+            ", cell " + std::to_string(cell) + " (x " + std::to_string(cell / dy) + ", y " + std::to_string(cell % dy) +
+            "): it leaves the pool or has more links than the pool holds (nothing was written)";
+    return -5;
+  }
+  const uint32_t n = *reinterpret_cast<const uint32_t*>(k.h_res), w = std::min(n, std::min(bcap, cap));
+  const BasinAcc* b = reinterpret_cast<const BasinAcc*>(k.h_res + basin_at);
+  const BudgetAcc* a = reinterpret_cast<const BudgetAcc*>(k.h_res + acc_at);
+  const BudgetSoilRec* s = reinterpret_cast<const BudgetSoilRec*>(k.h_res + soil_at);
+  const size_t take = struct_size < sizeof(BudgetBasinRec) ? (size_t)struct_size : sizeof(BudgetBasinRec);
+  const size_t stake = soil_struct_size < sizeof(BudgetSoilRec) ? (size_t)soil_struct_size : sizeof(BudgetSoilRec);
+  *nbasins = n;
+  for (size_t i = 0; i < nm; i++) {
+    for (uint32_t r = 0; r < w; r++) {
+      BudgetBasinRec rec;
+      budget_finish(b[r], a[i * bcap + r], rec);
+      memcpy(reinterpret_cast<char*>(out) + (i * cap + r) * (size_t)struct_size, &rec, take);
+    }
+    for (uint32_t t = 0; t < nt; t++) memcpy(reinterpret_cast<char*>(soils) + (i * nt + t) * (size_t)soil_struct_size, s + i * nt + t, stake);
+  }
+  if (!nplanes) return 0;
+  ok = true;
+  for (size_t j = 0; j < 4; j++) ok = copy_back(c, ok, want64[j], d64[j], plane_bytes);
+  return analysis_wait(c, ok, "copying the planes");
+}
+// the checks of the two calls behind analysis_begin's: what the base has to be
+static bool budget_base_ok(const AnalysisCall& c, smx_ctx* base, int device, const smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes, int& rc) {
+  auto no = [&](int code, const std::string& why) { c.err = std::string(c.who) + ": " + why; rc = code; return false; };
+  if (base->partial()) return no(-2, "the base is a strip context (smx_create_strip): it holds only a part of the map");
+  if (base->cfg.device != device) return no(-2, "the base lives on another device");
+  if (soils && soil_struct_size == 0) return no(-2, "soil_struct_size is 0 (pass sizeof(smx_budget_soil) of the header you compiled against)");
+  if (soils && (ntypes < 1u || ntypes > (uint32_t)SMX_TOTALS_MAX_TYPES)) return no(-2, "ntypes is " + std::to_string(ntypes) + ", outside 1..64");
+  for (uint32_t i = 0; i < c.nm; i++) {
+    const smx_ctx* x = c.ms[i];
+    const std::string who = c.ensemble ? "member " + std::to_string(i) : std::string("the context");
+    if (x == base) return no(-2, "the base is " + who + " itself");
+    if (x->cfg.dimx != base->cfg.dimx || x->cfg.dimy != base->cfg.dimy)
+      return no(-2, who + " is " + std::to_string(x->cfg.dimx) + "x" + std::to_string(x->cfg.dimy) + ", the base is " + std::to_string(base->cfg.dimx) + "x" + std::to_string(base->cfg.dimy));
+  }
+  if (!base->stream) return no(-3, "the base has no device");
+  return true;
+}
+int smx_budget(smx_ctx* ctx, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, smx_budget_soil* soils,
+               uint64_t soil_struct_size, uint32_t ntypes, double* dground, double* dheight, int64_t* dsolid, int64_t* dwater) {
+  if (!ctx) return -2;
+  if (!base) { ctx->err = "smx_budget: base is null"; return -2; }
+  const AnalysisCall c = call_on("smx_budget", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_budget_basin", "nbasins", struct_size, nullptr, nbasins, out, cap, rc)) return rc;
+  if (!budget_base_ok(c, base, ctx->cfg.device, soils, soil_struct_size, ntypes, rc)) return rc;
+  roctx_range rr("soilmx:budget");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return budget_run(c, ctx->budget, base, out, struct_size, cap, nbasins, soils, soil_struct_size, ntypes, dground, dheight, dsolid, dwater);
+}
+int smx_ensemble_budget(smx_ensemble* e, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins,
+                        smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes) {
+  if (!e) return -2;
+  if (!base) { e->err = "smx_ensemble_budget: base is null"; return -2; }
+  const AnalysisCall c = call_on("smx_ensemble_budget", e);
+  int rc;
+  if (!analysis_begin(c, "smx_budget_basin", "nbasins", struct_size, nullptr, nbasins, out, cap_per_member, rc)) return rc;
+  if (!budget_base_ok(c, base, e->device, soils, soil_struct_size, ntypes, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_budget");
+  HIPCHK(e, hipSetDevice(e->device));
+  return budget_run(c, e->budget, base, out, struct_size, cap_per_member, nbasins, soils, soil_struct_size, ntypes, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ---------------- point operations ----------------

@@ -350,6 +350,27 @@ class Ensemble:
         recs = [[out[i * nt + t].as_dict() for t in range(nt)] for i in range(n)]
         return (recs, [int(v) for v in rest[:n]]) if other else recs
 
+    def budget(self, base: Layermap, ntypes: int, cap: int | None = None) -> list:
+        """How far every member moved from ``base`` (``smx_ensemble_budget``: the drainage chain once, on the base, and the same
+        launches whatever the member count): one ``(basins, soils)`` per member, in member order, each as
+        ``Layermap.budget(base, ntypes)`` gives it -- the basins are the BASE's, so every member has the same ones. ``base`` is a
+        ``Layermap`` or an ``EnsembleMember`` of another ensemble with the members' dimensions on this device, typically the source
+        of the fork. ``cap`` None: two calls, the basin count and the fetch; else at most ``cap`` basins per member."""
+        self._check_members()
+        n, nt = len(self.members), int(ntypes)
+        if n == 0:
+            return []
+        count = C.c_uint32()
+        if cap is None:
+            self._chk(self.L.smx_ensemble_budget(self.h, base.h, None, C.sizeof(capi.BudgetBasin), 0, C.byref(count), None, 0, 0))
+            cap = int(count.value)
+        cap = int(cap)
+        out = (capi.BudgetBasin * max(1, n * cap))()
+        soils = (capi.BudgetSoil * max(1, n * max(nt, 0)))()
+        self._chk(self.L.smx_ensemble_budget(self.h, base.h, out, C.sizeof(capi.BudgetBasin), cap, C.byref(count), soils, C.sizeof(capi.BudgetSoil), nt))
+        k = min(cap, int(count.value))
+        return [([out[i * cap + r].as_dict() for r in range(k)], [soils[i * nt + t].as_dict() for t in range(nt)]) for i in range(n)]
+
     def timing(self) -> dict:
         t = capi.Timing()
         self._chk(self.L.smx_ensemble_get_timing(self.h, C.byref(t), C.sizeof(t)))

@@ -347,6 +347,36 @@ class Layermap:
         self._chk(self.L.smx_get_dispersal_rounds(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def budget(self, base: "Layermap", ntypes: int | None = None, dground: bool = False, dheight: bool = False, dsolid: bool = False, dwater: bool = False,
+               cap: int | None = None):
+        """The sediment budget (``smx_budget``): what changed from ``base`` -- another map of the same dimensions on the same device,
+        typically the ``copy_from`` taken before the run -- to this map. Returns ``(basins, soils)``. ``basins``: one dict per
+        drainage basin of the BASE in rank order -- ``first_cell`` and ``cells`` (join on them with ``base.drainage()``),
+        ``lowered_cells`` / ``raised_cells`` (the ground went down / up; the ground is the top of the solid column, the floor of a
+        water section), ``resurfaced_cells`` (another top type), ``eroded_q40`` / ``deposited_q40`` (the exact integer sums of the
+        cells' losses / gains of floor(size * 2^40) over every section that is not Air), ``water_gained_q40`` / ``water_lost_q40``
+        (the same for Air), ``cut_max`` / ``cut_cell`` and ``fill_max`` / ``fill_cell`` (the deepest cut and the highest fill and the
+        smallest cell that has it; 0.0 and 0xFFFFFFFF without one), ``flags`` (1: a term was unreliable, 2: a sum wrapped, 4: a NaN
+        ground) and the floats ``eroded``, ``deposited`` and ``net`` in height units x cells: the basin's sediment yield is
+        ``-net``. ``soils``: one dict per type 0..ntypes-1 for the whole map -- ``gained_q40`` / ``lost_q40`` (the cells' gains /
+        losses of the type's volume), ``held_gained_q40`` / ``held_lost_q40`` (the same on size * sat), ``cells_gained`` /
+        ``cells_lost``, ``surfaced`` / ``covered`` (cells where the type came to the top / left it), ``flags`` and the floats
+        ``gained``, ``lost`` and ``net``. ``ntypes`` None: the soil table's length, capped at 64. With a plane asked for the result
+        is ``(basins, soils, planes)``, ``planes`` a dict of (dimx, dimy) arrays: ``dground`` and ``dheight`` (float64), ``dsolid``
+        and ``dwater`` (int64, in units of 2^-40). ``cap`` None: two calls, the basin count and the fetch; else at most ``cap``
+        basins. Sees every tick queued before it on either map and changes nothing."""
+        nt = min(len(self._soils), capi.TOTALS_MAX_TYPES) if ntypes is None else int(ntypes)
+        soils = (capi.BudgetSoil * max(1, nt))()
+
+        def call(out, cap, n, *pl):
+            fetch = out is not None or cap != 0 or any(p is not None for p in pl)        # (the counting call takes no soil table)
+            return self.L.smx_budget(self.h, base.h, out, C.sizeof(capi.BudgetBasin), cap, n, soils if fetch else None, C.sizeof(capi.BudgetSoil), nt, *pl)
+
+        recs, planes = self._analysis(call, capi.BudgetBasin, cap, [("dground", dground), ("dheight", dheight), ("dsolid", dsolid), ("dwater", dwater)],
+                                      dtype={"dground": np.float64, "dheight": np.float64, "dsolid": np.int64, "dwater": np.int64})
+        table = [soils[t].as_dict() for t in range(nt)]
+        return (recs, table, planes) if planes else (recs, table)
+
     def hillslopes(self, threshold: int, entry: bool = False, hillslope: bool = False, straight: bool = False, diagonal: bool = False, hand: bool = False,
                    cap: int | None = None):
         """The land beside the channels (``smx_hillslopes``): one dict per segment, record k for segment k of ``streams(threshold)``
