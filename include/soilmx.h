@@ -576,6 +576,56 @@ int smx_flowpaths(smx_ctx* ctx, smx_flowpath* out, uint64_t struct_size, uint32_
                   uint32_t* straight, uint32_t* diagonal, double* drop, uint32_t* upstream, uint32_t* source, uint32_t* stem,
                   uint32_t* profile, uint32_t profile_cap, uint32_t* nprofile);
 int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nbasins);
+/* ---- catchments of listed outlets: which land drains through each cell of the caller's list (a gauge, a dam site, the last cell of
+ *      a stream segment), one record per listed cell, the tree the gauges form along the flow, and per catchment a height
+ *      distribution (hypsometry) ----
+ * Cells, h(c), wet cells, receivers R, sinks, basins and their ranks are those of smx_drainage, the ordered image K that of
+ * smx_spill. The GAUGES are the n >= 1 distinct cell indices x*dimy + y of the list; any cell may be one: dry, wet or a sink. The
+ * ENTRY e(c) of a dry cell is the first cell on c, R(c), R(R(c)), ..., c included, that is a gauge, a sink or a wet cell; a wet cell
+ * is its own entry. gauge(c) is the position of e(c) in the list, 0xFFFFFFFF where e(c) is no gauge. straight(c) / diagonal(c) count
+ * the steps from c to e(c), split as in smx_segment; drop(c) = h(c) - h(e(c)) is one f64 subtraction, +0.0 where e(c) == c. These
+ * three are defined for EVERY cell; where no gauge lies on a cell's path they are the straight, diagonal and drop of smx_flowpaths.
+ * The OWN CATCHMENT of gauge i is the set of cells with gauge(c) == i, the gauge cell included. For a gauge cell g that is dry and
+ * no sink, downstream(i) = gauge(R(g)), the next gauge down the flow; otherwise 0xFFFFFFFF. A path strictly descends, so the gauges
+ * form a forest: the whole catchment of gauge i is its own plus those of the gauges above it, and area(i) is cells summed over them.
+ * Hypsometry: a cell of own catchment i counts in bin b of row i, q = drop(c) / bin_height in one f64 division and
+ * b = q < nbins ? (u32)q : nbins - 1, so that a NaN and an infinity land in the last bin. Every figure is an exact integer, an
+ * order-free extreme or one f64 subtraction or division: a host restatement reproduces each bit. */
+enum { SMX_CATCHMENT_MAX_BINS = 64 };
+typedef struct smx_catchment {            /* 64 bytes; record i belongs to position i of the list */
+  uint32_t cell;                         /* the gauge cell, cells[i] */
+  uint32_t cells;                        /* the size of the own catchment, at least 1 */
+  uint32_t area;                         /* cells summed over the gauge and every gauge above it; for a dry gauge the area plane of smx_drainage at the cell */
+  uint32_t downstream;                   /* list position of the next gauge down the flow, 0xFFFFFFFF without one */
+  uint32_t basin;                        /* the rank of the gauge cell's basin (the label plane of smx_drainage) */
+  uint32_t steps_max;                    /* the largest straight + diagonal in the own catchment */
+  uint32_t farthest_cell;                /* the cell that has it, the smallest cell index among equals; the gauge cell for a catchment of one cell */
+  uint32_t flags;                        /* 1: drop_sum_q40 unreliable, 2: the gauge cell is wet, 4: the gauge cell is a sink */
+  uint64_t straight_sum, diagonal_sum;   /* exact sums over the own catchment */
+  double   drop_max;                     /* the largest drop in it by K */
+  uint64_t drop_sum_q40;                 /* the sum of floor(drop * 2^40), as smx_hillslope.hand_sum_q40 */
+} smx_catchment;
+/* n records are written per map, record i at byte i * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each
+ * record); there is no cap and no counting call. nbins (0 to 64) > 0: hist holds n * nbins u32 per map, row i for gauge i, and every
+ * row sums to cells of its record; nbins == 0: hist and bin_height are not looked at and no histogram work is launched. The planes
+ * (NULL = skip; smx_catchments only) hold dimx*dimy words in cell order: gauge, straight and diagonal u32, drop doubles. In the
+ * ensemble call ONE list serves every member, as an index into each member's own plane; member i's records start at out + i * n
+ * records and its table at hist + i * n * nbins; an empty ensemble: 0, nothing written. Refused with -2, the error text naming the
+ * offending position, before anything is launched or written: cells NULL, n == 0, out NULL, a cell outside a member, a cell listed
+ * twice, nbins > 64, nbins > 0 with hist NULL or with a bin_height that is not finite and positive, n * nbins >= 2^31; also a strip
+ * context and struct_size == 0; a context without a device -3. Both calls run on the context's / the ensemble's stream (they see
+ * every tick queued before them), launch the same kernels whatever the map holds and however many members there are (one upload of
+ * the tables and the list; k_catch_mark; the drainage chain with its statistics and WITHOUT its area walk on the call's own scratch;
+ * k_catch_init; k rounds of k_hill_jump, k the smallest number with 2^k >= cells of the largest map - 1, at most 32 and known before
+ * the launch; k_catch_fold; with bins k_catch_hist; the RESULTS copied back), synchronise once and change no map, flag, counter or
+ * generator; the results and the scratch of the sibling analyses are not touched. No kernel waits for another lane or workgroup.
+ * area is folded on the host, children into parents, in O(n). The scratch -- ten u32 planes and one f64 plane per cell, n records
+ * and n * nbins words per map and the list -- is allocated at first use and kept; an allocation that fails returns < 0 and leaves
+ * the context / the ensemble usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_catchments(smx_ctx* ctx, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size, uint32_t* hist,
+                   uint32_t nbins, double bin_height, uint32_t* gauge, uint32_t* straight, uint32_t* diagonal, double* drop);
+int smx_ensemble_catchments(smx_ensemble* e, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size,
+                            uint32_t* hist, uint32_t nbins, double bin_height);
 /* ---- dispersed flow: the multiple-flow-direction (MFD) contributing area in fixed point, every cell's donors and receivers, and per
  *      basin what arrives at its terminal and what leaks over its divides ----
  * Cells, h(c), wet cells, lakes, the receiver R(c), sinks, basins, first_cell and the rank are those of smx_drainage.

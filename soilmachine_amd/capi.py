@@ -162,6 +162,18 @@ class Flowpath(C.Structure):
         return d
 
 
+class Catchment(C.Structure):
+    """smx_catchment: one listed cell's record of smx_catchments / smx_ensemble_catchments (64 bytes)."""
+    _fields_ = [("cell", C.c_uint32), ("cells", C.c_uint32), ("area", C.c_uint32), ("downstream", C.c_uint32),
+                ("basin", C.c_uint32), ("steps_max", C.c_uint32), ("farthest_cell", C.c_uint32), ("flags", C.c_uint32),
+                ("straight_sum", C.c_uint64), ("diagonal_sum", C.c_uint64), ("drop_max", C.c_double), ("drop_sum_q40", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["drop_sum"] = int(self.drop_sum_q40) * 2.0 ** -40    # below the exact sum of the drops by less than cells * 2^-40
+        return d
+
+
 class Dispersal(C.Structure):
     """smx_dispersal_record: one basin's record of smx_dispersal / smx_ensemble_dispersal (64 bytes)."""
     _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("flags", C.c_uint32), ("peak_cell", C.c_uint32),
@@ -240,7 +252,10 @@ HILL_NONE = 0xFFFFFFFF                 # the entry / hillslope planes: a wet cel
 HILL_HAND_UNRELIABLE = 1                # smx_hillslope.flags
 PATH_NONE = 0xFFFFFFFF                 # the stem plane: a cell off the stems
 PATH_TERMINAL_WET = 1                  # smx_flowpath.flags
-DISPERSAL_ONE = 1 << 24                # one cell of dispersed area (the area plane, the *_q24 fields)
+CATCH_NONE = 0xFFFFFFFF                # the gauge plane: the entry is no gauge; smx_catchment.downstream: no gauge down the flow
+CATCH_DROP_UNRELIABLE, CATCH_WET, CATCH_SINK = 1, 2, 4                 # smx_catchment.flags
+CATCHMENT_MAX_BINS = 64                # SMX_CATCHMENT_MAX_BINS
+DISPERSAL_ONE = 1 << 24               # one cell of dispersed area (the area plane, the *_q24 fields)
 DISPERSAL_MAX_EXPONENT = 16
 
 PLANE_HEIGHT, PLANE_WATER, PLANE_WFREQ, PLANE_WINDFREQ = 0, 1, 2, 3    # SMX_PLANE_*
@@ -268,6 +283,7 @@ SYMBOLS = [
     "smx_through", "smx_ensemble_through", "smx_get_through_sweeps", "smx_ensemble_get_through_sweeps",
     "smx_hillslopes", "smx_ensemble_hillslopes",
     "smx_flowpaths", "smx_ensemble_flowpaths",
+    "smx_catchments", "smx_ensemble_catchments",
     "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_budget", "smx_ensemble_budget",
@@ -412,6 +428,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_hillslopes.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_flowpaths.argtypes = [vp, vp, u64, u32, C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32)]
     L.smx_ensemble_flowpaths.argtypes = [vp, vp, u64, u32, vp]
+    L.smx_catchments.argtypes = [vp, vp, u32, vp, u64, vp, u32, dbl, vp, vp, vp, vp]
+    L.smx_ensemble_catchments.argtypes = [vp, vp, u32, vp, u64, vp, u32, dbl]
     L.smx_dispersal.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
     L.smx_ensemble_dispersal.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_get_dispersal_rounds.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]

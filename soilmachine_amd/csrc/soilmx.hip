@@ -55,6 +55,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_streams.h"
 #include "soil_hills.h"
 #include "soil_paths.h"
+#include "soil_catch.h"
 #include "soil_disp.h"
 #include "soil_strata.h"
 #include "soil_budget.h"
@@ -557,6 +558,41 @@ __global__ void __launch_bounds__(LAKE_LANES) k_path_stem(const LakeMember* __re
   if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   path_stem_group(m, g, blockIdx.x, p.T, p.s.J, p.s.S, p.s.G, p.UP, p.FH, p.FS, p.PA, acc, nbasins + blockIdx.y, nprofile + blockIdx.y, o);
+}
+
+// ---------------- the catchments of listed outlets (smx_catchments / smx_ensemble_catchments; bodies: soil_catch.h) ----------------
+// Behind the drainage chain with its statistics and without its area step, on its planes; the pointer doubling is k_hill_jump.
+// k_catch_mark takes one lane per list entry, the others one lane per cell. k_catch_fold's table holds 512 cells' worth of gauges
+// (26 KB of LDS), k_catch_hist's 512 cells' worth of (gauge, bin) keys (4 KB).
+struct CatchPlanes {   // what the kernels around the jump rounds work on (soil_catch.h): s the first set for k_catch_init, the settled one behind the rounds
+  uint32_t *T, *R, *M;
+  HillSet s;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_catch_mark(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ list, uint32_t n, uint32_t* M) {
+  const LakeMember m = tab[blockIdx.y];
+  ObsGroup g;
+  catch_mark_group(m, g, blockIdx.x, list, n, M);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_catch_init(const LakeMember* __restrict__ tab, CatchPlanes p, CatchAcc* acc) {
+  const LakeMember m = tab[blockIdx.y];
+  const uint64_t n = (uint64_t)m.dimx * (uint64_t)m.dimy;
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= n) return;
+  ObsGroup g;
+  catch_init_group(m, g, blockIdx.x, (uint32_t)((n + LAKE_LANES - 1) / LAKE_LANES), p.R, p.M, p.s.J, p.s.S, p.s.G, acc);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_catch_fold(const LakeMember* __restrict__ tab, CatchPlanes p, CatchAcc* acc, uint32_t* gauge, double* drop) {
+  __shared__ CatchTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  catch_fold_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.T, p.R, p.M, p.s.J, p.s.S, p.s.G, acc, gauge, drop);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_catch_hist(const LakeMember* __restrict__ tab, CatchPlanes p, uint32_t* hist, uint32_t nbins, double bin_height) {
+  __shared__ CatchHistTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  catch_hist_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.M, p.s.J, hist, nbins, bin_height);
 }
 
 // ---------------- dispersed flow (smx_dispersal / smx_ensemble_dispersal; bodies: soil_disp.h) ----------------
@@ -2185,6 +2221,7 @@ struct smx_ctx : EventTimer {
   ForkScratch fork;                   // smx_copy_state into this context
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths: one each
   AnalysisScratch disp;                                                  // smx_dispersal
+  AnalysisScratch catchments;                                            // smx_catchments
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
   BudgetScratch budget;               // smx_budget of this context against a base
 };
@@ -3767,6 +3804,7 @@ struct smx_ensemble : EventTimer {
   ForkScratch fork;                       // smx_ensemble_fork
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes, _flowpaths: one each
   AnalysisScratch disp;                                                  // smx_ensemble_dispersal
+  AnalysisScratch catchments;                                            // smx_ensemble_catchments
   StrataScratch strata;                   // smx_ensemble_soil_totals
   BudgetScratch budget;                   // smx_ensemble_budget
 };
@@ -4227,8 +4265,8 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 }  // extern "C"
 
 // ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes, the flow paths ----------------
-// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths and their smx_ensemble_* twins; kernels:
-// soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h)
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths, smx_catchments and their smx_ensemble_*
+// twins; kernels: soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h, soil_catch.h)
 // One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
 // cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
 // stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
@@ -4242,7 +4280,7 @@ struct AnalysisCall {   // who runs an analysis: a context (its one map) or an e
 static AnalysisCall call_on(const char* who, smx_ctx*& ctx) { return {who, false, ctx->partial(), ctx->mem, ctx->stream, &ctx, 1u, ctx->err}; }
 static AnalysisCall call_on(const char* who, smx_ensemble* e) { return {who, true, false, e->mem, e->stream, e->members.data(), (uint32_t)e->members.size(), e->err}; }
 
-// The argument checks of the ten entry points, in the order they have always had -- an ensemble is asked for its device first, a
+// The argument checks of the analyses' entry points, in the order they have always had -- an ensemble is asked for its device first, a
 // context last; an empty ensemble is done (rc 0) before its counts pointer is looked at. false: the
 // entry point returns rc. (record: the name of the public struct; threshold: smx_streams' only)
 static bool analysis_begin(const AnalysisCall& c, const char* record, const char* counts_name, uint64_t struct_size, const uint32_t* threshold, const void* counts,
@@ -4776,6 +4814,76 @@ static int paths_run(const AnalysisCall& c, AnalysisScratch& k, smx_flowpath* ou
   return 0;
 }
 
+// ---- the catchments: ten planes and the f64 plane. The caller's list goes into the result region with the tables' upload; the mark
+// plane M (plane 3) is filled and k_catch_mark scatters the list into it for every member. The drainage chain with its statistics
+// through the bare table and WITHOUT its area step (T becomes the rank plane, no basin record is written), k_catch_init through the
+// table with the record caps (n a member), k rounds of k_hill_jump between the sets (4, 5, 6) and (7, 8, 9) -- k is known before the
+// launch from the cells of the largest map --, k_catch_fold on the set the last round wrote and, with bins, k_catch_hist on the
+// zeroed tables. The gauge plane goes to the other set's J, the drop to the f64 plane, the steps are the settled set itself. The
+// region holds the chain's counts, the records, the tables and the list; all but the list copied back with the planes asked for,
+// one synchronisation. The records are cut per map with area folded over the gauges' forest (catch_area).
+static_assert(sizeof(smx_catchment) == 64 && sizeof(CatchRec) == sizeof(smx_catchment) && offsetof(smx_catchment, area) == offsetof(CatchRec, area) &&
+              offsetof(smx_catchment, basin) == offsetof(CatchRec, basin) && offsetof(smx_catchment, farthest_cell) == offsetof(CatchRec, farthest_cell) &&
+              offsetof(smx_catchment, straight_sum) == offsetof(CatchRec, straight_sum) && offsetof(smx_catchment, drop_max) == offsetof(CatchRec, drop_max) &&
+              offsetof(smx_catchment, drop_sum_q40) == offsetof(CatchRec, drop_sum_q40) && (uint32_t)SMX_CATCHMENT_MAX_BINS == CATCH_MAX_BINS,
+              "smx_catchment layout");
+static int catch_run(const AnalysisCall& c, AnalysisScratch& k, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size, uint32_t* hist,
+                     uint32_t nbins, double bin_height, uint32_t* gauge, uint32_t* straight, uint32_t* diagonal, double* drop) {
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, n, CAP_CELLS, pl)) return rc;   // (n distinct cells inside every member: every member keeps n records)
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm), hist_at = rec_at + (size_t)pl.nrec * sizeof(CatchAcc);
+  const size_t hist_bytes = (size_t)pl.nrec * nbins * 4, list_at = hist_at + ((hist_bytes + 63) & ~(size_t)63);
+  need.words = (size_t)pl.words; need.planes = 10; need.f64 = true; need.members = c.nm; need.res_bytes = list_at + (size_t)n * 4;
+  if (!scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "catchment", pl.nrec)) return rc;
+  const HillSet set[2] = {{k.plane[4], k.plane[5], k.plane[6]}, {k.plane[7], k.plane[8], k.plane[9]}};
+  uint64_t largest = 0;
+  for (uint32_t i = 0; i < c.nm; i++) largest = std::max<uint64_t>(largest, c.ms[i]->ncells);
+  const uint32_t rounds = hill_rounds(largest - 1u);   // (a path has at most cells - 1 steps)
+  uint32_t* const B = k.plane[1];
+  const CatchPlanes first{k.plane[0], k.plane[2], k.plane[3], set[0]}, last{k.plane[0], k.plane[2], k.plane[3], set[rounds & 1u]};
+  uint32_t* const d_gauge = set[(rounds + 1u) & 1u].J;
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  CatchAcc* acc = reinterpret_cast<CatchAcc*>(k.d_res + rec_at);
+  uint32_t* d_hist = reinterpret_cast<uint32_t*>(k.d_res + hist_at);
+  uint32_t* d_list = reinterpret_cast<uint32_t*>(k.d_res + list_at);
+  const LakeMember* bare = k.d_tab + c.nm;
+  memcpy(k.h_res + list_at, cells, (size_t)n * 4);
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  ok = ok && hipMemcpyAsync(d_list, k.h_res + list_at, (size_t)n * 4, hipMemcpyHostToDevice, c.st) == hipSuccess;
+  ok = ok && hipMemsetAsync(first.M, 0xFF, (size_t)pl.words * 4, c.st) == hipSuccess;
+  ok = ok && (!nbins || hipMemsetAsync(d_hist, 0, hist_bytes, c.st) == hipSuccess);
+  if (ok) {
+    hipLaunchKernelGGL(k_catch_mark, dim3((unsigned)(((size_t)n + LAKE_LANES - 1) / LAKE_LANES), c.nm), pl.wg, 0, c.st, bare, d_list, n, first.M);
+    ok = launch_drain_chain(pl, c.st, k, bare, bare, first.T, B, first.R, nullptr, d_n, nullptr, nullptr);
+    hipLaunchKernelGGL(k_catch_init, pl.gf, pl.wg, 0, c.st, k.d_tab, first, acc);
+    for (uint32_t r = 0; r < rounds; r++) hipLaunchKernelGGL(k_hill_jump, pl.gf, pl.wg, 0, c.st, bare, set[r & 1u], set[(r + 1u) & 1u]);
+    hipLaunchKernelGGL(k_catch_fold, pl.gs, pl.wg, 0, c.st, k.d_tab, last, acc, gauge ? d_gauge : nullptr, drop ? k.h64 : nullptr);
+    if (nbins) hipLaunchKernelGGL(k_catch_hist, pl.gs, pl.wg, 0, c.st, k.d_tab, last, d_hist, nbins, bin_height);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, hist_at + hist_bytes);
+  // (smx_catchments only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, gauge, d_gauge, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, straight, last.s.S, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, diagonal, last.s.G, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, drop, k.h64, (size_t)pl.words * 8);
+  if (analysis_wait(c, ok, "the catchments")) return -1;
+  const CatchAcc* a = reinterpret_cast<const CatchAcc*>(k.h_res + rec_at);
+  const size_t take = struct_size < sizeof(CatchRec) ? (size_t)struct_size : sizeof(CatchRec);
+  std::vector<CatchRec> recs(n);
+  std::vector<uint32_t> work(2 * (size_t)n);
+  for (uint32_t i = 0; i < c.nm; i++) {
+    for (uint32_t r = 0; r < n; r++) catch_finish(a[(size_t)pl.tab[i].rec0 + r], recs[r]);
+    catch_area(recs.data(), n, work.data(), work.data() + n);
+    for (uint32_t r = 0; r < n; r++) memcpy(reinterpret_cast<char*>(out) + ((size_t)i * n + r) * (size_t)struct_size, &recs[r], take);
+  }
+  if (nbins) memcpy(hist, k.h_res + hist_at, hist_bytes);
+  return 0;
+}
+
 // ---- dispersed flow: planes T, B, R of the chain, P, RC, the list plane Q, and the 64-bit plane AQ in the f64 plane's place. The
 // drainage chain with its statistics and ITS records (first_cell, cells and flags of a dispersal record are the basin's), then
 // k_disp_pending. k_disp_flow in the round loop: DISP_BATCH launches, then ONE word back -- a bit per launch that found cells in
@@ -4980,6 +5088,58 @@ int smx_ensemble_flowpaths(smx_ensemble* e, smx_flowpath* out, uint64_t struct_s
   roctx_range rr("soilmx:ensemble_flowpaths");
   HIPCHK(e, hipSetDevice(e->device));
   return paths_run(c, e->paths, out, struct_size, cap_per_member, nbasins, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
+}
+// the checks of the two catchment calls behind analysis_begin's: the list, the records' room and the bins. Nothing is launched and
+// nothing written before all of them hold. (The list is read last: a call refused for its sizes never looks at it.)
+static bool catch_args_ok(const AnalysisCall& c, const uint32_t* cells, uint32_t n, const void* out, const uint32_t* hist, uint32_t nbins, double bin_height, int& rc) {
+  auto no = [&](const std::string& why) { c.err = std::string(c.who) + ": " + why; rc = -2; return false; };
+  if (!cells) return no("cells is null (the list of gauge cells)");
+  if (n == 0) return no("n is 0 (at least one gauge)");
+  if (!out) return no("out is null (" + std::to_string(n) + " records per map)");
+  if (nbins > CATCH_MAX_BINS) return no("nbins is " + std::to_string(nbins) + " (0 to " + std::to_string(CATCH_MAX_BINS) + ")");
+  if (nbins && !hist) return no("hist is null while nbins is " + std::to_string(nbins));
+  if (nbins && !(bin_height > 0.0 && std::isfinite(bin_height))) return no("bin_height is " + std::to_string(bin_height) + " (finite and positive)");
+  if ((uint64_t)n * nbins >= (1ull << 31)) return no("n * nbins is " + std::to_string((uint64_t)n * nbins) + " (below 2^31)");
+  uint64_t least = ~0ull; uint32_t which = 0;
+  for (uint32_t i = 0; i < c.nm; i++) if ((uint64_t)c.ms[i]->ncells < least) { least = c.ms[i]->ncells; which = i; }
+  for (uint32_t i = 0; i < n; i++)
+    if (cells[i] >= least)
+      return no("cells[" + std::to_string(i) + "] is " + std::to_string(cells[i]) + ", outside " + (c.ensemble ? "member " + std::to_string(which) : std::string("the map")) + " (" +
+                std::to_string(least) + " cells)");
+  std::vector<uint64_t> seen((size_t)((least + 63) / 64), 0ull);   // a bit per cell of the smallest member: O(n) for a list of any length
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t& w = seen[cells[i] >> 6];
+    const uint64_t bit = 1ull << (cells[i] & 63u);
+    if (w & bit) {
+      uint32_t of = 0u;
+      while (cells[of] != cells[i]) of++;
+      return no("cells[" + std::to_string(i) + "] repeats cells[" + std::to_string(of) + "] (cell " + std::to_string(cells[i]) + "): the gauges are distinct");
+    }
+    w |= bit;
+  }
+  return true;
+}
+int smx_catchments(smx_ctx* ctx, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size, uint32_t* hist, uint32_t nbins, double bin_height,
+                   uint32_t* gauge, uint32_t* straight, uint32_t* diagonal, double* drop) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_catchments", ctx);
+  int rc;
+  if (!analysis_begin(c, "smx_catchment", "cells", struct_size, nullptr, &rc, nullptr, 0u, rc)) return rc;   // (no counts and no cap: n records a map)
+  if (!catch_args_ok(c, cells, n, out, hist, nbins, bin_height, rc)) return rc;
+  roctx_range rr("soilmx:catchments");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return catch_run(c, ctx->catchments, cells, n, out, struct_size, hist, nbins, bin_height, gauge, straight, diagonal, drop);
+}
+int smx_ensemble_catchments(smx_ensemble* e, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size, uint32_t* hist, uint32_t nbins,
+                            double bin_height) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_catchments", e);
+  int rc;
+  if (!analysis_begin(c, "smx_catchment", "cells", struct_size, nullptr, &rc, nullptr, 0u, rc)) return rc;
+  if (!catch_args_ok(c, cells, n, out, hist, nbins, bin_height, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_catchments");
+  HIPCHK(e, hipSetDevice(e->device));
+  return catch_run(c, e->catchments, cells, n, out, struct_size, hist, nbins, bin_height, nullptr, nullptr, nullptr, nullptr);
 }
 int smx_dispersal(smx_ctx* ctx, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint64_t* area, uint32_t* donors,
                   uint32_t* receivers) {

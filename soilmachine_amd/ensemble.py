@@ -299,6 +299,27 @@ class Ensemble:
         count; else at most ``cap`` basins per member. Members may differ in size."""
         return self._analysis(lambda out, cap, counts: self.L.smx_ensemble_flowpaths(self.h, out, C.sizeof(capi.Flowpath), cap, counts), capi.Flowpath, cap)
 
+    def catchments(self, cells, bins: int = 0, bin_height: float | None = None) -> list:
+        """The catchment records of every member (``smx_ensemble_catchments``: the same launches whatever the member count): one list
+        of dicts per member, in member order, each as ``Layermap.catchments(cells, bins=bins, bin_height=bin_height)`` gives it.
+        ONE list serves every member, as flat indices into each member's own plane: give ``(x, y)`` pairs only where all members
+        have the same ``dimy`` (the first member's is used). Every listed cell has to lie inside every member."""
+        self._check_members()
+        nm = len(self.members)
+        cl = np.asarray(cells if isinstance(cells, np.ndarray) else list(cells), np.int64)
+        if cl.ndim == 2 and cl.shape[1] == 2:
+            cl = cl[:, 0] * (self.members[0].dimy if nm else 1) + cl[:, 1]
+        cl = np.ascontiguousarray(cl.reshape(-1), np.uint32)
+        n, bins = len(cl), int(bins)
+        out = (capi.Catchment * max(1, nm * n))()
+        hist = np.zeros((max(1, nm), n, bins), np.uint32) if bins else None
+        self._chk(self.L.smx_ensemble_catchments(self.h, capi.ptr(cl), n, out, C.sizeof(capi.Catchment), capi.ptr(hist), bins, float(bin_height or 0.0)))
+        res = [[out[i * n + k].as_dict() for k in range(n)] for i in range(nm)]
+        for i, recs in enumerate(res if bins else ()):
+            for k, r in enumerate(recs):
+                r["hist"] = hist[i, k].copy()
+        return res
+
     def dispersal(self, exponent: int = 1, cap: int | None = None) -> list:
         """The dispersed-flow records of every member (``smx_ensemble_dispersal``: the same launches whatever the member count): one
         list of dicts per member, in member order, each as ``Layermap.dispersal(exponent)`` gives it, record k for basin k of

@@ -322,6 +322,55 @@ class Layermap:
                 r["profile"] = prof[r["profile_at"]:r["profile_at"] + r["steps_max"] + 1].copy()
         return (recs, planes) if planes else recs
 
+    def catchments(self, cells, gauge: bool = False, straight: bool = False, diagonal: bool = False, drop: bool = False, bins: int = 0,
+                   bin_height: float | None = None):
+        """Which land drains through the listed cells (``smx_catchments``). ``cells``: a sequence of distinct flat indices x*dimy + y
+        or of ``(x, y)`` pairs -- gauges, dam sites, outlets; any cell may be one. One dict per listed cell, in list order --
+        ``cell``, ``cells`` (the OWN catchment: the cells whose way down meets this gauge before any other gauge, sink or wet cell,
+        the gauge cell included), ``area`` (``cells`` summed over the gauge and every gauge above it: the whole catchment, for a dry
+        gauge the ``area`` plane of ``drainage()`` at the cell), ``downstream`` (the list position of the next gauge down the flow,
+        0xFFFFFFFF without one), ``basin`` (the rank in ``drainage()``), ``steps_max`` / ``farthest_cell`` (the longest way to the
+        gauge inside the own catchment and the cell it starts at), ``straight_sum`` / ``diagonal_sum``, ``drop_max``,
+        ``drop_sum_q40`` (the exact integer sum of floor(drop * 2^40)) and ``drop_sum`` (that as a float) and ``flags`` (1:
+        ``drop_sum_q40`` unreliable, 2: the gauge cell is wet, 4: it is a sink). ``bins`` (1 to 64) with ``bin_height``: every dict
+        also gets ``hist``, the hypsometry of the own catchment -- ``hist[b]`` counts its cells with
+        ``b * bin_height <= drop < (b + 1) * bin_height``, the last bin everything above. With a plane asked for the result is
+        ``(records, planes)``, ``planes`` a dict of (dimx, dimy) arrays for EVERY cell: ``gauge`` (the list position of the cell's
+        entry, 0xFFFFFFFF where its water meets no gauge), ``straight`` / ``diagonal`` (the steps to the entry), uint32, and ``drop``
+        (float64, the height above the entry). One call, no count; sees every tick queued before it and changes nothing.
+
+        The catchments of chosen stream segments, delineated at their outlets::
+
+            segs = [s for s in m.streams(256) if s["order"] >= 3]
+            recs, planes = m.catchments([s["last_cell"] for s in segs], gauge=True)
+            own = planes["gauge"] == 0                  # the own catchment of segs[0]'s outlet
+
+        A gauge's WHOLE catchment is its own plus those of the gauges that have it as ``downstream``, and theirs in turn::
+
+            def whole(i):
+                mask = planes["gauge"] == i
+                for j, r in enumerate(recs):
+                    if r["downstream"] == i:
+                        mask |= whole(j)
+                return mask                             # mask.sum() == recs[i]["area"]
+        """
+        cl = np.asarray(cells if isinstance(cells, np.ndarray) else list(cells), np.int64)
+        if cl.ndim == 2 and cl.shape[1] == 2:
+            cl = cl[:, 0] * self.dimy + cl[:, 1]
+        cl = np.ascontiguousarray(cl.reshape(-1), np.uint32)
+        n, bins = len(cl), int(bins)
+        out = (capi.Catchment * max(1, n))()
+        hist = np.zeros((n, bins), np.uint32) if bins else None
+        wanted = [("gauge", gauge), ("straight", straight), ("diagonal", diagonal), ("drop", drop)]
+        got = {k: np.zeros(self.dimx * self.dimy, np.float64 if k == "drop" else np.uint32) for k, want in wanted if want}
+        self._chk(self.L.smx_catchments(self.h, capi.ptr(cl), n, out, C.sizeof(capi.Catchment), capi.ptr(hist), bins, float(bin_height or 0.0),
+                                        *[capi.ptr(got.get(k)) for k, _ in wanted]))
+        recs = [out[k].as_dict() for k in range(n)]
+        for k, r in enumerate(recs if bins else ()):
+            r["hist"] = hist[k].copy()
+        planes = {k: v.reshape(self.dimx, self.dimy) for k, v in got.items()}
+        return (recs, planes) if planes else recs
+
     def dispersal(self, exponent: int = 1, area: bool = False, donors: bool = False, receivers: bool = False, cap: int | None = None):
         """Dispersed flow (``smx_dispersal``): the multiple-flow-direction contributing area next to the D8 one of ``drainage()``. A
         dry cell splits its water over ALL lower neighbours in proportion to slope ** ``exponent`` (0 to 16; a diagonal step counts
