@@ -867,6 +867,26 @@ int smx_get_relax_settle(smx_ctx* ctx, uint64_t* crowded_cells, uint64_t* epochs
  * them, and those of them that found at least one cell flagged in the epoch in their tiles' rectangle widened by one cell -- a function of the input,
  * not of timing (whether the flood had to spin is not counted). Synchronises the context's stream. Any pointer may be null. */
 int smx_get_relax_flood_flow(smx_ctx* ctx, uint64_t* epochs_joined, uint64_t* floods_acted, uint64_t* floods_gated);
+/* the terrain analyses and the strata readers: the LAUNCH SHAPE of their three families of strided launches -- never the result
+ * (tests/test_gpu_analysis_launch.py runs small maps through the second and later iterations of every stride). Each value is the most
+ * workgroups (grid.x) of the family's launches; the workgroups stride over the rest of the work:
+ *   flow_blocks    k_disp_flow (smx_dispersal), default 1024: strides once a round's part of the ready list exceeds flow_blocks * 256 givers
+ *   relax_blocks   k_spill_relax, k_through_hops, k_through_exit (smx_spill, smx_through), default 2048: strides once a map has more than
+ *                  relax_blocks * 256 boundary cells
+ *   strata_blocks  k_strata_totals, k_strata_thickness, k_core_count, k_core_scatter (smx_soil_totals, smx_soil_thickness, smx_cores),
+ *                  default 8192: strides above strata_blocks * 64 columns or listed cells; smx_ensemble_soil_totals gives every member
+ *                  strata_blocks / members workgroups (at least one)
+ * 0 = the default; 1 .. the default = that many. Anything else: -2, a text in smx_last_error, nothing changed. The values belong to the
+ * owner of the call's scratch: a context's hold for the calls on that context, an ensemble's for the smx_ensemble_* calls, and neither
+ * reaches the other. Records, their order, the counts, every plane and the batches of smx_get_*_sweeps / smx_get_dispersal_rounds are
+ * bit-identical for every value; the number of relax and hop sweeps and of dispersal rounds may differ (a sweep works in place, a walk
+ * carries on into the next round's cells). */
+int smx_set_analysis_launch(smx_ctx* ctx, int32_t flow_blocks, int32_t relax_blocks, int32_t strata_blocks);
+int smx_ensemble_set_analysis_launch(smx_ensemble* ens, int32_t flow_blocks, int32_t relax_blocks, int32_t strata_blocks);
+/* ... and what is in force: blocks[3] = the three values (a default as its number), last_grid[3] = the grid.x that the last call on this
+ * owner gave the launches of each family (0: none yet). Needs no device work. Either pointer may be null. */
+int smx_get_analysis_launch(smx_ctx* ctx, int32_t* blocks, uint32_t* last_grid);
+int smx_ensemble_get_analysis_launch(smx_ensemble* ens, int32_t* blocks, uint32_t* last_grid);
 /* REMOVED in round 5 (nested particles run inside their parent since then; there is nothing to interleave): kept as a symbol that fails
  * loudly (-2, smx_last_error says so) so that a round-4 caller neither crashes at load time nor silently runs another schedule. */
 int smx_set_grid_interleave(smx_ctx* ctx, int32_t k);

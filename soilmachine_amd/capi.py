@@ -287,6 +287,7 @@ SYMBOLS = [
     "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_budget", "smx_ensemble_budget",
+    "smx_set_analysis_launch", "smx_ensemble_set_analysis_launch", "smx_get_analysis_launch", "smx_ensemble_get_analysis_launch",
     "smx_switches",
 ]
 
@@ -440,6 +441,10 @@ def load() -> C.CDLL:
     L.smx_cores.argtypes = [vp, vp, u32, vp, u64, C.POINTER(u64), vp, vp, vp, vp]
     L.smx_budget.argtypes = [vp, vp, vp, u64, u32, C.POINTER(u32), vp, u64, u32, vp, vp, vp, vp]
     L.smx_ensemble_budget.argtypes = [vp, vp, vp, u64, u32, C.POINTER(u32), vp, u64, u32]
+    L.smx_set_analysis_launch.argtypes = [vp, i32, i32, i32]
+    L.smx_ensemble_set_analysis_launch.argtypes = [vp, i32, i32, i32]
+    L.smx_get_analysis_launch.argtypes = [vp, vp, vp]
+    L.smx_ensemble_get_analysis_launch.argtypes = [vp, vp, vp]
     L.smx_switches.argtypes = [C.c_char_p, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         f = getattr(L, name)

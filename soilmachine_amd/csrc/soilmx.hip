@@ -2153,6 +2153,17 @@ struct BudgetScratch {
   char* d_planes = nullptr; size_t planes_cap = 0;
 };
 
+// smx_set_analysis_launch: the most workgroups (grid.x) of the three families of launches that stride -- k_disp_flow; k_spill_relax,
+// k_through_hops and k_through_exit; the strata readers -- and the grid.x the owner's last call gave each. A launch shape, never a result.
+constexpr size_t STRATA_GRID = 8192;   // workgroups of one strata launch at most: 32 wavefronts per compute unit, the rest is strided
+enum { LAUNCH_FLOW, LAUNCH_RELAX, LAUNCH_STRATA };
+struct AnalysisLaunch {
+  int32_t set[3] = {0, 0, 0};     // 0: the default
+  uint32_t grid[3] = {0, 0, 0};   // 0: no launch of the family yet
+  static uint32_t most(int which) { return which == LAUNCH_FLOW ? (uint32_t)DISP_FLOW_BLOCKS : which == LAUNCH_RELAX ? (uint32_t)SPILL_RELAX_BLOCKS : (uint32_t)STRATA_GRID; }
+  uint32_t cap(int which) const { return set[which] ? (uint32_t)set[which] : most(which); }
+};
+
 struct smx_ctx : EventTimer {
   smx_config cfg;
   DevState d;
@@ -2224,6 +2235,7 @@ struct smx_ctx : EventTimer {
   AnalysisScratch catchments;                                            // smx_catchments
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
   BudgetScratch budget;               // smx_budget of this context against a base
+  AnalysisLaunch launch;              // smx_set_analysis_launch
 };
 
 // a failed HIP call: its text and the runtime's message go to the `err` of `obj` (a context, an ensemble, a lattice), the function returns -1
@@ -3807,6 +3819,7 @@ struct smx_ensemble : EventTimer {
   AnalysisScratch catchments;                                            // smx_ensemble_catchments
   StrataScratch strata;                   // smx_ensemble_soil_totals
   BudgetScratch budget;                   // smx_ensemble_budget
+  AnalysisLaunch launch;                  // smx_ensemble_set_analysis_launch
 };
 
 static int ens_reserve(smx_ensemble* e, uint32_t n) {   // tables for n members (the old ones are dropped once the stream is idle)
@@ -4276,9 +4289,10 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 struct AnalysisCall {   // who runs an analysis: a context (its one map) or an ensemble (its members)
   const char* who; bool ensemble, partial;
   DevMem& mem; hipStream_t st; smx_ctx* const* ms; uint32_t nm; std::string& err;
+  AnalysisLaunch& launch;   // the owner's (smx_set_analysis_launch)
 };
-static AnalysisCall call_on(const char* who, smx_ctx*& ctx) { return {who, false, ctx->partial(), ctx->mem, ctx->stream, &ctx, 1u, ctx->err}; }
-static AnalysisCall call_on(const char* who, smx_ensemble* e) { return {who, true, false, e->mem, e->stream, e->members.data(), (uint32_t)e->members.size(), e->err}; }
+static AnalysisCall call_on(const char* who, smx_ctx*& ctx) { return {who, false, ctx->partial(), ctx->mem, ctx->stream, &ctx, 1u, ctx->err, ctx->launch}; }
+static AnalysisCall call_on(const char* who, smx_ensemble* e) { return {who, true, false, e->mem, e->stream, e->members.data(), (uint32_t)e->members.size(), e->err, e->launch}; }
 
 // The argument checks of the analyses' entry points, in the order they have always had -- an ensemble is asked for its device first, a
 // context last; an empty ensemble is done (rc 0) before its counts pointer is looked at. false: the
@@ -4329,10 +4343,11 @@ static int plan_members(const AnalysisCall& c, uint32_t cap, CapRule rule, Analy
   pl.gt = dim3((unsigned)tiles, c.nm); pl.gf = dim3((unsigned)flat, c.nm); pl.gs = dim3((unsigned)stat, c.nm);
   return 0;
 }
-static void plan_basins(AnalysisPlan& pl, const uint32_t* counts) {   // spill and through, the chain's counts back: a record for every basin
+static void plan_basins(const AnalysisCall& c, AnalysisPlan& pl, const uint32_t* counts) {   // spill and through, the chain's counts back: a record for every basin
   pl.nrec = 0; pl.most = 0;
   for (LakeMember& m : pl.tab) { m.cap = *counts++; m.rec0 = (uint32_t)pl.nrec; pl.nrec += m.cap; pl.most = std::max(pl.most, m.cap); }
-  pl.gb = dim3((unsigned)(((size_t)pl.most + LAKE_LANES - 1) / LAKE_LANES), pl.gt.y); pl.gr = dim3(std::min<unsigned>(pl.gf.x, SPILL_RELAX_BLOCKS), pl.gt.y);
+  pl.gb = dim3((unsigned)(((size_t)pl.most + LAKE_LANES - 1) / LAKE_LANES), pl.gt.y); pl.gr = dim3(std::min<unsigned>(pl.gf.x, c.launch.cap(LAUNCH_RELAX)), pl.gt.y);
+  c.launch.grid[LAUNCH_RELAX] = pl.gr.x;
 }
 // the plan's table into half `half` of the pinned tables (bare: every cap 0), and `halves` halves from `half` on to the device
 static void put_table(AnalysisScratch& k, const AnalysisPlan& pl, uint32_t half, bool bare) {
@@ -4582,7 +4597,7 @@ static int spill_run(const AnalysisCall& c, AnalysisScratch& k, smx_spill_record
   ok = ok && hipGetLastError() == hipSuccess;
   ok = copy_back(c, ok, k.h_cnt, k.d_cnt, (size_t)c.nm * 4);
   if (analysis_wait(c, ok, "the drainage chain")) return -1;
-  plan_basins(pl, k.h_cnt);
+  plan_basins(c, pl, k.h_cnt);
   need.res_bytes = (size_t)pl.nrec * sizeof(SpillAcc);
   if (int rc = analysis_reserve(c, k, need, "spill", pl.nrec)) return rc;   // (the stream is idle)
   SpillAcc* acc = reinterpret_cast<SpillAcc*>(k.d_res);
@@ -4642,7 +4657,7 @@ static int through_run(const AnalysisCall& c, AnalysisScratch& k, smx_through_re
   ok = ok && hipGetLastError() == hipSuccess;
   ok = copy_back(c, ok, k.h_cnt, k.d_cnt, (size_t)c.nm * 4);
   if (analysis_wait(c, ok, "the drainage chain")) return -1;
-  plan_basins(pl, k.h_cnt);
+  plan_basins(c, pl, k.h_cnt);
   need.res_bytes = (size_t)pl.nrec * (sizeof(SpillAcc) + sizeof(ThroughAcc));
   if (int rc = analysis_reserve(c, k, need, "through-drainage", pl.nrec)) return rc;   // (the stream is idle)
   const size_t acc_at = (size_t)pl.nrec * sizeof(SpillAcc);
@@ -4915,7 +4930,8 @@ static int disp_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t exponent
   uint32_t* const h_busy = k.h_cnt + (size_t)c.nm * DISP_RING;
   uint64_t largest = 0;
   for (uint32_t i = 0; i < c.nm; i++) largest = std::max<uint64_t>(largest, c.ms[i]->ncells);
-  const dim3 gw(std::min<unsigned>(pl.gf.x, DISP_FLOW_BLOCKS), pl.gf.y);
+  const dim3 gw(std::min<unsigned>(pl.gf.x, c.launch.cap(LAUNCH_FLOW)), pl.gf.y);
+  c.launch.grid[LAUNCH_FLOW] = gw.x;
   put_table(k, pl, 0, false); put_table(k, pl, 1, true);
   bool ok = send_tables(c, k, 0, 2);
   ok = ok && hipMemsetAsync(ring, 0, (size_t)c.nm * DISP_RING * 4, c.st) == hipSuccess;
@@ -5192,10 +5208,37 @@ int smx_ensemble_get_dispersal_rounds(smx_ensemble* e, uint32_t* rounds, uint32_
   return e ? sweeps_of(e->disp, e->err, "smx_ensemble_get_dispersal_rounds", rounds, &none, batches) : -2;
 }
 
+// The launch shape of the analyses' strided launches, on a context and on an ensemble: stored whole or not at all.
+static int set_analysis_launch(AnalysisLaunch& a, std::string& err, const char* who, int32_t flow_blocks, int32_t relax_blocks, int32_t strata_blocks) {
+  static const char* const name[3] = {"flow_blocks", "relax_blocks", "strata_blocks"};
+  const int32_t v[3] = {flow_blocks, relax_blocks, strata_blocks};
+  for (int i = 0; i < 3; i++)
+    if (v[i] < 0 || (uint32_t)v[i] > AnalysisLaunch::most(i)) {
+      err = std::string(who) + ": " + name[i] + " is " + std::to_string(v[i]) + ", outside 0.." + std::to_string(AnalysisLaunch::most(i)) + " (0: the default; nothing was changed)";
+      return -2;
+    }
+  for (int i = 0; i < 3; i++) a.set[i] = v[i];
+  return 0;
+}
+static int get_analysis_launch(const AnalysisLaunch& a, int32_t* blocks, uint32_t* last_grid) {
+  for (int i = 0; i < 3; i++) {
+    if (blocks) blocks[i] = (int32_t)a.cap(i);
+    if (last_grid) last_grid[i] = a.grid[i];
+  }
+  return 0;
+}
+int smx_set_analysis_launch(smx_ctx* ctx, int32_t flow_blocks, int32_t relax_blocks, int32_t strata_blocks) {
+  return ctx ? set_analysis_launch(ctx->launch, ctx->err, "smx_set_analysis_launch", flow_blocks, relax_blocks, strata_blocks) : -2;
+}
+int smx_ensemble_set_analysis_launch(smx_ensemble* e, int32_t flow_blocks, int32_t relax_blocks, int32_t strata_blocks) {
+  return e ? set_analysis_launch(e->launch, e->err, "smx_ensemble_set_analysis_launch", flow_blocks, relax_blocks, strata_blocks) : -2;
+}
+int smx_get_analysis_launch(smx_ctx* ctx, int32_t* blocks, uint32_t* last_grid) { return ctx ? get_analysis_launch(ctx->launch, blocks, last_grid) : -2; }
+int smx_ensemble_get_analysis_launch(smx_ensemble* e, int32_t* blocks, uint32_t* last_grid) { return e ? get_analysis_launch(e->launch, blocks, last_grid) : -2; }
+
 // ---------------- reading the strata (smx_soil_totals / smx_ensemble_soil_totals / smx_soil_thickness / smx_cores; kernels: soil_strata.h) ----------------
 static_assert(sizeof(smx_soil_total) == 48 && sizeof(StrataRec) == sizeof(smx_soil_total) && offsetof(smx_soil_total, flags) == offsetof(StrataRec, flags) &&
               (int)SMX_TOTALS_MAX_TYPES == STRATA_MAX_TYPES, "smx_soil_total layout");
-constexpr size_t STRATA_GRID = 8192;   // workgroups of one launch at most: 32 wavefronts per compute unit, the rest is strided
 static size_t strata_blocks(uint64_t items, size_t most) { return (size_t)std::max<uint64_t>(1, std::min<uint64_t>((items + STRATA_LANES - 1) / STRATA_LANES, most)); }
 static size_t strata_pad(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
 static StrataMap strata_map(const smx_ctx* c) {
@@ -5222,7 +5265,7 @@ static std::string strata_bad_text(const char* who, const smx_ctx* c, uint64_t w
 }
 
 // One path for both totals calls: one table upload, one memset of the results, one launch, the results back, one synchronisation.
-static int totals_run(const char* who, StrataScratch& k, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, bool ensemble, smx_soil_total* out,
+static int totals_run(const char* who, StrataScratch& k, AnalysisLaunch& launch, DevMem& mem, hipStream_t st, smx_ctx* const* ms, uint32_t nm, bool ensemble, smx_soil_total* out,
                       uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections, std::string& err) {
   const size_t tab_bytes = strata_pad((size_t)nm * sizeof(StrataMap)), nrec = (size_t)nm * ntypes;
   const size_t res_bytes = (size_t)nm * 16 + nrec * sizeof(StrataRec);   // error words, counts of other sections, records
@@ -5240,7 +5283,8 @@ static int totals_run(const char* who, StrataScratch& k, DevMem& mem, hipStream_
   bool ok = hipMemcpyAsync(k.d_buf, k.h_buf, (size_t)nm * sizeof(StrataMap), hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemsetAsync(d_bad, 0, res_bytes, st) == hipSuccess;
   if (ok) {
-    const size_t bx = strata_blocks(most, std::max<size_t>(1, STRATA_GRID / nm));
+    const size_t bx = strata_blocks(most, std::max<size_t>(1, launch.cap(LAUNCH_STRATA) / nm));
+    launch.grid[LAUNCH_STRATA] = (uint32_t)bx;
     hipLaunchKernelGGL(k_strata_totals, dim3((unsigned)bx, nm), dim3(STRATA_LANES), 0, st, reinterpret_cast<const StrataMap*>(k.d_buf), ntypes, d_acc, d_other, d_bad);
     ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(k.h_buf + tab_bytes, d_bad, res_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
   }
@@ -5265,7 +5309,7 @@ int smx_soil_totals(smx_ctx* ctx, smx_soil_total* out, uint64_t struct_size, uin
   if (!ctx->stream) { ctx->err = "smx_soil_totals: a context without a device"; return -3; }
   roctx_range rr("soilmx:soil_totals");
   HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
-  return totals_run("smx_soil_totals", ctx->strata, ctx->mem, ctx->stream, &ctx, 1u, false, out, struct_size, ntypes, other_sections, ctx->err);
+  return totals_run("smx_soil_totals", ctx->strata, ctx->launch, ctx->mem, ctx->stream, &ctx, 1u, false, out, struct_size, ntypes, other_sections, ctx->err);
 }
 int smx_ensemble_soil_totals(smx_ensemble* e, smx_soil_total* out, uint64_t struct_size, uint32_t ntypes, uint64_t* other_sections) {
   if (!e) return -2;
@@ -5277,7 +5321,7 @@ int smx_ensemble_soil_totals(smx_ensemble* e, smx_soil_total* out, uint64_t stru
   if (!out) { e->err = "smx_ensemble_soil_totals: out is null (ntypes records per member)"; return -2; }
   roctx_range rr("soilmx:ensemble_soil_totals");
   HIPCHK(e, hipSetDevice(e->device));
-  return totals_run("smx_ensemble_soil_totals", e->strata, e->mem, e->stream, e->members.data(), nm, true, out, struct_size, ntypes, other_sections, e->err);
+  return totals_run("smx_ensemble_soil_totals", e->strata, e->launch, e->mem, e->stream, e->members.data(), nm, true, out, struct_size, ntypes, other_sections, e->err);
 }
 
 int smx_soil_thickness(smx_ctx* ctx, const uint32_t* types, int32_t ntypes, double* thickness, double* cover, uint32_t* sections) {
@@ -5304,7 +5348,9 @@ int smx_soil_thickness(smx_ctx* ctx, const uint32_t* types, int32_t ntypes, doub
   double* d_cv = cover ? reinterpret_cast<double*>(k.d_sec + at_cover) : nullptr;
   uint32_t* d_n = sections ? reinterpret_cast<uint32_t*>(k.d_sec + at_sec) : nullptr;
   HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-  hipLaunchKernelGGL(k_strata_thickness, dim3((unsigned)strata_blocks(ctx->ncells, STRATA_GRID)), dim3(STRATA_LANES), 0, ctx->stream, strata_map(ctx), ty, d_th, d_cv, d_n, d_bad);
+  const unsigned nb = (unsigned)strata_blocks(ctx->ncells, ctx->launch.cap(LAUNCH_STRATA));
+  ctx->launch.grid[LAUNCH_STRATA] = nb;
+  hipLaunchKernelGGL(k_strata_thickness, dim3(nb), dim3(STRATA_LANES), 0, ctx->stream, strata_map(ctx), ty, d_th, d_cv, d_n, d_bad);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(k.h_buf, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the verdict first: a bad chain writes nothing to the caller
@@ -5348,7 +5394,8 @@ int smx_cores(smx_ctx* ctx, const uint32_t* cells, uint32_t n, uint32_t* count, 
   uint32_t* d_count = reinterpret_cast<uint32_t*>(k.d_buf + at_count);
   uint64_t* d_base = reinterpret_cast<uint64_t*>(k.d_buf + at_base);
   const StrataMap m = strata_map(ctx);
-  const unsigned nb = (unsigned)strata_blocks(n, STRATA_GRID);
+  const unsigned nb = (unsigned)strata_blocks(n, ctx->launch.cap(LAUNCH_STRATA));
+  ctx->launch.grid[LAUNCH_STRATA] = nb;
   HIPCHK(ctx, hipMemsetAsync(d_word, 0, 16, st));
   HIPCHK(ctx, hipMemcpyAsync(d_list, cells, (size_t)n * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_core_count, dim3(nb), dim3(STRATA_LANES), 0, st, m, d_list, (uint64_t)n, d_count, d_word);
@@ -5399,7 +5446,7 @@ static_assert(sizeof(smx_budget_soil) == 64 && sizeof(BudgetSoilRec) == sizeof(s
 static int budget_run(const AnalysisCall& c, BudgetScratch& ks, smx_ctx* base, smx_budget_basin* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins,
                       smx_budget_soil* soils, uint64_t soil_struct_size, uint32_t ntypes, double* dground, double* dheight, int64_t* dsolid, int64_t* dwater) {
   AnalysisScratch& k = ks.a;
-  const AnalysisCall cb{c.who, false, false, c.mem, c.st, &base, 1u, c.err};   // the chain's call: the base alone
+  const AnalysisCall cb{c.who, false, false, c.mem, c.st, &base, 1u, c.err, c.launch};   // the chain's call: the base alone
   AnalysisPlan pl;
   if (int rc = plan_members(cb, cap, CAP_CELLS, pl)) return rc;
   const uint32_t nm = c.nm, bcap = pl.tab[0].cap, nt = soils ? ntypes : 0u;

@@ -359,6 +359,19 @@ class Ensemble:
         self._chk(self.L.smx_ensemble_get_through_sweeps(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    def set_analysis_launch(self, flow_blocks: int = 0, relax_blocks: int = 0, strata_blocks: int = 0):
+        """The launch shape of this ensemble's ``dispersal()``, ``spill()`` / ``through()`` and ``soil_totals()``, never a result
+        (``smx_ensemble_set_analysis_launch``; see ``Layermap.set_analysis_launch``). ``soil_totals()`` gives every member
+        ``strata_blocks // len(ensemble)`` workgroups, at least one. Holds for the calls on the ensemble, not for a member's own."""
+        self._chk(self.L.smx_ensemble_set_analysis_launch(self.h, int(flow_blocks), int(relax_blocks), int(strata_blocks)))
+
+    def analysis_launch(self) -> dict:
+        """The values in force and the workgroups of the last call's launches, as ``Layermap.analysis_launch`` gives them."""
+        b, g = (C.c_int32 * 3)(), (C.c_uint32 * 3)()
+        self._chk(self.L.smx_ensemble_get_analysis_launch(self.h, b, g))
+        return {"flow_blocks": int(b[0]), "relax_blocks": int(b[1]), "strata_blocks": int(b[2]),
+                "flow_grid": int(g[0]), "relax_grid": int(g[1]), "strata_grid": int(g[2])}
+
     def soil_totals(self, ntypes: int, other: bool = False) -> list:
         """The soil totals of every member (``smx_ensemble_soil_totals``: one table upload and one launch whatever the member count):
         one list of ``ntypes`` dicts per member, in member order, each as ``Layermap.soil_totals(ntypes)`` gives it. ``other``: a pair,

@@ -538,6 +538,21 @@ class Layermap:
         resident wavefronts the fused launch may count on (0 = the device's), lanes = flagged cells per wavefront (0 = the rule's)"""
         self._chk(self.L.smx_set_relax_settle(self.h, int(mode), int(max_waves), int(lanes)))
 
+    def set_analysis_launch(self, flow_blocks: int = 0, relax_blocks: int = 0, strata_blocks: int = 0):
+        """the analyses' strided launches: launch shape only, never the result (smx_set_analysis_launch): the most workgroups of
+        ``dispersal()``'s flow rounds (default 1024), of the relax, hop and exit sweeps of ``spill()`` and ``through()`` (2048) and of
+        ``soil_totals()``, ``soil_thickness()`` and ``cores()`` (8192); 0 = the default. Holds for the calls on this map, not for an
+        ensemble's"""
+        self._chk(self.L.smx_set_analysis_launch(self.h, int(flow_blocks), int(relax_blocks), int(strata_blocks)))
+
+    def analysis_launch(self) -> dict:
+        """the values of ``set_analysis_launch`` in force (a default as its number) and, under ``flow_grid`` / ``relax_grid`` /
+        ``strata_grid``, the workgroups the last call on this map gave each family's launches (0: none yet)"""
+        b, g = (C.c_int32 * 3)(), (C.c_uint32 * 3)()
+        self._chk(self.L.smx_get_analysis_launch(self.h, b, g))
+        return {"flow_blocks": int(b[0]), "relax_blocks": int(b[1]), "strata_blocks": int(b[2]),
+                "flow_grid": int(g[0]), "relax_grid": int(g[1]), "strata_grid": int(g[2])}
+
     def relax_settle_stats(self) -> dict:
         """cells that went through the waiting (crowded) path of k_relax_settle; dense epochs that took the fused / the two-launch path"""
         c, f, s = C.c_uint64(), C.c_uint64(), C.c_uint64()

@@ -170,37 +170,39 @@ class Streams(Analysis):
 
 class Spill(Analysis):
     name, entry, headers, record = "spill", "sh_spill", ("soil_drain.h", "soil_spill.h"), capi.Spill
-    includes, shapes, struct_size, tail = (Drainage,), ("sh", 4, 4), True, (C.POINTER(u32), C.POINTER(u32))
+    includes, shapes, scalars, struct_size, tail = (Drainage,), ("sh", 4, 4), (u32,), True, (C.POINTER(u32), C.POINTER(u32))
     planes = {"filled": np.float64}
+    RELAX_BLOCKS = 0xFFFFFFFF              # a lane per cell: no stride (the library's cap, SPILL_RELAX_BLOCKS, is 2048)
 
-    def run_many(self, maps, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True):
+    def run_many(self, maps, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True, relax_blocks: int = RELAX_BLOCKS):
         """([(records, filled plane or None, nbasins) per map], (sweeps, batches)). order: bit 0 the workgroups, bit 1 the lanes,
-        last to first."""
+        last to first; relax_blocks: the workgroups of a relax sweep at most."""
         sw, ba = u32(), u32()
-        res = self._run(maps, variant, lanes, order, (), cap, self.PLANES if filled else (), [C.byref(sw), C.byref(ba)])
+        res = self._run(maps, variant, lanes, order, (relax_blocks,), cap, self.PLANES if filled else (), [C.byref(sw), C.byref(ba)])
         return [(recs, pl.get("filled"), n) for recs, pl, n in res], (int(sw.value), int(ba.value))
 
-    def run(self, s: Snapshot, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True):
+    def run(self, s: Snapshot, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, filled: bool = True, relax_blocks: int = RELAX_BLOCKS):
         """((records, filled plane, nbasins), (sweeps, batches)) of one snapshot."""
-        res, sweeps = self.run_many([self.HostMap(s)], variant, lanes, order, cap, filled)
+        res, sweeps = self.run_many([self.HostMap(s)], variant, lanes, order, cap, filled, relax_blocks)
         return res[0], sweeps
 
 
 class Through(Analysis):
     name, entry, headers, record = "through", "th_through", ("soil_drain.h", "soil_spill.h", "soil_through.h"), capi.Through
-    includes, shapes, struct_size, tail = (Drainage,), ("th", 4, 4), True, (vp,)
+    includes, shapes, scalars, struct_size, tail = (Drainage,), ("th", 4, 4), (u32,), True, (vp,)
     planes = {"through_area": np.uint32, "outlets": np.uint32}
+    RELAX_BLOCKS = Spill.RELAX_BLOCKS
 
-    def run_many(self, maps, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, planes: bool = True):
+    def run_many(self, maps, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, planes: bool = True, relax_blocks: int = RELAX_BLOCKS):
         """([(records, planes dict or None, nbasins) per map], (level sweeps, hop sweeps, batches)). order: bit 0 the workgroups,
-        bit 1 the lanes, last to first."""
+        bit 1 the lanes, last to first; relax_blocks: the workgroups of a relax sweep, a hop sweep and the exit at most."""
         sw = np.zeros(3, np.uint32)
-        res = self._run(maps, variant, lanes, order, (), cap, self.PLANES if planes else (), [capi.ptr(sw)])
+        res = self._run(maps, variant, lanes, order, (relax_blocks,), cap, self.PLANES if planes else (), [capi.ptr(sw)])
         return [(recs, pl if planes else None, n) for recs, pl, n in res], tuple(int(v) for v in sw)
 
-    def run(self, s: Snapshot, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, planes: bool = True):
+    def run(self, s: Snapshot, variant: int = 0, lanes: int = 256, order: int = 0, cap: int | None = None, planes: bool = True, relax_blocks: int = RELAX_BLOCKS):
         """((records, planes, nbasins), (level sweeps, hop sweeps, batches)) of one snapshot."""
-        res, sweeps = self.run_many([self.HostMap(s)], variant, lanes, order, cap, planes)
+        res, sweeps = self.run_many([self.HostMap(s)], variant, lanes, order, cap, planes, relax_blocks)
         return res[0], sweeps
 
 

@@ -5,12 +5,14 @@
 // after the other and the workgroups of a launch one after the other, in ascending or descending order, as drainage_host does; the
 // relax sweeps run lane by lane (the body has no barrier), so the order decides how far a level travels in one sweep -- and must not
 // decide where it ends. The host loop around the sweeps is the library's: batches of SPILL_BATCH, stop after the batch that holds a
-// sweep that changed nothing, give up after nbasins + 2. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
+// sweep that changed nothing, give up after nbasins + 2. A relax sweep has min(a lane per cell, relax_blocks) workgroups, as the
+// library caps its launch: the workgroups stride over the rest of the boundary list. tests/analysis_host_lib.py builds and binds this
+// file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_spill.h"
 
 template <int TX, int TY, int PS, int SLOTS>
-static int run_spill(std::vector<LakeMember> tab, uint32_t lanes, int descending, int lanes_descending, bool filled, std::vector<double>& H,
+static int run_spill(std::vector<LakeMember> tab, uint32_t lanes, int descending, int lanes_descending, uint32_t relax_blocks, bool filled, std::vector<double>& H,
                      std::vector<SpillAcc>& acc, uint32_t* nbasins, uint32_t* sweeps, uint32_t* batches) {
   static double hs[(TX + 2) * (TY + 2)];             // (the "LDS")
   static uint32_t ls[(TX + 2) * (TY + 2)];
@@ -61,7 +63,7 @@ static int run_spill(std::vector<LakeMember> tab, uint32_t lanes, int descending
     for (uint32_t j = 0; j < SPILL_BATCH; j++) {
       changed[j] = 0u;
       for (const LakeMember& m : tab) {
-        const uint32_t nb = (uint32_t)(((uint64_t)m.dimx * m.dimy + lanes - 1) / lanes);   // (the device launches at most as many)
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(((uint64_t)m.dimx * m.dimy + lanes - 1) / lanes, relax_blocks);   // (the library's cap: the rest is strided)
         for (uint32_t b = 0; b < nb; b++)
           for (uint32_t l = 0; l < lanes; l++) {
             DrainHostLane one{lanes, nth(l, lanes, lanes_descending)};
@@ -94,11 +96,12 @@ uint32_t sh_batch() { return SPILL_BATCH; }
 
 // The spill analysis of maps[0..nm) in one go, as smx_ensemble_spill runs it (nm == 1: smx_spill). out: nm * cap records of
 // struct_size bytes (the prefix of each 64-byte record, as the library cuts it), map i's from record i * cap; nbasins: one count
-// per map; filled: the planes of all maps, one after the other (NULL = skip); sweeps / batches: as smx_get_spill_sweeps. lanes and order as dh_drainage. 0, -2 for a bad argument, -1 where the levels did not
-// settle within the bound.
-int sh_spill(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t cap, void* out, uint64_t struct_size, uint32_t* nbasins,
-             double* filled, uint32_t* sweeps, uint32_t* batches) {
-  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || !nbasins || !sweeps || !batches || (!out && cap)) return -2;
+// per map; filled: the planes of all maps, one after the other (NULL = skip); sweeps / batches: as smx_get_spill_sweeps. lanes and order as dh_drainage;
+// relax_blocks: the workgroups of a relax sweep at most (>= 1). 0, -2 for a bad argument, -1 where the levels did not settle within
+// the bound.
+int sh_spill(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t relax_blocks, uint32_t cap, void* out, uint64_t struct_size,
+             uint32_t* nbasins, double* filled, uint32_t* sweeps, uint32_t* batches) {
+  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || relax_blocks == 0 || !nbasins || !sweeps || !batches || (!out && cap)) return -2;
   Members pl = plan_members(maps, nm, cap, CAP_NONE);
   std::vector<double> H(pl.words, -12345.0);
   std::vector<SpillAcc> acc;
@@ -106,7 +109,7 @@ int sh_spill(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int 
   int rc = 0;
   if (!with_shape<PASS_SHAPES>(variant, [&](auto s) {
         using S = decltype(s);
-        rc = run_spill<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, filled != nullptr, H, acc, nbasins, sweeps, batches);
+        rc = run_spill<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, relax_blocks, filled != nullptr, H, acc, nbasins, sweeps, batches);
       })) return -2;
   if (rc) return rc;
   plan_basins(pl, nbasins);   // (as run_spill laid its copy of the table out)

@@ -1,8 +1,9 @@
 """Spill analysis on the CPU: soil_spill.h compiled by g++ (tests/spill_host) against the independent restatement tests/spill_ref.py.
 
 Every record field, the count and the filled plane must equal the restatement exactly (floats by their bits), for every tile shape,
-every workgroup width and every launch order the host build offers: the order decides how many sweeps the fill levels take, never
-where they end. The filled plane is held against a heap priority flood that knows nothing of basins."""
+every workgroup width and every launch order the host build offers, and for relax sweeps of 1 and 3 workgroups that stride over the
+boundary list as the library's capped launch does: the order and the stride decide how many sweeps the fill levels take, never where
+they end. The filled plane is held against a heap priority flood that knows nothing of basins."""
 import ctypes as C
 import struct
 
@@ -24,19 +25,25 @@ def _bound(rounds):
     return -(-rounds // G) * G
 
 
+CAPPED = (1, 3)                            # relax_blocks below a lane per cell: the workgroups stride over the boundary list
+FULL = H.RELAX_BLOCKS
+
+
 def _runs(dims):
-    """(variant, lanes, order): every shape x width, all four launch orders on two of the shapes; at 128^2 two shapes, both ends."""
+    """(variant, lanes, order, relax_blocks). At full width every shape x width, all four launch orders on two of the shapes; at
+    128^2 two shapes, both ends. Then relax sweeps of 1 and 3 workgroups on the kernels' own shape: both widths, both ends."""
+    capped = [(0, lanes, order, blocks) for blocks in CAPPED for lanes in WIDTHS for order in (0, 3)]
     if tuple(dims) == tuple(R.BIG):
-        return [(0, 256, 0), (0, 64, 3), (2, 64, 0), (2, 256, 3)]
-    return [(v, lanes, order) for v in VARIANTS for lanes in WIDTHS for order in ((0, 1, 2, 3) if v in (0, 2) else (0,))]
+        return [(0, 256, 0, FULL), (0, 64, 3, FULL), (2, 64, 0, FULL), (2, 256, 3, FULL)] + capped
+    return [(v, lanes, order, FULL) for v in VARIANTS for lanes in WIDTHS for order in ((0, 1, 2, 3) if v in (0, 2) else (0,))] + capped
 
 
 def _check_all_shapes(s, want, what, dims, cap=None):
     m = H.HostMap(s)
-    for v, lanes, order in _runs(dims):
-        res, (sweeps, batches) = H.run_many([m], v, lanes, order, cap)
+    for v, lanes, order, blocks in _runs(dims):
+        res, (sweeps, batches) = H.run_many([m], v, lanes, order, cap, relax_blocks=blocks)
         recs, filled, n = res[0]
-        tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}"
+        tag = f"{what} variant {H.variants()[v]} lanes {lanes} order {order}" + (f" relax_blocks {blocks}" if blocks != FULL else "")
         k = len(want[0]) if cap is None else min(cap, len(want[0]))
         assert n == len(want[0]), f"{tag}: {n} basins counted, expected {len(want[0])}"
         R.assert_same_spill((recs, filled), (want[0][:k], want[1]), tag)
@@ -148,7 +155,7 @@ def test_cap_smaller_equal_and_larger_than_the_count_and_a_short_struct():
     nb = np.zeros(1, np.uint32)
     sw, ba = C.c_uint32(), C.c_uint32()
     hs = (C.c_void_p * 1)(m.h)
-    assert H.lib().sh_spill(hs, 1, 0, 256, 0, n, capi.ptr(short), 16, capi.ptr(nb), None, C.byref(sw), C.byref(ba)) == 0
+    assert H.lib().sh_spill(hs, 1, 0, 256, 0, H.RELAX_BLOCKS, n, capi.ptr(short), 16, capi.ptr(nb), None, C.byref(sw), C.byref(ba)) == 0
     assert int(nb[0]) == n and (short[4 * n:] == 0xFFFFFFFF).all()
     for k, r in enumerate(want[0]):
         assert [int(v) for v in short[4 * k:4 * k + 4]] == [r["first_cell"], r["pour_cell"], r["pour_to"], r["to_basin"]]

@@ -7,7 +7,9 @@
 // bodies without a barrier (the sweeps, the exit, the link, the two walks) run lane by lane, so the order decides how far a level or
 // a hop count travels in one sweep and which lane finishes a walk -- and must not decide any result. The host loops around the
 // sweeps are the library's. The planes are shared as the library shares them: the boundary marks and the pending words are one plane,
-// the boundary list and the area another. tests/analysis_host_lib.py builds and binds this file; the product never loads it.
+// the boundary list and the area another. The relax sweeps, the hop sweeps and the exit have min(a lane per cell, relax_blocks)
+// workgroups, as the library caps their launches: the workgroups stride over the rest of the boundary list.
+// tests/analysis_host_lib.py builds and binds this file; the product never loads it.
 #include "../drainage_host/drainage_host.cpp"
 #include "../../soilmachine_amd/csrc/soil_through.h"
 
@@ -19,7 +21,7 @@ struct ThroughOut {
 };
 
 template <int TX, int TY, int PS, int SLOTS>
-static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descending, int lanes_descending, bool want_area, bool want_outlets, size_t words,
+static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descending, int lanes_descending, uint32_t relax_blocks, bool want_area, bool want_outlets, size_t words,
                        ThroughOut& o, uint32_t* nbasins) {
   static double hs[(TX + 2) * (TY + 2)];             // (the "LDS")
   static uint32_t ls[(TX + 2) * (TY + 2)];
@@ -43,6 +45,7 @@ static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descendi
   DrainHostGroup g{lanes};
   const uint32_t* T = p.T.data();
   auto flat_blocks = [&](const LakeMember& m) { return (uint32_t)(((uint64_t)m.dimx * m.dimy + lanes - 1) / lanes); };
+  auto relax_groups = [&](const LakeMember& m) { return std::min<uint32_t>(flat_blocks(m), relax_blocks); };   // (the library's cap: the rest is strided)
   auto basin_blocks = [&](const LakeMember& m) { return (m.cap + lanes - 1) / lanes; };
   // a body with a barrier: the workgroup's lanes looped inside it
   auto groups = [&](auto&& blocks, auto&& body) {
@@ -86,7 +89,7 @@ static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descendi
       uint32_t changed[SPILL_BATCH];
       for (uint32_t j = 0; j < SPILL_BATCH; j++) {
         changed[j] = 0u;
-        each_lane(flat_blocks, [&](const LakeMember& m, DrainHostLane& one, uint32_t b, uint32_t nb) {   // (the device launches at most as many)
+        each_lane(relax_groups, [&](const LakeMember& m, DrainHostLane& one, uint32_t b, uint32_t nb) {
           if (what) through_hops_group(m, one, b, nb, T, p.B.data(), M.data(), Q.data(), H.data(), sacc, acc, changed + j);
           else spill_relax_group(m, one, b, nb, sweeps + j + 1u, T, p.B.data(), M.data(), Q.data(), H.data(), sacc, changed + j);
         });
@@ -95,7 +98,7 @@ static int run_through(std::vector<LakeMember> tab, uint32_t lanes, int descendi
       for (uint32_t j = 0; j < SPILL_BATCH; j++) done = done || changed[j] == 0u;
     }
   }
-  each_lane(flat_blocks, [&](const LakeMember& m, DrainHostLane& one, uint32_t b, uint32_t nb) {
+  each_lane(relax_groups, [&](const LakeMember& m, DrainHostLane& one, uint32_t b, uint32_t nb) {
     through_exit_group(m, one, b, nb, T, p.B.data(), M.data(), Q.data(), H.data(), sacc, acc);
   });
   uint32_t* P = M.data();    // the marks and the list are done with: the pending words and the area take their planes
@@ -132,17 +135,18 @@ uint32_t th_batch() { return SPILL_BATCH; }
 // The through-drainage of maps[0..nm) in one go, as smx_ensemble_through runs it (nm == 1: smx_through). out: nm * cap records of
 // struct_size bytes (the prefix of each 64-byte record, as the library cuts it), map i's from record i * cap; nbasins: one count per
 // map; through_area / outlets: the planes of all maps, one after the other (NULL = skip); sweeps[3]: level sweeps, hop sweeps,
-// batches. lanes and order as dh_drainage. 0, -2 for a bad argument, -1 where the sweeps did not settle within the bound.
-int th_through(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t cap, void* out, uint64_t struct_size, uint32_t* nbasins,
-               uint32_t* through_area, uint32_t* outlets, uint32_t* sweeps) {
-  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || !nbasins || !sweeps || (!out && cap)) return -2;
+// batches. lanes and order as dh_drainage; relax_blocks: the workgroups of a relax sweep, a hop sweep and the exit at most (>= 1). 0,
+// -2 for a bad argument, -1 where the sweeps did not settle within the bound.
+int th_through(dh_map* const* maps, uint32_t nm, int variant, uint32_t lanes, int order, uint32_t relax_blocks, uint32_t cap, void* out, uint64_t struct_size,
+               uint32_t* nbasins, uint32_t* through_area, uint32_t* outlets, uint32_t* sweeps) {
+  if (nm == 0 || struct_size == 0 || !lanes_ok(lanes) || relax_blocks == 0 || !nbasins || !sweeps || (!out && cap)) return -2;
   Members pl = plan_members(maps, nm, cap, CAP_NONE);
   ThroughOut o;
   const int desc = order & 1, ldesc = (order >> 1) & 1;
   int rc = 0;
   if (!with_shape<PASS_SHAPES>(variant, [&](auto s) {
         using S = decltype(s);
-        rc = run_through<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, through_area != nullptr, outlets != nullptr, (size_t)pl.words, o, nbasins);
+        rc = run_through<S::TX, S::TY, S::PS, S::SLOTS>(pl.tab, lanes, desc, ldesc, relax_blocks, through_area != nullptr, outlets != nullptr, (size_t)pl.words, o, nbasins);
       })) return -2;
   if (rc) return rc;
   sweeps[0] = o.level_sweeps; sweeps[1] = o.hop_sweeps; sweeps[2] = o.batches;
