@@ -626,6 +626,66 @@ int smx_catchments(smx_ctx* ctx, const uint32_t* cells, uint32_t n, smx_catchmen
                    uint32_t nbins, double bin_height, uint32_t* gauge, uint32_t* straight, uint32_t* diagonal, double* drop);
 int smx_ensemble_catchments(smx_ensemble* e, const uint32_t* cells, uint32_t n, smx_catchment* out, uint64_t struct_size,
                             uint32_t* hist, uint32_t nbins, double bin_height);
+/* ---- horizons: what every cell sees when it looks UP along sixteen lattice directions -- the sky-view factor, cast shadows for a
+ *      list of suns, the shelter from a wind (Winstral's Sx is the horizon slope of the upwind direction within a reach) ----
+ * Cells, c = x*dimy + y and h(c) are those of smx_drainage: Layermap::height of the top record, so a lake's surface counts and an
+ * empty column is 0.0; the ordered image K is that of smx_spill. The DIRECTIONS d = 0..15 run counter-clockwise from +x:
+ *   (1,0) (2,1) (1,1) (1,2) (0,1) (-1,2) (-1,1) (-2,1) (-1,0) (-2,-1) (-1,-1) (-1,-2) (0,-1) (1,-2) (1,-1) (2,-1)
+ * and len(d) is 1.0, the f64 nearest sqrt 2 (0x3FF6A09E667F3BCD) or the f64 nearest sqrt 5 (0x4001E3779B97F4A8). A caller selects
+ * directions by a 16-bit mask; nd is its popcount, at least 1. The RAY of c = (x, y) in direction d is the cells c_k = (x + k ux,
+ * y + k uy), k = 1, 2, ..., while c_k lies in the map and k <= reach (reach 0: no limit). No cell is interpolated: a knight's-move ray
+ * visits only the lattice points on it. s_k = (h(c_k) - h(c)) / ((double)k * len(d)): one subtraction, one multiplication, one
+ * division, nothing contracted. The HORIZON STEP K_d(c) is the smallest k with the largest s_k among those with s_k > +0.0, by plain
+ * f64 > -- a NaN is never a horizon and a NaN cell has none --, 0 where no s_k > 0 exists; the HORIZON SLOPE S_d(c) is that s_k,
+ * +0.0 where there is none. The planes (NULL = skip; smx_horizons only), in cell order:
+ *   slope  f64, nd * cells: plane j belongs to the j-th selected direction in ascending d (indices are 64 bits wide)
+ *   step   u32, the same layout, K
+ *   sky    f64 per cell: the sum over the selected directions in ascending d, from 0.0, of 1.0 / (1.0 + S*S), then divided by
+ *          (double)nd -- the sky-view factor of a cell whose horizon in every direction stands for an equal sector; 1.0 on open ground
+ *   open   u32 per cell: bit d set where d is selected and K_d(c) == 0
+ *   lit    u32 per cell: the number of suns that light the cell
+ * A SUN has a lattice direction TOWARDS it, which has to be selected, and tangent = tan(elevation), finite and >= 0; it lights c
+ * unless S_d(c) > tangent. lit_cells[i] is the number of cells sun i lights. Every figure is a comparison, an exact integer, an
+ * order-free extreme or a fixed sequence of single f64 operations: a host restatement reproduces each bit. */
+enum { SMX_HORIZON_DIRECTIONS = 16, SMX_HORIZON_MAX_SUNS = 64 };
+typedef struct smx_sun {                  /* 16 bytes */
+  uint32_t direction;                    /* the lattice direction towards the sun, 0..15, a bit of the mask */
+  uint32_t reserved;
+  double   tangent;                      /* tan(elevation), finite and >= 0 */
+} smx_sun;
+typedef struct smx_horizon_record {       /* 64 bytes; one per selected direction, in ascending d */
+  uint32_t direction;                    /* d */
+  int16_t  ux, uy;                       /* its lattice step */
+  uint32_t bounded;                      /* the cells with K != 0: something stands above them in this direction */
+  uint32_t step_max;                     /* the largest K */
+  uint32_t step_max_cell;                /* the cell that has it, the smallest cell index among equals; 0xFFFFFFFF when bounded == 0 */
+  uint32_t reserved0;                    /* 0 */
+  uint64_t step_sum;                     /* the exact sum of K */
+  double   slope_max;                    /* the largest S by K (the ordered image), +0.0 when bounded == 0 */
+  uint32_t reserved[6];                  /* 0 */
+} smx_horizon_record;
+/* nd records are written per map, record j at byte j * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each
+ * record); there is no cap and no counting call. suns: nsuns (0 to 64) of them, lit_cells: nsuns counts per map. In the ensemble
+ * call ONE mask, reach and sun list serve every member; member i's records start at out + i * nd records and its counts at
+ * lit_cells + i * nsuns; an empty ensemble: 0, nothing written. Refused with -2, the error text naming the offender, before anything
+ * is launched or written: a null or a strip context, struct_size == 0, out NULL, a mask of 0 or with a bit above 15, nsuns > 64,
+ * nsuns > 0 with suns or lit_cells NULL, a sun outside the mask or with a tangent that is not finite and >= 0, lit asked for with
+ * nsuns == 0; a context without a device -3. Both calls run on the context's / the ensemble's stream (they see every tick queued
+ * before them), launch the same kernels whatever the map holds and however many members there are (one upload of the tables and the
+ * suns; k_horizon_heights: the f64 height plane and the maxima of its 8 x 8 and 64 x 64 tiles and of the map; k_horizon_scan, a
+ * lane per cell and selected direction, which asks the map's, the coarse and the fine maximum before it loads a height and steps
+ * past a tile that cannot hold the horizon -- the result is the plain walk's bit for bit --, and folds the records and the sun
+ * counts; with sky, open or lit k_horizon_sky over the slopes and steps of all directions; the RESULTS copied back), synchronise
+ * once and change no map, flag, counter or generator; the results and the scratch of the sibling analyses are not touched. No
+ * kernel waits for another lane or workgroup; no launch strides, so smx_set_analysis_launch has no family for them. The scratch --
+ * a double per cell and per tile; with a plane asked for also nd doubles and nd words per cell, a double for sky, a word each for
+ * open and lit -- is allocated at first use and kept; an allocation that fails returns < 0 and leaves the context / the ensemble
+ * usable. Maps of up to 65536 cells a side and 2^32 - 2 cells per call. */
+int smx_horizons(smx_ctx* ctx, uint32_t directions, uint32_t reach, smx_horizon_record* out, uint64_t struct_size,
+                 const smx_sun* suns, uint32_t nsuns, uint32_t* lit_cells,
+                 double* slope, uint32_t* step, double* sky, uint32_t* open, uint32_t* lit);
+int smx_ensemble_horizons(smx_ensemble* e, uint32_t directions, uint32_t reach, smx_horizon_record* out, uint64_t struct_size,
+                          const smx_sun* suns, uint32_t nsuns, uint32_t* lit_cells);
 /* ---- dispersed flow: the multiple-flow-direction (MFD) contributing area in fixed point, every cell's donors and receivers, and per
  *      basin what arrives at its terminal and what leaks over its divides ----
  * Cells, h(c), wet cells, lakes, the receiver R(c), sinks, basins, first_cell and the rank are those of smx_drainage.

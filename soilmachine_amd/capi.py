@@ -174,6 +174,20 @@ class Catchment(C.Structure):
         return d
 
 
+class Horizon(C.Structure):
+    """smx_horizon_record: one selected direction's record of smx_horizons / smx_ensemble_horizons (64 bytes)."""
+    _fields_ = [("direction", C.c_uint32), ("ux", C.c_int16), ("uy", C.c_int16), ("bounded", C.c_uint32), ("step_max", C.c_uint32),
+                ("step_max_cell", C.c_uint32), ("reserved0", C.c_uint32), ("step_sum", C.c_uint64), ("slope_max", C.c_double), ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
+
+
+class Sun(C.Structure):
+    """smx_sun: a sun of smx_horizons / smx_ensemble_horizons (16 bytes): the lattice direction towards it and tan(elevation)."""
+    _fields_ = [("direction", C.c_uint32), ("reserved", C.c_uint32), ("tangent", C.c_double)]
+
+
 class Dispersal(C.Structure):
     """smx_dispersal_record: one basin's record of smx_dispersal / smx_ensemble_dispersal (64 bytes)."""
     _fields_ = [("first_cell", C.c_uint32), ("cells", C.c_uint32), ("flags", C.c_uint32), ("peak_cell", C.c_uint32),
@@ -255,6 +269,10 @@ PATH_TERMINAL_WET = 1                  # smx_flowpath.flags
 CATCH_NONE = 0xFFFFFFFF                # the gauge plane: the entry is no gauge; smx_catchment.downstream: no gauge down the flow
 CATCH_DROP_UNRELIABLE, CATCH_WET, CATCH_SINK = 1, 2, 4                 # smx_catchment.flags
 CATCHMENT_MAX_BINS = 64                # SMX_CATCHMENT_MAX_BINS
+HORIZON_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), (-2, 1),
+                      (-1, 0), (-2, -1), (-1, -1), (-1, -2), (0, -1), (1, -2), (1, -1), (2, -1))   # (ux, uy) of direction d, counter-clockwise from +x
+HORIZON_MAX_SUNS = 64                  # SMX_HORIZON_MAX_SUNS
+HORIZON_NONE = 0xFFFFFFFF              # smx_horizon_record.step_max_cell: no bounded cell
 DISPERSAL_ONE = 1 << 24               # one cell of dispersed area (the area plane, the *_q24 fields)
 DISPERSAL_MAX_EXPONENT = 16
 
@@ -284,6 +302,7 @@ SYMBOLS = [
     "smx_hillslopes", "smx_ensemble_hillslopes",
     "smx_flowpaths", "smx_ensemble_flowpaths",
     "smx_catchments", "smx_ensemble_catchments",
+    "smx_horizons", "smx_ensemble_horizons",
     "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_budget", "smx_ensemble_budget",
@@ -431,6 +450,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_flowpaths.argtypes = [vp, vp, u64, u32, vp]
     L.smx_catchments.argtypes = [vp, vp, u32, vp, u64, vp, u32, dbl, vp, vp, vp, vp]
     L.smx_ensemble_catchments.argtypes = [vp, vp, u32, vp, u64, vp, u32, dbl]
+    L.smx_horizons.argtypes = [vp, u32, u32, vp, u64, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.smx_ensemble_horizons.argtypes = [vp, u32, u32, vp, u64, vp, u32, vp]
     L.smx_dispersal.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
     L.smx_ensemble_dispersal.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_get_dispersal_rounds.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
@@ -475,3 +496,50 @@ def switches() -> dict:
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- the horizons' small helpers (pure Python: no device, no library)
+def horizon_mask(directions) -> int:
+    """The 16-bit mask of ``directions``: a mask already, or an iterable of indices 0..15 or of (ux, uy) pairs of HORIZON_DIRECTIONS."""
+    if isinstance(directions, (int, np.integer)):
+        return int(directions)
+    mask = 0
+    for d in directions:
+        if not isinstance(d, (int, np.integer)):
+            pair = (int(d[0]), int(d[1]))
+            if pair not in HORIZON_DIRECTIONS:
+                raise ValueError(f"{pair} is no lattice direction (the sixteen of capi.HORIZON_DIRECTIONS)")
+            d = HORIZON_DIRECTIONS.index(pair)
+        if not 0 <= int(d) < 16:
+            raise ValueError(f"direction {d} is outside 0..15")
+        mask |= 1 << int(d)
+    return mask
+
+
+def horizon_direction(azimuth: float, elevation: float) -> tuple:
+    """(d, tangent) of a sun or a wind at ``azimuth`` and ``elevation``, both in degrees: the lattice direction whose own azimuth
+    atan2(uy, ux) is nearest (of two equally near the smaller d) and tan(elevation). The azimuth is counted from +x towards +y."""
+    if not 0.0 <= elevation < 90.0:
+        raise ValueError(f"elevation {elevation} is outside [0, 90) degrees")
+    a = math.radians(azimuth)
+
+    def off(d):
+        ux, uy = HORIZON_DIRECTIONS[d]
+        return abs(math.remainder(math.atan2(uy, ux) - a, 2.0 * math.pi))
+
+    return min(range(16), key=lambda d: (off(d), d)), math.tan(math.radians(elevation))
+
+
+def horizon_suns(positions):
+    """A ctypes array of Sun from (azimuth, elevation) pairs in degrees (horizon_direction), as ``suns=`` of ``horizons`` takes it;
+    an entry that is a Sun already, or a (d, tangent) pair with an integer d, is taken as it is."""
+    out = (Sun * max(1, len(positions)))()
+    for i, p in enumerate(positions):
+        if isinstance(p, Sun):
+            d, t = p.direction, p.tangent
+        elif isinstance(p[0], (int, np.integer)):
+            d, t = int(p[0]), float(p[1])
+        else:
+            d, t = horizon_direction(float(p[0]), float(p[1]))
+        out[i].direction, out[i].reserved, out[i].tangent = d, 0, t
+    return out

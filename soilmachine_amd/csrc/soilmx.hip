@@ -56,6 +56,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_hills.h"
 #include "soil_paths.h"
 #include "soil_catch.h"
+#include "soil_horizon.h"
 #include "soil_disp.h"
 #include "soil_strata.h"
 #include "soil_budget.h"
@@ -593,6 +594,42 @@ __global__ void __launch_bounds__(LAKE_LANES) k_catch_hist(const LakeMember* __r
   if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   catch_hist_group<LAKE_SLOTS>(m, g, blockIdx.x, t, p.M, p.s.J, hist, nbins, bin_height);
+}
+
+// ---------------- the horizons (smx_horizons / smx_ensemble_horizons; bodies: soil_horizon.h) ----------------
+// On planes of their own: no drainage chain in front. k_horizon_heights takes a workgroup per coarse tile (64 x 64 cells, a wavefront
+// on 64 consecutive records of a column; 520 bytes of LDS), k_horizon_scan a workgroup per 256 consecutive cells and selected
+// direction (blockIdx.z; 288 bytes of LDS), k_horizon_sky a lane per cell. The table holds every member twice: tab[y] as everywhere,
+// tab[gridDim.y + y] the view of its tiles.
+struct HorizonPlanes {   // what the three kernels work on: the scan's view, the planes of all directions (null: not kept) and the fold's tables
+  double *H, *FM, *CM;
+  uint64_t* MM;
+  double* S; uint32_t* K;
+  HorizonAcc* acc; uint32_t* lit_cells;
+  const HorizonSun* suns; uint32_t nsuns;
+  uint64_t words;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_horizon_heights(const LakeMember* __restrict__ tab, HorizonPlanes p) {
+  __shared__ HorizonTileMax<HORIZON_FINE, HORIZON_COARSE> s;
+  const LakeMember m = tab[blockIdx.y], t = tab[gridDim.y + blockIdx.y];
+  if (blockIdx.x >= horizon_tiles(m, HORIZON_COARSE)) return;
+  ObsGroup g;
+  horizon_heights_group<HORIZON_FINE, HORIZON_COARSE>(m, t, g, blockIdx.x, s, p.H, p.FM, p.CM, p.MM);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_horizon_scan(const LakeMember* __restrict__ tab, HorizonPlanes p, uint32_t mask, uint32_t reach) {
+  __shared__ HorizonFold f;
+  const LakeMember m = tab[blockIdx.y], t = tab[gridDim.y + blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  const HorizonView v{p.H, p.FM, p.CM, p.MM};
+  horizon_scan_group<HORIZON_FINE, HORIZON_COARSE>(m, t, g, blockIdx.x, f, v, horizon_nth(mask, blockIdx.z), blockIdx.z, reach, p.suns, p.nsuns, p.words, p.S, p.K, p.acc,
+                                                   p.lit_cells);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_horizon_sky(const LakeMember* __restrict__ tab, HorizonPlanes p, uint32_t mask, double* sky, uint32_t* open, uint32_t* lit) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  horizon_sky_group(m, g, blockIdx.x, mask, p.suns, p.nsuns, p.words, p.S, p.K, sky, open, lit);
 }
 
 // ---------------- dispersed flow (smx_dispersal / smx_ensemble_dispersal; bodies: soil_disp.h) ----------------
@@ -2233,6 +2270,7 @@ struct smx_ctx : EventTimer {
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths: one each
   AnalysisScratch disp;                                                  // smx_dispersal
   AnalysisScratch catchments;                                            // smx_catchments
+  AnalysisScratch horizons;                                              // smx_horizons
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
   BudgetScratch budget;               // smx_budget of this context against a base
   AnalysisLaunch launch;              // smx_set_analysis_launch
@@ -3817,6 +3855,7 @@ struct smx_ensemble : EventTimer {
   AnalysisScratch lakes, drain, streams, spill, through, hills, paths;   // smx_ensemble_lakes, _drainage, _streams, _spill, _through, _hillslopes, _flowpaths: one each
   AnalysisScratch disp;                                                  // smx_ensemble_dispersal
   AnalysisScratch catchments;                                            // smx_ensemble_catchments
+  AnalysisScratch horizons;                                              // smx_ensemble_horizons
   StrataScratch strata;                   // smx_ensemble_soil_totals
   BudgetScratch budget;                   // smx_ensemble_budget
   AnalysisLaunch launch;                  // smx_ensemble_set_analysis_launch
@@ -4278,8 +4317,9 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 }  // extern "C"
 
 // ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes, the flow paths ----------------
-// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths, smx_catchments and their smx_ensemble_*
-// twins; kernels: soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h, soil_catch.h)
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths, smx_catchments, smx_horizons and their
+// smx_ensemble_* twins; kernels: soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h,
+// soil_catch.h, soil_horizon.h)
 // One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
 // cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
 // stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
@@ -4899,6 +4939,87 @@ static int catch_run(const AnalysisCall& c, AnalysisScratch& k, const uint32_t* 
   return 0;
 }
 
+// ---- the horizons: no chain and no u32 plane of the common kind. Everything that is a double lives in the f64 plane, one stretch
+// behind the other: the heights H (a double per cell), the fine and the coarse maxima of every member, the members' maxima MM (ordered
+// images, zeroed), and only where asked for the sky plane and the slopes of all directions (nd doubles per cell). The u32 planes --
+// the steps of all directions, open, lit -- are carved from the temporary storage, which no scan needs here; a records-only call keeps
+// neither slopes nor steps. The members go into the tables twice: as everywhere with cap = nd and rec0 = i * nd, and the view of
+// their tiles (soil_horizon.h). The region holds the suns (uploaded with the tables), the records and the sun counts (zeroed: the
+// fold's identities); k_horizon_heights, k_horizon_scan with a z per direction, k_horizon_sky where sky, open or lit is asked for;
+// the records, the counts and the planes asked for copied back, one synchronisation.
+static_assert(sizeof(smx_horizon_record) == 64 && sizeof(HorizonRec) == sizeof(smx_horizon_record) && offsetof(smx_horizon_record, ux) == offsetof(HorizonRec, ux) &&
+              offsetof(smx_horizon_record, bounded) == offsetof(HorizonRec, bounded) && offsetof(smx_horizon_record, step_max_cell) == offsetof(HorizonRec, step_max_cell) &&
+              offsetof(smx_horizon_record, step_sum) == offsetof(HorizonRec, step_sum) && offsetof(smx_horizon_record, slope_max) == offsetof(HorizonRec, slope_max) &&
+              sizeof(smx_sun) == sizeof(HorizonSun) && offsetof(smx_sun, tangent) == offsetof(HorizonSun, tangent) && (uint32_t)SMX_HORIZON_MAX_SUNS == HORIZON_MAX_SUNS &&
+              (uint32_t)SMX_HORIZON_DIRECTIONS == HORIZON_DIRS,
+              "smx_horizon_record / smx_sun layout");
+static int horizons_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t mask, uint32_t reach, smx_horizon_record* out, uint64_t struct_size, const smx_sun* suns,
+                        uint32_t nsuns, uint32_t* lit_cells, double* slope, uint32_t* step, double* sky, uint32_t* open, uint32_t* lit) {
+  const uint32_t nd = horizon_count(mask);
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, nd, CAP_CELLS, pl)) return rc;
+  std::vector<LakeMember> tiles(pl.tab);
+  uint64_t nfine = 0, ncoarse = 0;
+  unsigned most = 1;
+  for (uint32_t i = 0; i < c.nm; i++) {   // (a fine tile holds a cell at least: no more tiles than cells, the offsets fit)
+    pl.tab[i].cap = nd; pl.tab[i].rec0 = i * nd;
+    tiles[i].off = (uint32_t)nfine; tiles[i].rec0 = (uint32_t)ncoarse; tiles[i].cap = i;
+    nfine += horizon_tiles(pl.tab[i], HORIZON_FINE);
+    const uint32_t nc = horizon_tiles(pl.tab[i], HORIZON_COARSE);
+    ncoarse += nc; most = std::max<unsigned>(most, nc);
+  }
+  pl.nrec = (uint64_t)c.nm * nd;
+  const bool folded = sky || open || lit, kept = slope || step || folded;
+  const size_t W = (size_t)pl.words;
+  const size_t fm_at = W, cm_at = fm_at + (size_t)nfine, mm_at = cm_at + (size_t)ncoarse, sky_at = mm_at + c.nm, s_at = sky_at + (sky ? W : 0);
+  const size_t open_at = kept ? (size_t)nd * W : 0, lit_at = open_at + (open ? W : 0);
+  const size_t rec_at = ((size_t)nsuns * sizeof(HorizonSun) + 63) & ~(size_t)63, cnt_at = rec_at + (size_t)pl.nrec * sizeof(HorizonAcc);
+  AnalysisScratch::Need need;
+  need.words = s_at + (kept ? (size_t)nd * W : 0); need.planes = 0; need.f64 = true; need.members = c.nm;
+  need.temp_bytes = (lit_at + (lit ? W : 0)) * 4;
+  need.res_bytes = cnt_at + (size_t)c.nm * nsuns * 4;
+  if (int rc = analysis_reserve(c, k, need, "horizon", pl.nrec)) return rc;
+  uint32_t* const U = static_cast<uint32_t*>(k.temp);
+  HorizonPlanes p;
+  p.H = k.h64; p.FM = k.h64 + fm_at; p.CM = k.h64 + cm_at; p.MM = reinterpret_cast<uint64_t*>(k.h64 + mm_at);
+  p.S = kept ? k.h64 + s_at : nullptr; p.K = kept ? U : nullptr;
+  p.acc = reinterpret_cast<HorizonAcc*>(k.d_res + rec_at); p.lit_cells = reinterpret_cast<uint32_t*>(k.d_res + cnt_at);
+  p.suns = reinterpret_cast<const HorizonSun*>(k.d_res); p.nsuns = nsuns; p.words = pl.words;
+  double* const d_sky = sky ? k.h64 + sky_at : nullptr;
+  uint32_t* const d_open = open ? U + open_at : nullptr;
+  uint32_t* const d_lit = lit ? U + lit_at : nullptr;
+  if (nsuns) memcpy(k.h_res, suns, (size_t)nsuns * sizeof(HorizonSun));
+  put_table(k, pl, 0, false);
+  memcpy(k.h_tab + c.nm, tiles.data(), (size_t)c.nm * sizeof(LakeMember));
+  bool ok = send_tables(c, k, 0, 2);
+  ok = ok && (!nsuns || hipMemcpyAsync(k.d_res, k.h_res, (size_t)nsuns * sizeof(HorizonSun), hipMemcpyHostToDevice, c.st) == hipSuccess);
+  ok = ok && hipMemsetAsync(k.d_res + rec_at, 0, need.res_bytes - rec_at, c.st) == hipSuccess;
+  ok = ok && hipMemsetAsync(p.MM, 0, (size_t)c.nm * 8, c.st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_horizon_heights, dim3(most, c.nm), pl.wg, 0, c.st, k.d_tab, p);
+    hipLaunchKernelGGL(k_horizon_scan, dim3(pl.gf.x, c.nm, nd), pl.wg, 0, c.st, k.d_tab, p, mask, reach);
+    if (folded) hipLaunchKernelGGL(k_horizon_sky, pl.gf, pl.wg, 0, c.st, k.d_tab, p, mask, d_sky, d_open, d_lit);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res + rec_at, k.d_res + rec_at, need.res_bytes - rec_at);
+  // (smx_horizons only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, slope, p.S, (size_t)nd * W * 8);
+  ok = copy_back(c, ok, step, p.K, (size_t)nd * W * 4);
+  ok = copy_back(c, ok, sky, d_sky, W * 8);
+  ok = copy_back(c, ok, open, d_open, W * 4);
+  ok = copy_back(c, ok, lit, d_lit, W * 4);
+  if (analysis_wait(c, ok, "the horizons")) return -1;
+  const HorizonAcc* a = reinterpret_cast<const HorizonAcc*>(k.h_res + rec_at);
+  const size_t take = struct_size < sizeof(HorizonRec) ? (size_t)struct_size : sizeof(HorizonRec);
+  for (size_t r = 0; r < (size_t)pl.nrec; r++) {
+    HorizonRec rec;
+    horizon_finish(a[r], horizon_nth(mask, (uint32_t)(r % nd)), rec);
+    memcpy(reinterpret_cast<char*>(out) + r * (size_t)struct_size, &rec, take);
+  }
+  if (nsuns) memcpy(lit_cells, k.h_res + cnt_at, (size_t)c.nm * nsuns * 4);
+  return 0;
+}
+
 // ---- dispersed flow: planes T, B, R of the chain, P, RC, the list plane Q, and the 64-bit plane AQ in the f64 plane's place. The
 // drainage chain with its statistics and ITS records (first_cell, cells and flags of a dispersal record are the basin's), then
 // k_disp_pending. k_disp_flow in the round loop: DISP_BATCH launches, then ONE word back -- a bit per launch that found cells in
@@ -5156,6 +5277,48 @@ int smx_ensemble_catchments(smx_ensemble* e, const uint32_t* cells, uint32_t n, 
   roctx_range rr("soilmx:ensemble_catchments");
   HIPCHK(e, hipSetDevice(e->device));
   return catch_run(c, e->catchments, cells, n, out, struct_size, hist, nbins, bin_height, nullptr, nullptr, nullptr, nullptr);
+}
+// the checks of the two horizon calls beside analysis_begin's: the mask, the records' room, the suns. Nothing is launched and nothing
+// written before all of them hold. They need no device: a context asks them first, so that a context without one still names the offender.
+static bool horizon_args_ok(const AnalysisCall& c, uint32_t mask, const void* out, const smx_sun* suns, uint32_t nsuns, const uint32_t* lit_cells, const uint32_t* lit, int& rc) {
+  auto no = [&](const std::string& why) { c.err = std::string(c.who) + ": " + why; rc = -2; return false; };
+  if (!out) return no("out is null (a record per selected direction and map)");
+  if (mask == 0u) return no("directions is 0 (a mask of at least one of the 16 lattice directions)");
+  if (mask >> HORIZON_DIRS) return no("directions is " + std::to_string(mask) + ": a bit above 15 is set (16 lattice directions)");
+  if (nsuns > HORIZON_MAX_SUNS) return no("nsuns is " + std::to_string(nsuns) + " (0 to " + std::to_string(HORIZON_MAX_SUNS) + ")");
+  if (nsuns && !suns) return no("suns is null while nsuns is " + std::to_string(nsuns));
+  if (nsuns && !lit_cells) return no("lit_cells is null while nsuns is " + std::to_string(nsuns) + " (a count per sun and map)");
+  if (lit && !nsuns) return no("lit is asked for while nsuns is 0");
+  for (uint32_t i = 0; i < nsuns; i++) {
+    if (suns[i].direction >= HORIZON_DIRS || !((mask >> suns[i].direction) & 1u))
+      return no("suns[" + std::to_string(i) + "].direction is " + std::to_string(suns[i].direction) + ", not a direction of the mask " + std::to_string(mask));
+    if (!(suns[i].tangent >= 0.0 && std::isfinite(suns[i].tangent)))
+      return no("suns[" + std::to_string(i) + "].tangent is " + std::to_string(suns[i].tangent) + " (finite and not negative: the tangent of the sun's elevation)");
+  }
+  return true;
+}
+int smx_horizons(smx_ctx* ctx, uint32_t directions, uint32_t reach, smx_horizon_record* out, uint64_t struct_size, const smx_sun* suns, uint32_t nsuns,
+                 uint32_t* lit_cells, double* slope, uint32_t* step, double* sky, uint32_t* open, uint32_t* lit) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_horizons", ctx);
+  int rc;
+  if (c.partial || struct_size == 0) { analysis_begin(c, "smx_horizon_record", "lit_cells", struct_size, nullptr, &rc, nullptr, 0u, rc); return rc; }
+  if (!horizon_args_ok(c, directions, out, suns, nsuns, lit_cells, lit, rc)) return rc;
+  if (!analysis_begin(c, "smx_horizon_record", "lit_cells", struct_size, nullptr, &rc, nullptr, 0u, rc)) return rc;   // (no counts and no cap: nd records a map)
+  roctx_range rr("soilmx:horizons");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return horizons_run(c, ctx->horizons, directions, reach, out, struct_size, suns, nsuns, lit_cells, slope, step, sky, open, lit);
+}
+int smx_ensemble_horizons(smx_ensemble* e, uint32_t directions, uint32_t reach, smx_horizon_record* out, uint64_t struct_size, const smx_sun* suns, uint32_t nsuns,
+                          uint32_t* lit_cells) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_horizons", e);
+  int rc;
+  if (!analysis_begin(c, "smx_horizon_record", "lit_cells", struct_size, nullptr, &rc, nullptr, 0u, rc)) return rc;   // (an empty ensemble: 0 before anything is looked at)
+  if (!horizon_args_ok(c, directions, out, suns, nsuns, lit_cells, nullptr, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_horizons");
+  HIPCHK(e, hipSetDevice(e->device));
+  return horizons_run(c, e->horizons, directions, reach, out, struct_size, suns, nsuns, lit_cells, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 int smx_dispersal(smx_ctx* ctx, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint64_t* area, uint32_t* donors,
                   uint32_t* receivers) {

@@ -320,6 +320,26 @@ class Ensemble:
                 r["hist"] = hist[i, k].copy()
         return res
 
+    def horizons(self, directions=0xFFFF, reach: int = 0, suns=None) -> list:
+        """The horizon records of every member (``smx_ensemble_horizons``: the same launches whatever the member count): one list of
+        dicts per member, in member order, each as ``Layermap.horizons(directions, reach, suns)`` gives it. ONE mask, reach and sun
+        list serve every member; members may differ in size."""
+        self._check_members()
+        nm = len(self.members)
+        mask = capi.horizon_mask(directions)
+        ds = [d for d in range(16) if mask >> d & 1]
+        nd = len(ds)
+        sl = capi.horizon_suns(list(suns)) if suns is not None and len(suns) else None
+        ns = len(suns) if sl is not None else 0
+        counts = np.zeros(max(1, nm * ns), np.uint32)
+        out = (capi.Horizon * max(1, nm * nd))()
+        self._chk(self.L.smx_ensemble_horizons(self.h, mask, int(reach), out, C.sizeof(capi.Horizon), sl, ns, capi.ptr(counts) if ns else None))
+        res = [[out[i * nd + j].as_dict() for j in range(nd)] for i in range(nm)]
+        for i, recs in enumerate(res):
+            for r in recs:
+                r["lit_cells"] = [int(counts[i * ns + k]) for k in range(ns) if sl[k].direction == r["direction"]]
+        return res
+
     def dispersal(self, exponent: int = 1, cap: int | None = None) -> list:
         """The dispersed-flow records of every member (``smx_ensemble_dispersal``: the same launches whatever the member count): one
         list of dicts per member, in member order, each as ``Layermap.dispersal(exponent)`` gives it, record k for basin k of

@@ -371,6 +371,46 @@ class Layermap:
         planes = {k: v.reshape(self.dimx, self.dimy) for k, v in got.items()}
         return (recs, planes) if planes else recs
 
+    def horizons(self, directions=0xFFFF, reach: int = 0, suns=None, slope: bool = False, step: bool = False, sky: bool = False, open: bool = False,
+                 lit: bool = False):
+        """What every cell sees when it looks up along the lattice directions (``smx_horizons``). ``directions``: a 16-bit mask, or
+        an iterable of indices 0..15 or of ``(ux, uy)`` pairs of ``capi.HORIZON_DIRECTIONS`` (counter-clockwise from +x); ``reach``:
+        the steps a ray is followed at most, 0 = to the map's edge; ``suns``: what ``capi.horizon_suns`` takes or gives -- (azimuth,
+        elevation) pairs in degrees, (d, tangent) pairs, at most 64, each towards a selected direction. One dict per selected
+        direction in ascending d -- ``direction``, ``ux``, ``uy``, ``bounded`` (the cells with something above them that way),
+        ``step_max`` / ``step_max_cell`` (the farthest horizon and the cell that has it), ``step_sum``, ``slope_max`` and
+        ``lit_cells``: the number of cells each sun of THIS direction lights, in the order of ``suns``. With a plane asked for the
+        result is ``(records, planes)``: ``slope`` (float64) and ``step`` (uint32) of shape (nd, dimx, dimy), plane j for the j-th
+        selected direction -- the horizon slope S, +0.0 on open ground, and the step K that has it, 0 there --; ``sky`` (float64,
+        the sky-view factor: the mean of 1 / (1 + S*S), 1.0 on open ground), ``open`` (uint32, bit d where nothing stands above the
+        cell in direction d) and ``lit`` (uint32, the number of suns that light the cell) of shape (dimx, dimy). One call; sees
+        every tick queued before it and changes nothing.
+
+        The shadow of a low sun in the south-west and the shelter from a wind out of the north (Winstral's Sx within 64 cells)::
+
+            d, tangent = capi.horizon_direction(azimuth=225.0, elevation=10.0)
+            recs, pl = m.horizons([d], suns=[(d, tangent)], lit=True)
+            shadow = pl["lit"] == 0
+            up, _ = capi.horizon_direction(90.0, 0.0)          # the direction the wind comes from
+            sx = m.horizons([up], reach=64, slope=True)[1]["slope"][0]
+        """
+        mask = capi.horizon_mask(directions)
+        ds = [d for d in range(16) if mask >> d & 1]
+        nd, n = max(1, len(ds)), self.dimx * self.dimy
+        sl = capi.horizon_suns(list(suns)) if suns is not None and len(suns) else None
+        ns = len(suns) if sl is not None else 0
+        counts = np.zeros(max(1, ns), np.uint32)
+        out = (capi.Horizon * nd)()
+        wanted = [("slope", slope, np.float64, nd * n), ("step", step, np.uint32, nd * n), ("sky", sky, np.float64, n), ("open", open, np.uint32, n), ("lit", lit, np.uint32, n)]
+        got = {k: np.zeros(size, dt) for k, want, dt, size in wanted if want}
+        self._chk(self.L.smx_horizons(self.h, mask, int(reach), out, C.sizeof(capi.Horizon), sl, ns, capi.ptr(counts) if ns else None,
+                                      *[capi.ptr(got.get(k)) for k, _, _, _ in wanted]))
+        recs = [out[j].as_dict() for j in range(len(ds))]
+        for r in recs:
+            r["lit_cells"] = [int(counts[i]) for i in range(ns) if sl[i].direction == r["direction"]]
+        planes = {k: v.reshape((len(ds), self.dimx, self.dimy) if k in ("slope", "step") else (self.dimx, self.dimy)) for k, v in got.items()}
+        return (recs, planes) if planes else recs
+
     def dispersal(self, exponent: int = 1, area: bool = False, donors: bool = False, receivers: bool = False, cap: int | None = None):
         """Dispersed flow (``smx_dispersal``): the multiple-flow-direction contributing area next to the D8 one of ``drainage()``. A
         dry cell splits its water over ALL lower neighbours in proportion to slope ** ``exponent`` (0 to 16; a diagonal step counts
