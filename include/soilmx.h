@@ -686,6 +686,56 @@ int smx_horizons(smx_ctx* ctx, uint32_t directions, uint32_t reach, smx_horizon_
                  double* slope, uint32_t* step, double* sky, uint32_t* open, uint32_t* lit);
 int smx_ensemble_horizons(smx_ensemble* e, uint32_t directions, uint32_t reach, smx_horizon_record* out, uint64_t struct_size,
                           const smx_sun* suns, uint32_t nsuns, uint32_t* lit_cells);
+/* ---- proximity: how far every cell is from water or from a listed cell as the crow flies (the exact Euclidean distance transform),
+ *      which lake or listed cell is nearest (allocation zones), and how much of every zone lies how far out (buffers) ----
+ * Cells, c = x*dimy + y, wet cells, lakes and lake ranks are those of smx_lakes. The SITES are a set of cells, each with a GROUP.
+ * LIST mode (cells != NULL, n >= 1): the sites are the n distinct listed cells, the group of site cells[i] is i; any cell may be
+ * listed, wet or dry. WATER mode (cells == NULL, n == 0): the sites are the wet cells and a site's group is the rank of its lake; a
+ * map without a wet cell has no site and no record.
+ * d2(c, s) = (xc - xs)^2 + (yc - ys)^2, an exact integer. nearest(c) is the site with the smallest (d2(c, s), s): the smaller squared
+ * distance, then the smaller site cell index; a site is its own nearest. dist2(c) = d2(c, nearest(c)) and group(c) =
+ * group(nearest(c)). Without any site all three are 0xFFFFFFFF for every cell. The ZONE of group g is the set of cells with
+ * group(c) == g, sites included. Buffers: r(c) is the integer with r^2 <= dist2(c) < (r+1)^2, and a cell of zone g counts in bin
+ * min(r / bin_width, nbins - 1) of row g, by integer division; every row sums to cells of its record. Every figure is an exact
+ * integer or an order-free extreme: a host restatement reproduces each bit. No floating point enters but the f64 square root that
+ * starts r, exact for an integer below 2^52 and corrected in integers. */
+enum { SMX_PROXIMITY_MAX_BINS = 64, SMX_PROXIMITY_MAX_SIDE = 32768 };
+typedef struct smx_proximity_record {     /* 64 bytes; record g belongs to group g */
+  uint32_t site;                         /* LIST: cells[g]; WATER: the lake's first_cell */
+  uint32_t sites;                        /* LIST: 1; WATER: the lake's cells */
+  uint32_t cells;                        /* the size of the zone, at least sites */
+  uint32_t dist2_max;                    /* the largest dist2 in the zone */
+  uint32_t farthest_cell;                /* the cell that has it, the smallest cell index among equals */
+  uint32_t flags;                        /* 1: the zone has a cell on the map border */
+  uint64_t dist2_sum;                    /* the exact sum of dist2 over the zone */
+  uint16_t x0, y0, x1, y1;               /* the zone's bounding box, inclusive */
+  uint32_t reserved[6];                  /* 0 */
+} smx_proximity_record;
+/* Record g is written at byte g * struct_size (a caller passes sizeof(ITS struct) and gets that prefix of each record). LIST mode
+ * writes n records per map: cap must be at least n, and *nrecords = n. WATER mode sets *nrecords to the number of lakes whatever cap
+ * is and writes the first min(cap, *nrecords) records in rank order; out may be NULL with cap == 0 (the counting call). nbins (0 to
+ * 64) > 0: hist row g holds nbins u32, for the records that are written; nbins == 0: hist and bin_width are not looked at and no
+ * histogram work is launched. The planes nearest, group and dist2 (NULL = skip; smx_proximity only) hold dimx*dimy u32 in cell
+ * order, for EVERY cell whatever cap is. In the ensemble call ONE list serves every member, as an index into each member's own
+ * plane; member i's records start at out + i * cap_per_member records, its rows at hist + i * cap_per_member * nbins, and there is
+ * one count per member; an empty ensemble: 0, nothing written. Refused with -2, the error text naming the offender, before anything
+ * is launched or written: a null or a strip context, struct_size == 0, nrecords NULL, cells NULL with n != 0 or cells given with
+ * n == 0, a cell outside a member, a cell listed twice, cap < n in LIST mode, records asked for (cap > 0) with out NULL, nbins > 64,
+ * nbins > 0 with hist NULL or bin_width == 0, cap * nbins >= 2^31, a member with a side above 32768 (that keeps dist2 below 2^31 and
+ * 0xFFFFFFFF free for "no site"); a context without a device -3. Both calls run on the context's / the ensemble's stream (they see
+ * every tick queued before them), launch the same kernels whatever the map holds and however many members there are (one upload of
+ * the tables and the list; WATER: the census's labelling and the rank scan; k_prox_mark; k_prox_columns, a workgroup per column;
+ * k_prox_envelope, a lane per row and band of columns, the one serial pass, of dimx / bands steps; k_prox_query, a lane per cell,
+ * which takes the nearest over the bands; with bins k_prox_hist; the
+ * RESULTS copied back), synchronise once and change no map, flag, counter or generator; the results and the scratch of the sibling
+ * analyses are not touched. No kernel waits for another lane or workgroup; no launch strides, so smx_set_analysis_launch has no
+ * family for them. The scratch -- eight u32 planes per cell, the records, the rows and the list -- is allocated at first use and
+ * kept; an allocation that fails returns < 0 and leaves the context / the ensemble usable. At most 2^32 - 2 cells per call. */
+int smx_proximity(smx_ctx* ctx, const uint32_t* cells, uint32_t n, smx_proximity_record* out, uint64_t struct_size, uint32_t cap,
+                  uint32_t* nrecords, uint32_t* hist, uint32_t nbins, uint32_t bin_width,
+                  uint32_t* nearest, uint32_t* group, uint32_t* dist2);
+int smx_ensemble_proximity(smx_ensemble* e, const uint32_t* cells, uint32_t n, smx_proximity_record* out, uint64_t struct_size,
+                           uint32_t cap_per_member, uint32_t* nrecords, uint32_t* hist, uint32_t nbins, uint32_t bin_width);
 /* ---- dispersed flow: the multiple-flow-direction (MFD) contributing area in fixed point, every cell's donors and receivers, and per
  *      basin what arrives at its terminal and what leaks over its divides ----
  * Cells, h(c), wet cells, lakes, the receiver R(c), sinks, basins, first_cell and the rank are those of smx_drainage.

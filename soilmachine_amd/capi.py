@@ -183,6 +183,16 @@ class Horizon(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("reserved")}
 
 
+class Proximity(C.Structure):
+    """smx_proximity_record: one group's record of smx_proximity / smx_ensemble_proximity (64 bytes)."""
+    _fields_ = [("site", C.c_uint32), ("sites", C.c_uint32), ("cells", C.c_uint32), ("dist2_max", C.c_uint32), ("farthest_cell", C.c_uint32),
+                ("flags", C.c_uint32), ("dist2_sum", C.c_uint64), ("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16), ("y1", C.c_uint16),
+                ("reserved", C.c_uint32 * 6)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Sun(C.Structure):
     """smx_sun: a sun of smx_horizons / smx_ensemble_horizons (16 bytes): the lattice direction towards it and tan(elevation)."""
     _fields_ = [("direction", C.c_uint32), ("reserved", C.c_uint32), ("tangent", C.c_double)]
@@ -273,6 +283,9 @@ HORIZON_DIRECTIONS = ((1, 0), (2, 1), (1, 1), (1, 2), (0, 1), (-1, 2), (-1, 1), 
                       (-1, 0), (-2, -1), (-1, -1), (-1, -2), (0, -1), (1, -2), (1, -1), (2, -1))   # (ux, uy) of direction d, counter-clockwise from +x
 HORIZON_MAX_SUNS = 64                  # SMX_HORIZON_MAX_SUNS
 HORIZON_NONE = 0xFFFFFFFF              # smx_horizon_record.step_max_cell: no bounded cell
+PROXIMITY_NONE = 0xFFFFFFFF            # the nearest, group and dist2 planes: the map has no site
+PROXIMITY_BORDER = 1                   # smx_proximity_record.flags
+PROXIMITY_MAX_BINS, PROXIMITY_MAX_SIDE = 64, 32768                     # SMX_PROXIMITY_MAX_BINS, SMX_PROXIMITY_MAX_SIDE
 DISPERSAL_ONE = 1 << 24               # one cell of dispersed area (the area plane, the *_q24 fields)
 DISPERSAL_MAX_EXPONENT = 16
 
@@ -303,6 +316,7 @@ SYMBOLS = [
     "smx_flowpaths", "smx_ensemble_flowpaths",
     "smx_catchments", "smx_ensemble_catchments",
     "smx_horizons", "smx_ensemble_horizons",
+    "smx_proximity", "smx_ensemble_proximity",
     "smx_dispersal", "smx_ensemble_dispersal", "smx_get_dispersal_rounds", "smx_ensemble_get_dispersal_rounds",
     "smx_soil_totals", "smx_ensemble_soil_totals", "smx_soil_thickness", "smx_cores",
     "smx_budget", "smx_ensemble_budget",
@@ -452,6 +466,8 @@ def load() -> C.CDLL:
     L.smx_ensemble_catchments.argtypes = [vp, vp, u32, vp, u64, vp, u32, dbl]
     L.smx_horizons.argtypes = [vp, u32, u32, vp, u64, vp, u32, vp, vp, vp, vp, vp, vp]
     L.smx_ensemble_horizons.argtypes = [vp, u32, u32, vp, u64, vp, u32, vp]
+    L.smx_proximity.argtypes = [vp, vp, u32, vp, u64, u32, vp, vp, u32, u32, vp, vp, vp]
+    L.smx_ensemble_proximity.argtypes = [vp, vp, u32, vp, u64, u32, vp, vp, u32, u32]
     L.smx_dispersal.argtypes = [vp, u32, vp, u64, u32, C.POINTER(u32), vp, vp, vp]
     L.smx_ensemble_dispersal.argtypes = [vp, u32, vp, u64, u32, vp]
     L.smx_get_dispersal_rounds.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
@@ -496,6 +512,20 @@ def switches() -> dict:
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def proximity_cells(cells, dimy: int):
+    """(list, n) as smx_proximity takes them: (None, 0) for ``cells`` None (the wet cells), else the flat uint32 indices of a
+    sequence of flat indices x*dimy + y or of (x, y) pairs."""
+    if cells is None:
+        return None, 0
+    cl = np.asarray(cells if isinstance(cells, np.ndarray) else list(cells), np.int64)
+    if cl.ndim == 2 and cl.shape[1] == 2:
+        cl = cl[:, 0] * int(dimy) + cl[:, 1]
+    cl = np.ascontiguousarray(cl.reshape(-1), np.uint32)
+    if not len(cl):
+        raise ValueError("proximity: cells is empty (None means the wet cells)")
+    return cl, len(cl)
 
 
 # ---- the horizons' small helpers (pure Python: no device, no library)

@@ -57,6 +57,7 @@ __device__ unsigned long long g_sect[32];                    // (experiment buil
 #include "soil_paths.h"
 #include "soil_catch.h"
 #include "soil_horizon.h"
+#include "soil_prox.h"
 #include "soil_disp.h"
 #include "soil_strata.h"
 #include "soil_budget.h"
@@ -630,6 +631,54 @@ __global__ void __launch_bounds__(LAKE_LANES) k_horizon_sky(const LakeMember* __
   if ((uint64_t)blockIdx.x * LAKE_LANES >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
   ObsGroup g;
   horizon_sky_group(m, g, blockIdx.x, mask, p.suns, p.nsuns, p.words, p.S, p.K, sky, open, lit);
+}
+
+// ---------------- proximity (smx_proximity / smx_ensemble_proximity; bodies: soil_prox.h) ----------------
+// On planes of their own; in WATER mode behind the census's labelling and the rank scan. k_prox_mark takes a lane per list entry or,
+// in WATER mode, per cell; k_prox_columns a workgroup per column (8 KB of LDS: the column's site mask); k_prox_envelope a lane per
+// row and band (PROX_BANDS bands of columns) in workgroups of ONE wavefront, so that the serial pass spreads over as many compute
+// units as the map has 64-row stretches times bands;
+// k_prox_query's table holds 512 cells' worth of groups (26 KB of LDS), k_prox_hist's 512 cells' worth of (group, bin) keys (4 KB).
+constexpr int PROX_ENV_LANES = 64;
+struct ProxPlanes {   // what the kernels work on (soil_prox.h): the marks, the rank scan (WATER) and later the depths, the columns' candidates, the envelopes
+  uint32_t *M, *BD, *P, *S, *T;
+};
+__global__ void __launch_bounds__(LAKE_LANES) k_prox_mark(const LakeMember* __restrict__ tab, ProxPlanes p, const uint32_t* __restrict__ list, uint32_t n, ProxAcc* acc,
+                                                          uint32_t* nlakes) {
+  const LakeMember m = tab[blockIdx.y];
+  const uint32_t nb = prox_mark_blocks(m, list != nullptr, n, LAKE_LANES);
+  if (blockIdx.x >= nb) return;
+  ObsGroup g;
+  prox_mark_group(m, g, blockIdx.x, nb, list, n, p.M, p.BD, acc, nlakes + blockIdx.y);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_prox_columns(const LakeMember* __restrict__ tab, ProxPlanes p) {
+  __shared__ ProxColumn s;
+  const LakeMember m = tab[blockIdx.y];
+  if (blockIdx.x >= (uint32_t)m.dimx) return;
+  ObsGroup g;
+  prox_columns_group(m, g, blockIdx.x, s, p.M, p.P);
+}
+__global__ void __launch_bounds__(PROX_ENV_LANES) k_prox_envelope(const LakeMember* __restrict__ tab, ProxPlanes p, uint32_t bands) {
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * PROX_ENV_LANES >= (uint64_t)m.dimy * prox_bands(m, bands)) return;
+  ObsGroup g;
+  prox_envelope_group(m, g, blockIdx.x, bands, p.P, p.S, p.T, p.BD);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_prox_query(const LakeMember* __restrict__ tab, ProxPlanes p, uint32_t bands, ProxAcc* acc, uint32_t* nearest, uint32_t* dist2,
+                                                           uint32_t* group) {
+  __shared__ ProxTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  prox_query_group<LAKE_SLOTS>(m, g, blockIdx.x, bands, t, p.M, p.P, p.S, p.T, p.BD, acc, nearest, dist2, group);
+}
+__global__ void __launch_bounds__(LAKE_LANES) k_prox_hist(const LakeMember* __restrict__ tab, const uint32_t* __restrict__ dist2, const uint32_t* __restrict__ group,
+                                                          uint32_t* hist, uint32_t nbins, uint32_t bin_width) {
+  __shared__ ProxHistTable<LAKE_SLOTS> t;
+  const LakeMember m = tab[blockIdx.y];
+  if ((uint64_t)blockIdx.x * lake_stats_cells(LAKE_SLOTS, LAKE_LANES) >= (uint64_t)m.dimx * (uint64_t)m.dimy) return;
+  ObsGroup g;
+  prox_hist_group<LAKE_SLOTS>(m, g, blockIdx.x, t, dist2, group, hist, nbins, bin_width);
 }
 
 // ---------------- dispersed flow (smx_dispersal / smx_ensemble_dispersal; bodies: soil_disp.h) ----------------
@@ -2271,6 +2320,7 @@ struct smx_ctx : EventTimer {
   AnalysisScratch disp;                                                  // smx_dispersal
   AnalysisScratch catchments;                                            // smx_catchments
   AnalysisScratch horizons;                                              // smx_horizons
+  AnalysisScratch proximity;                                             // smx_proximity
   StrataScratch strata;               // smx_soil_totals, smx_soil_thickness, smx_cores
   BudgetScratch budget;               // smx_budget of this context against a base
   AnalysisLaunch launch;              // smx_set_analysis_launch
@@ -3856,6 +3906,7 @@ struct smx_ensemble : EventTimer {
   AnalysisScratch disp;                                                  // smx_ensemble_dispersal
   AnalysisScratch catchments;                                            // smx_ensemble_catchments
   AnalysisScratch horizons;                                              // smx_ensemble_horizons
+  AnalysisScratch proximity;                                             // smx_ensemble_proximity
   StrataScratch strata;                   // smx_ensemble_soil_totals
   BudgetScratch budget;                   // smx_ensemble_budget
   AnalysisLaunch launch;                  // smx_ensemble_set_analysis_launch
@@ -4317,9 +4368,9 @@ int smx_ensemble_fork(smx_ensemble* e, smx_ctx* src, int32_t n, uint64_t pool_ca
 }  // extern "C"
 
 // ---------------- the terrain analyses: the lake census, drainage, the stream network, spill, through-drainage, the hillslopes, the flow paths ----------------
-// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths, smx_catchments, smx_horizons and their
-// smx_ensemble_* twins; kernels: soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h, soil_paths.h,
-// soil_catch.h, soil_horizon.h)
+// (smx_lakes, smx_drainage, smx_streams, smx_spill, smx_through, smx_hillslopes, smx_flowpaths, smx_catchments, smx_horizons, smx_proximity and
+// their smx_ensemble_* twins; kernels: soil_lakes.h, soil_drain.h, soil_streams.h, soil_spill.h, soil_through.h, soil_hills.h,
+// soil_paths.h, soil_catch.h, soil_horizon.h, soil_prox.h)
 // One path per analysis for a context and for an ensemble: the maps ms[0..nm) share the planes (member i at words [off_i, off_i +
 // cells_i)), one table upload, the same launches whatever the maps hold and however many there are. What the five have in common
 // stands once, here: the call and its argument checks, the member table, the growth of the scratch (AnalysisScratch, soil_scratch.h),
@@ -5020,6 +5071,79 @@ static int horizons_run(const AnalysisCall& c, AnalysisScratch& k, uint32_t mask
   return 0;
 }
 
+// ---- proximity: eight planes and no chain. M (0) the marks, BD (1) the rank scan in WATER mode and the envelopes' depths behind it,
+// P (2) the columns' candidates, S and T (3, 4) the envelopes of the PROX_BANDS bands, then nearest, dist2 and group (5, 6, 7), written only where a plane or
+// the histogram asks for them. LIST mode: the list goes into the result region with the tables' upload, M is filled and k_prox_mark
+// scatters the list into it for every member; WATER mode: the census's labelling through the bare table, the scan of the root marks
+// and k_prox_mark turning roots into ranks. Then k_prox_columns, k_prox_envelope, k_prox_query and, with bins, k_prox_hist on the
+// zeroed rows. The region holds the counts, the records, the rows and the list; all but the list copied back with the planes asked
+// for, one synchronisation.
+static_assert(sizeof(smx_proximity_record) == 64 && sizeof(ProxRec) == sizeof(smx_proximity_record) && offsetof(smx_proximity_record, dist2_max) == offsetof(ProxRec, dist2_max) &&
+              offsetof(smx_proximity_record, flags) == offsetof(ProxRec, flags) && offsetof(smx_proximity_record, dist2_sum) == offsetof(ProxRec, dist2_sum) &&
+              offsetof(smx_proximity_record, x0) == offsetof(ProxRec, x0) && offsetof(smx_proximity_record, reserved) == offsetof(ProxRec, reserved) &&
+              (uint32_t)SMX_PROXIMITY_MAX_BINS == PROX_MAX_BINS && (uint32_t)SMX_PROXIMITY_MAX_SIDE == PROX_MAX_SIDE, "smx_proximity_record layout");
+static int prox_run(const AnalysisCall& c, AnalysisScratch& k, const uint32_t* cells, uint32_t n, smx_proximity_record* out, uint64_t struct_size, uint32_t cap,
+                    uint32_t* nrecords, uint32_t* hist, uint32_t nbins, uint32_t bin_width, uint32_t* nearest, uint32_t* group, uint32_t* dist2) {
+  const bool list = cells != nullptr;
+  AnalysisPlan pl;
+  if (int rc = plan_members(c, list ? n : cap, list ? CAP_CELLS : CAP_BLOCKS, pl)) return rc;   // (LIST: n distinct cells inside every member: every member keeps n records)
+  unsigned columns = 1, rows = 1, marks = 1;
+  for (const LakeMember& m : pl.tab) {
+    columns = std::max(columns, (unsigned)m.dimx);
+    rows = std::max(rows, (unsigned)(((uint64_t)m.dimy * prox_bands(m, PROX_BANDS) + PROX_ENV_LANES - 1) / PROX_ENV_LANES));
+    marks = std::max(marks, (unsigned)prox_mark_blocks(m, list, n, LAKE_LANES));
+  }
+  AnalysisScratch::Need need;
+  const size_t rec_at = counts_pad(c.nm), hist_at = rec_at + (size_t)pl.nrec * sizeof(ProxAcc);
+  const size_t hist_bytes = (size_t)pl.nrec * nbins * 4, list_at = hist_at + ((hist_bytes + 63) & ~(size_t)63);
+  need.words = (size_t)pl.words; need.planes = 8; need.members = c.nm; need.res_bytes = list_at + (size_t)n * 4;
+  if (!list && !scan_bytes(c, lake_marks(nullptr), pl.words, need.temp_bytes)) return -1;
+  if (int rc = analysis_reserve(c, k, need, "proximity", pl.nrec)) return rc;
+  const ProxPlanes p{k.plane[0], k.plane[1], k.plane[2], k.plane[3], k.plane[4]};
+  uint32_t* const d_nearest = nearest ? k.plane[5] : nullptr;
+  uint32_t* const d_dist2 = dist2 || nbins ? k.plane[6] : nullptr;
+  uint32_t* const d_group = group || nbins ? k.plane[7] : nullptr;
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(k.d_res);
+  ProxAcc* acc = reinterpret_cast<ProxAcc*>(k.d_res + rec_at);
+  uint32_t* d_hist = reinterpret_cast<uint32_t*>(k.d_res + hist_at);
+  uint32_t* d_list = reinterpret_cast<uint32_t*>(k.d_res + list_at);
+  const LakeMember* bare = k.d_tab + c.nm;
+  if (list) memcpy(k.h_res + list_at, cells, (size_t)n * 4);
+  put_table(k, pl, 0, false); put_table(k, pl, 1, true);
+  bool ok = send_tables(c, k, 0, 2);
+  ok = ok && (!list || hipMemcpyAsync(d_list, k.h_res + list_at, (size_t)n * 4, hipMemcpyHostToDevice, c.st) == hipSuccess);
+  ok = ok && (!list || hipMemsetAsync(p.M, 0xFF, (size_t)pl.words * 4, c.st) == hipSuccess);
+  ok = ok && (!nbins || !hist_bytes || hipMemsetAsync(d_hist, 0, hist_bytes, c.st) == hipSuccess);
+  if (ok && !list) {
+    launch_lake_labels(pl, c.st, bare, p.M, nullptr);
+    ok = scan_words(k, lake_marks(p.M), p.BD, pl.words, c.st);
+  }
+  if (ok) {
+    hipLaunchKernelGGL(k_prox_mark, dim3(marks, c.nm), pl.wg, 0, c.st, k.d_tab, p, list ? d_list : nullptr, n, acc, d_n);
+    hipLaunchKernelGGL(k_prox_columns, dim3(columns, c.nm), pl.wg, 0, c.st, k.d_tab, p);
+    hipLaunchKernelGGL(k_prox_envelope, dim3(rows, c.nm), dim3(PROX_ENV_LANES), 0, c.st, k.d_tab, p, PROX_BANDS);
+    hipLaunchKernelGGL(k_prox_query, pl.gs, pl.wg, 0, c.st, k.d_tab, p, PROX_BANDS, acc, d_nearest, d_dist2, d_group);
+    if (nbins && hist_bytes) hipLaunchKernelGGL(k_prox_hist, pl.gs, pl.wg, 0, c.st, k.d_tab, d_dist2, d_group, d_hist, nbins, bin_width);
+  }
+  ok = ok && hipGetLastError() == hipSuccess;
+  ok = copy_back(c, ok, k.h_res, k.d_res, hist_at + hist_bytes);
+  // (smx_proximity only: one map, off = 0, so a plane index is a cell index)
+  ok = copy_back(c, ok, nearest, d_nearest, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, dist2, d_dist2, (size_t)pl.words * 4);
+  ok = copy_back(c, ok, group, d_group, (size_t)pl.words * 4);
+  if (analysis_wait(c, ok, "proximity")) return -1;
+  uint32_t* const counts = reinterpret_cast<uint32_t*>(k.h_res);
+  if (list) for (uint32_t i = 0; i < c.nm; i++) counts[i] = n;   // (LIST: a record per listed cell, no count comes back)
+  const ProxAcc* a = reinterpret_cast<const ProxAcc*>(k.h_res + rec_at);
+  const uint32_t* rows_back = reinterpret_cast<const uint32_t*>(k.h_res + hist_at);
+  for (uint32_t i = 0; nbins && i < c.nm; i++) {   // the rows of the records that are written
+    const uint32_t w = std::min(counts[i], std::min(pl.tab[i].cap, cap));
+    if (w) memcpy(hist + (size_t)i * cap * nbins, rows_back + (size_t)pl.tab[i].rec0 * nbins, (size_t)w * nbins * 4);
+  }
+  cut_records<ProxRec>(pl, counts, out, struct_size, cap, nrecords, [a](size_t j, ProxRec& rec) -> const ProxRec& { prox_finish(a[j], rec); return rec; });
+  return 0;
+}
+
 // ---- dispersed flow: planes T, B, R of the chain, P, RC, the list plane Q, and the 64-bit plane AQ in the f64 plane's place. The
 // drainage chain with its statistics and ITS records (first_cell, cells and flags of a dispersal record are the basin's), then
 // k_disp_pending. k_disp_flow in the round loop: DISP_BATCH launches, then ONE word back -- a bit per launch that found cells in
@@ -5319,6 +5443,84 @@ int smx_ensemble_horizons(smx_ensemble* e, uint32_t directions, uint32_t reach, 
   roctx_range rr("soilmx:ensemble_horizons");
   HIPCHK(e, hipSetDevice(e->device));
   return horizons_run(c, e->horizons, directions, reach, out, struct_size, suns, nsuns, lit_cells, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+// the checks of the two proximity calls beside analysis_begin's: the mode, the list, the records' room, the bins and the members'
+// sides. Nothing is launched and nothing written before all of them hold; they need no device. (The list is read last: a call
+// refused for its sizes never looks at it.)
+static bool prox_args_ok(const AnalysisCall& c, const uint32_t* cells, uint32_t n, const void* out, uint32_t cap, const uint32_t* nrecords, const uint32_t* hist, uint32_t nbins,
+                         uint32_t bin_width, int& rc) {
+  auto no = [&](const std::string& why) { c.err = std::string(c.who) + ": " + why; rc = -2; return false; };
+  if (!nrecords) return no("nrecords is null (one count per map)");
+  if (!cells && n) return no("cells is null while n is " + std::to_string(n) + " (a list, or null and 0 for the wet cells)");
+  if (cells && !n) return no("n is 0 while cells is given (at least one listed cell, or null and 0 for the wet cells)");
+  if (cells && cap < n) return no("cap is " + std::to_string(cap) + " while n is " + std::to_string(n) + " (a record per listed cell)");
+  if (!out && cap) return no("out is null while cap is " + std::to_string(cap) + " (out may be null for counting, with cap 0)");
+  if (nbins > PROX_MAX_BINS) return no("nbins is " + std::to_string(nbins) + " (0 to " + std::to_string(PROX_MAX_BINS) + ")");
+  if (nbins && !hist) return no("hist is null while nbins is " + std::to_string(nbins));
+  if (nbins && !bin_width) return no("bin_width is 0 while nbins is " + std::to_string(nbins) + " (at least 1)");
+  if ((uint64_t)cap * nbins >= (1ull << 31)) return no("cap * nbins is " + std::to_string((uint64_t)cap * nbins) + " (below 2^31)");
+  uint64_t least = ~0ull; uint32_t which = 0;
+  for (uint32_t i = 0; i < c.nm; i++) {
+    const smx_ctx* x = c.ms[i];
+    if ((uint32_t)x->cfg.dimx > PROX_MAX_SIDE || (uint32_t)x->cfg.dimy > PROX_MAX_SIDE)
+      return no((c.ensemble ? "member " + std::to_string(i) : std::string("the map")) + " is " + std::to_string(x->cfg.dimx) + " x " + std::to_string(x->cfg.dimy) +
+                " (at most " + std::to_string(PROX_MAX_SIDE) + " cells a side: dist2 stays below 2^31)");
+    if ((uint64_t)x->ncells < least) { least = x->ncells; which = i; }
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (cells[i] >= least)
+      return no("cells[" + std::to_string(i) + "] is " + std::to_string(cells[i]) + ", outside " + (c.ensemble ? "member " + std::to_string(which) : std::string("the map")) + " (" +
+                std::to_string(least) + " cells)");
+  // the first position that repeats an earlier one. A short list is sorted with its positions (nothing of the map's size is touched
+  // for sixteen sites); a longer one sets a bit per cell of the smallest member, O(n) for a list of any length. (At 4096^2 sorting
+  // 65 536 entries added 2.5 ms to a call, the 2 MB of bits far less: the sort is for lists a 4096th of the map and shorter.)
+  uint32_t rep = 0xFFFFFFFFu;
+  if ((uint64_t)n * 4096u < least) {
+    std::vector<uint64_t> key(n);
+    for (uint32_t i = 0; i < n; i++) key[i] = ((uint64_t)cells[i] << 32) | i;
+    std::sort(key.begin(), key.end());
+    for (uint32_t i = 1; i < n; i++)   // (of a run of equal cells the second entry is its first repeat)
+      if ((key[i] >> 32) == (key[i - 1] >> 32) && (i < 2 || (key[i - 2] >> 32) != (key[i] >> 32))) rep = std::min(rep, (uint32_t)key[i]);
+  } else {
+    std::vector<uint64_t> seen(n ? (size_t)((least + 63) / 64) : 0u, 0ull);
+    for (uint32_t i = 0; i < n && rep == 0xFFFFFFFFu; i++) {
+      uint64_t& w = seen[cells[i] >> 6];
+      const uint64_t bit = 1ull << (cells[i] & 63u);
+      if (w & bit) rep = i;
+      w |= bit;
+    }
+  }
+  if (rep != 0xFFFFFFFFu) {
+    uint32_t of = 0u;
+    while (cells[of] != cells[rep]) of++;
+    return no("cells[" + std::to_string(rep) + "] repeats cells[" + std::to_string(of) + "] (cell " + std::to_string(cells[rep]) + "): the sites are distinct");
+  }
+  return true;
+}
+int smx_proximity(smx_ctx* ctx, const uint32_t* cells, uint32_t n, smx_proximity_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nrecords, uint32_t* hist,
+                  uint32_t nbins, uint32_t bin_width, uint32_t* nearest, uint32_t* group, uint32_t* dist2) {
+  if (!ctx) return -2;
+  const AnalysisCall c = call_on("smx_proximity", ctx);
+  int rc;
+  const uint32_t some_count = 0u;   // (a counts pointer for the checks in front of it: a strip context and struct_size 0 are refused before it is looked at)
+  if (c.partial || struct_size == 0) { analysis_begin(c, "smx_proximity_record", "nrecords", struct_size, nullptr, &some_count, nullptr, 0u, rc); return rc; }
+  if (!prox_args_ok(c, cells, n, out, cap, nrecords, hist, nbins, bin_width, rc)) return rc;
+  if (!analysis_begin(c, "smx_proximity_record", "nrecords", struct_size, nullptr, nrecords, out, cap, rc)) return rc;
+  roctx_range rr("soilmx:proximity");
+  HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
+  return prox_run(c, ctx->proximity, cells, n, out, struct_size, cap, nrecords, hist, nbins, bin_width, nearest, group, dist2);
+}
+int smx_ensemble_proximity(smx_ensemble* e, const uint32_t* cells, uint32_t n, smx_proximity_record* out, uint64_t struct_size, uint32_t cap_per_member, uint32_t* nrecords,
+                           uint32_t* hist, uint32_t nbins, uint32_t bin_width) {
+  if (!e) return -2;
+  const AnalysisCall c = call_on("smx_ensemble_proximity", e);
+  int rc;
+  const uint32_t some_count = 0u;   // (nrecords is prox_args_ok's to check, behind the empty ensemble)
+  if (!analysis_begin(c, "smx_proximity_record", "nrecords", struct_size, nullptr, &some_count, nullptr, 0u, rc)) return rc;   // (an empty ensemble: 0 before anything is looked at)
+  if (!prox_args_ok(c, cells, n, out, cap_per_member, nrecords, hist, nbins, bin_width, rc)) return rc;
+  roctx_range rr("soilmx:ensemble_proximity");
+  HIPCHK(e, hipSetDevice(e->device));
+  return prox_run(c, e->proximity, cells, n, out, struct_size, cap_per_member, nrecords, hist, nbins, bin_width, nullptr, nullptr, nullptr);
 }
 int smx_dispersal(smx_ctx* ctx, uint32_t exponent, smx_dispersal_record* out, uint64_t struct_size, uint32_t cap, uint32_t* nbasins, uint64_t* area, uint32_t* donors,
                   uint32_t* receivers) {

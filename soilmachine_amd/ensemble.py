@@ -340,6 +340,30 @@ class Ensemble:
                 r["lit_cells"] = [int(counts[i * ns + k]) for k in range(ns) if sl[k].direction == r["direction"]]
         return res
 
+    def proximity(self, cells=None, bins: int = 0, bin_width: int = 1) -> list:
+        """The proximity records of every member (``smx_ensemble_proximity``: the same launches whatever the member count): one list of
+        dicts per member, in member order, each as ``Layermap.proximity(cells, bins=bins, bin_width=bin_width)`` gives it. ``cells``
+        None: the wet cells of every member, grouped by its lakes (two calls, a count and the fetch sized by the largest count); else
+        ONE list serves every member, as flat indices into each member's own plane: give ``(x, y)`` pairs only where all members have
+        the same ``dimy`` (the first member's is used). Every listed cell has to lie inside every member."""
+        self._check_members()
+        nm = len(self.members)
+        cl, n = capi.proximity_cells(cells, self.members[0].dimy if nm else 1)
+        bins, bin_width = int(bins), int(bin_width)
+        counts = np.zeros(max(1, nm), np.uint32)
+        cap = n
+        if cl is None:
+            self._chk(self.L.smx_ensemble_proximity(self.h, None, 0, None, C.sizeof(capi.Proximity), 0, capi.ptr(counts), None, 0, 1))
+            cap = int(counts[:nm].max()) if nm else 0
+        out = (capi.Proximity * max(1, nm * cap))()
+        hist = np.zeros((max(1, nm), cap, bins), np.uint32) if bins else None
+        self._chk(self.L.smx_ensemble_proximity(self.h, capi.ptr(cl), n, out if cap else None, C.sizeof(capi.Proximity), cap, capi.ptr(counts), capi.ptr(hist), bins, bin_width))
+        res = [[out[i * cap + k].as_dict() for k in range(min(cap, int(counts[i])))] for i in range(nm)]
+        for i, recs in enumerate(res if bins else ()):
+            for k, r in enumerate(recs):
+                r["buffers"] = hist[i, k].copy()
+        return res
+
     def dispersal(self, exponent: int = 1, cap: int | None = None) -> list:
         """The dispersed-flow records of every member (``smx_ensemble_dispersal``: the same launches whatever the member count): one
         list of dicts per member, in member order, each as ``Layermap.dispersal(exponent)`` gives it, record k for basin k of

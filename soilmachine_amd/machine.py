@@ -411,6 +411,49 @@ class Layermap:
         planes = {k: v.reshape((len(ds), self.dimx, self.dimy) if k in ("slope", "step") else (self.dimx, self.dimy)) for k, v in got.items()}
         return (recs, planes) if planes else recs
 
+    def proximity(self, cells=None, nearest: bool = False, group: bool = False, dist2: bool = False, bins: int = 0, bin_width: int = 1, cap: int | None = None):
+        """How far every cell is from water or from a listed cell as the crow flies (``smx_proximity``): the exact Euclidean distance
+        transform. ``cells`` None: the SITES are the wet cells, grouped by the lakes of ``lakes()`` (group k is lake k); else a
+        sequence of distinct flat indices x*dimy + y or of ``(x, y)`` pairs, site ``cells[i]`` being group i. Every cell belongs to
+        the ZONE of its nearest site's group -- the smaller squared distance, then the smaller site cell index. One dict per group,
+        in group order -- ``site`` (the listed cell, or the lake's ``first_cell``), ``sites`` (1, or the lake's cells), ``cells`` (the
+        size of the zone), ``dist2_max`` / ``farthest_cell`` (the largest squared distance in the zone and the smallest cell that
+        has it), ``flags`` (1: the zone touches the map border), ``dist2_sum`` (exact) and the bounding box ``x0, y0, x1, y1``.
+        ``bins`` (1 to 64) with ``bin_width``: every dict also gets ``buffers`` -- ``buffers[b]`` counts the zone's cells with
+        ``b * bin_width <= floor(sqrt(dist2)) < (b + 1) * bin_width``, the last bin everything beyond. With a plane asked for the
+        result is ``(records, planes)``, ``planes`` a dict of (dimx, dimy) uint32 arrays for EVERY cell: ``nearest`` (the cell index
+        of the nearest site), ``group`` and ``dist2`` (the squared distance in cells; take the root for a distance); all three are
+        0xFFFFFFFF on a map without a site. A list: one call; water: ``cap`` None makes two, a count and the fetch, else at most
+        ``cap`` lakes get a record (the planes are whole either way). Sees every tick queued before it and changes nothing.
+
+        A riparian buffer of five cells around the lakes, and the distance to the nearest channel as a covariate next to HAND::
+
+            recs, pl = m.proximity(dist2=True)
+            shore = pl["dist2"] <= 25
+            channels = np.flatnonzero(m.streams(256, order=True)[1]["order"])
+            away = np.sqrt(m.proximity(channels, dist2=True)[1]["dist2"])
+        """
+        cl, n = capi.proximity_cells(cells, self.dimy)
+        bins, bin_width = int(bins), int(bin_width)
+        count = C.c_uint32()
+        wanted = [("nearest", nearest), ("group", group), ("dist2", dist2)]
+        if cl is not None:
+            cap = n
+        elif cap is None:
+            self._chk(self.L.smx_proximity(self.h, None, 0, None, C.sizeof(capi.Proximity), 0, C.byref(count), None, 0, 1, None, None, None))
+            cap = int(count.value)
+        cap = int(cap)
+        out = (capi.Proximity * max(1, cap))()
+        hist = np.zeros((cap, bins), np.uint32) if bins else None
+        got = {k: np.zeros(self.dimx * self.dimy, np.uint32) for k, want in wanted if want}
+        self._chk(self.L.smx_proximity(self.h, capi.ptr(cl), n, out if cap else None, C.sizeof(capi.Proximity), cap, C.byref(count), capi.ptr(hist), bins, bin_width,
+                                       *[capi.ptr(got.get(k)) for k, _ in wanted]))
+        recs = [out[k].as_dict() for k in range(min(cap, int(count.value)))]
+        for k, r in enumerate(recs if bins else ()):
+            r["buffers"] = hist[k].copy()
+        planes = {k: v.reshape(self.dimx, self.dimy) for k, v in got.items()}
+        return (recs, planes) if planes else recs
+
     def dispersal(self, exponent: int = 1, area: bool = False, donors: bool = False, receivers: bool = False, cap: int | None = None):
         """Dispersed flow (``smx_dispersal``): the multiple-flow-direction contributing area next to the D8 one of ``drainage()``. A
         dry cell splits its water over ALL lower neighbours in proportion to slope ** ``exponent`` (0 to 16; a diagonal step counts
